@@ -11,9 +11,15 @@ Multi-GPU (torchrun, one process per GPU): frames are independent, so every rank
 batch (weak scaling) with no collective on the data path; only the timing barrier / max-reduce uses
 the process group. value = pixels processed by all ranks / max-over-ranks time.
 
-Also reported: the roofline of the per-pixel kernel (HIP-event timed, algorithmic bytes = 1 B/px of
-frame input; traffic = measured FETCH_SIZE from profiles/r03_traffic.json), the north-star shape
-(Shi-Tomasi 1920x1080 batch 256), and the CPU baseline (the oracle restatement on a bounded sample of
+A plain run does only that: set up, warm up, time exactly `--steps` steps, print the line (metric, value,
+ms_per_step, config, rank layout). `--dump-outputs DIR` also writes what the last timed step returned
+(DIR/xy.npy, DIR/counts.npy, float32); the frames are seeded, so the same arguments give the same files.
+
+With `--full` the line also carries: the roofline of the per-pixel kernel (HIP-event timed, algorithmic
+bytes = 1 B/px of frame input; traffic = measured FETCH_SIZE from the latest profiles/rNN_traffic.json),
+the tie-order and pipelined variants of the headline, the north-star shape (Shi-Tomasi 1920x1080 batch
+256), the other BASELINE configs (FAST + BRIEF, LSD map and lines, SuperPoint), the copy ceilings, the
+PCIe-inclusive rates, and the CPU baseline beside every leg (the oracle restatement on a bounded sample of
 the same workload: single thread, and a pool of up to 16 threads).
 """
 from __future__ import annotations
@@ -193,7 +199,16 @@ def parse():
     p.add_argument("--no-superpoint", action="store_true", help="skip the SuperPoint (configs[4]) leg")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every other leg (kernel roofline, tie order, pipelined serving, "
+                        "north star, configs[2..4], copy ceilings, PCIe-inclusive rates, CPU baselines); off: only "
+                        "the headline is set up, timed and reported")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed headline step returned (xy, counts) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def make_frames(torch, pattern, n, rows, cols, seed, device, period=16):
@@ -326,6 +341,30 @@ def run_config(torch, fd, dev, detector, rows, cols, batch, pool, need, dist, pa
 
     secs, done = timed_graph(torch, step, steps, warmup, use_graph, per_graph=0, barrier=barrier)
     return secs, done, frames_pool, (xy, cnt)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # all dumped arrays together
+
+
+def dump_outputs(path, xy, cnt, rank=0):
+    """--dump-outputs: the headline's (xy, counts) as the last timed step left them, as float32
+    <path>/xy.npy [frames, stride, 2] and <path>/counts.npy [frames] (ranks above 0 add a _rank<r>
+    suffix). Rows of xy past a frame's count are unspecified by the API and are written as zeros, so
+    that two runs on the same inputs give identical files. A batch too large for the size limit is cut
+    to a fixed, seeded sample of its frames (their indices go to <path>/frames.npy)."""
+    xy = xy.detach().cpu().numpy().astype(np.float32)
+    cnt = cnt.detach().cpu().numpy()
+    b, stride = xy.shape[:2]
+    xy[np.arange(stride)[None, :] >= cnt[:, None]] = 0.0
+    arrays = {"xy": xy, "counts": cnt.astype(np.float32)}
+    per_frame = xy[0].nbytes + 8 if b else 0
+    if b * per_frame > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(20240611).choice(b, DUMP_LIMIT_BYTES // per_frame, replace=False))
+        arrays = {"xy": xy[keep], "counts": arrays["counts"][keep], "frames": keep.astype(np.float32)}
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def tie_frames(fd, dev, detector, frames_pool, need, dist):
@@ -918,13 +957,39 @@ def main():
     # ---- headline workload (per rank: its own frames; weak scaling) -------------------------------
     barrier = dist.barrier if world > 1 else None
     with phase(torch, "headline"):
-        secs, done, pool, _ = run_config(torch, fd, dev, args.detector, args.rows, args.cols, args.batch, args.pool,
-                                         args.need, args.dist, args.pattern, args.steps, args.warmup,
-                                         not args.no_graph, seed=1234 + 1000003 * rank, barrier=barrier)
+        secs, done, pool, headline_out = run_config(
+            torch, fd, dev, args.detector, args.rows, args.cols, args.batch, args.pool, args.need, args.dist,
+            args.pattern, args.steps, args.warmup, not args.no_graph, seed=1234 + 1000003 * rank, barrier=barrier)
     secs_max = max_over_ranks(secs, dist if world > 1 else None, dev if backend == "nccl" else None)
     px_step = args.batch * args.rows * args.cols
     value = world * done * px_step / secs_max / 1e6  # Mpix/s, all ranks
     ms_per_step = secs_max / done * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *headline_out, rank=rank)
+
+    out = {
+        "metric": "Mpix/s corner-response+NMS, 640x480 gray batch, 1/2/4/8 MI355X",
+        "value": round(value, 2), "unit": "Mpix/s", "n_gpus": world, "steps": done, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8->i32/f32", "data": "synthetic (seeded u8 %s frames generated on GPU)" % args.pattern,
+        "config": {"workload": f"{args.detector} response+NMS + grid NMS (greedy min-distance select), "
+                               f"{args.cols}x{args.rows} gray, batch {args.batch}/GPU (BASELINE configs[1])",
+                   "detector": args.detector, "rows": args.rows, "cols": args.cols, "global_batch": args.batch * world,
+                   "need": args.need, "min_feature_distance": args.dist, "min_valid_response": THR[args.detector],
+                   "parallelism": f"frame-sharded x{world} (no collective)", "graph": not args.no_graph},
+    }
+    out["ranks"], out["process_group"] = rank_layout(dist, world, rank, local, dev_index, ndev)
+    if args.full:
+        full_legs(torch, fd, dist, args, out, pool, ms_per_step, px_step, dev, world, rank, backend, barrier)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_legs(torch, fd, dist, args, out, pool, ms_per_step, px_step, dev, world, rank, backend, barrier):
+    """--full: every leg beside the headline, added to `out` (the line main() prints)."""
+    from feature_detector_amd.shard import max_over_ranks
 
     # ---- per-kernel timing for the roofline (rank-local, same stream) -----------------------------
     with phase(torch, "roofline_kernel"):
@@ -972,21 +1037,12 @@ def main():
                "phases": select_phase_cycles()}
     del pool
 
-    out = {
-        "metric": "Mpix/s corner-response+NMS, 640x480 gray batch, 1/2/4/8 MI355X",
-        "value": round(value, 2), "unit": "Mpix/s", "n_gpus": world, "steps": done, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8->i32/f32", "data": "synthetic (seeded u8 %s frames generated on GPU)" % args.pattern,
-        "config": {"workload": f"{args.detector} response+NMS + grid NMS (greedy min-distance select), "
-                               f"{args.cols}x{args.rows} gray, batch {args.batch}/GPU (BASELINE configs[1])",
-                   "detector": args.detector, "rows": args.rows, "cols": args.cols, "global_batch": args.batch * world,
-                   "need": args.need, "min_feature_distance": args.dist, "min_valid_response": THR[args.detector],
-                   "parallelism": f"frame-sharded x{world} (no collective)", "graph": not args.no_graph},
+    out.update({
         "roofline": roofline,
         "latency": latency,
         "kernels": kernels,
         "ties": ties_headline,
-    }
+    })
     if args.batch == 1 and not args.no_graph:
         with phase(torch, "headline_pipelined"):
             p_ms, p_frames = run_pipelined(torch, fd, dev, args.detector, args.rows, args.cols, args.need, args.dist,
@@ -1056,7 +1112,6 @@ def main():
             out["config4_lsd_map"] = run_lsd(torch, fd, dev, seed=4242 + 7 * s0, batch=e0 - s0,
                                              global_batch=STRONG_GLOBAL["config4_lsd_map"], barrier=barrier,
                                              max_fn=max_fn)
-    out["ranks"], out["process_group"] = rank_layout(dist, world, rank, local, dev_index, ndev)
     with phase(torch, "device_copy"):
         cb = copy_bandwidth(torch, dev)
         out["device_copy_gbs"] = cb.pop("device_copy_gbs")
@@ -1132,10 +1187,6 @@ def main():
                              label="FeatureLineDetector::DetectGoodFeatures restatement (oracle/fd_oracle_lines.cpp, "
                                    "the reference's data structures), 1920x1080 64-px checker")
             out["config4_lsd_map"]["lines"]["cpu_baseline"], out["config4_lsd_map"]["lines"]["cpu_baseline_pool"] = lb, lp
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 """CPU: the BRIEF pattern table and the oracle's BRIEF restatement.
 
 * The generated GPU pattern table (feature_detector_amd/csrc/fd_brief_pattern.inc) equals the
-  reference's pattern_idx_ (descriptor_brief.cpp:52-309), re-parsed from the reference source when it is
-  present (this container; the GPU box has no /root/reference).
+  reference's pattern_idx_ (descriptor_brief.cpp:52-309): its 1024 offsets have the fingerprint (count,
+  range, sums, SHA-256) recorded from the reference source in tests/golden/brief_pattern.json.
 * The C oracle (oracle/fd_oracle.cpp orc_brief) equals a second, independent restatement written here
   with numpy float32 scalars (IEEE single, no FMA), op for op after descriptor_brief.cpp:8-50, for both
   samplers, integral and fractional keypoints, several lengths and patch sizes.
@@ -10,6 +10,8 @@
   all-zero descriptor (:10, :15-17, :30); at integer keypoints the moments do not depend on the sampler.
 The sampled bits themselves are parity-unpinned (the reference's float sampler is un-vendored).
 """
+import hashlib
+import json
 import os
 import sys
 
@@ -17,7 +19,6 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_BRIEF = "/root/reference/src/feature_descriptor/descriptor_brief.cpp"
 F = np.float32
 
 
@@ -26,15 +27,19 @@ def orc(oracle):
     return oracle
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BRIEF), reason="reference source not present")
 def test_pattern_table_matches_reference():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_brief_pattern as g
 
-    ref = g.parse_pattern(REF_BRIEF)
+    with open(os.path.join(ROOT, "tests", "golden", "brief_pattern.json")) as f:
+        ref = json.load(f)
     words = g.read_inc()
     assert len(words) == 256
-    assert g.unpack(words) == ref
+    vals = g.unpack(words)
+    assert g.pack(vals) == words
+    assert len(vals) == ref["values"] and min(vals) == ref["min"] and max(vals) == ref["max"]
+    assert sum(vals) == ref["sum"] and sum(abs(v) for v in vals) == ref["abs_sum"]
+    assert hashlib.sha256(np.array(vals, np.int8).tobytes()).hexdigest() == ref["sha256_int8"]
 
 
 def test_pattern_table_shape(orc):

@@ -1,6 +1,6 @@
 """CPU: the PNG front end (fd_png_info / fd_png_decode) against a numpy reference
 decoder on encoder-made images (every row filter, every supported colour type), the reference's
-examples/image.png fixture and, when the reference tree is present, its examples/image2.png (RGB).
+examples/image.png fixture and its examples/image2.png (RGB), both kept under tests/golden/.
 The colour -> gray conversion of the reference's Visualizor2D::LoadImage is un-vendored: the library's
 BT.601 fixed-point rule is checked for self-consistency only (parity unpinned)."""
 import os
@@ -31,11 +31,11 @@ def test_image_png_fixture(image_png):
     assert np.array_equal(got, image_png)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/examples/image2.png"), reason="reference tree absent")
 def test_reference_image2_rgb():
     import feature_detector_amd as fd
 
-    data = open("/root/reference/examples/image2.png", "rb").read()
+    with open(os.path.join(os.path.dirname(__file__), "golden", "image2.png"), "rb") as f:
+        data = f.read()
     assert fd.png_info(data) == (480, 640, 3)
     got = fd.load_png(data)
     assert np.array_equal(got, gray_of(decode_png(data)))
