@@ -9,35 +9,9 @@
 
 #include <type_traits>
 
-// Shi-Tomasi's gate as a clamp (corner_response_fp; A/B switch)
-#ifndef FD_LP_GFMA
-#define FD_LP_GFMA 1
-#endif
-
 namespace fdk {
 
 namespace {
-
-// corner_response2<KIND, G1 = true> for k_corner_lp: Shi-Tomasi returns 2r = gate + sqrt(d*d + 4b*b),
-// i.e. the reference's fl(fl(gate + common) * 0.5) times two (exact), one multiply fewer per pixel.
-template <int KIND>
-__device__ __forceinline__ f2 corner_response_lp(uint32_t sxx0, uint32_t sxx1, uint32_t syy0, uint32_t syy1,
-                                                 uint32_t sxy0, uint32_t sxy1, float thr) {
-    if constexpr (KIND == 0) return corner_response2<0, true>(sxx0, sxx1, syy0, syy1, sxy0, sxy1, thr);
-    const f2 bxx = f2{__uint_as_float(sxx0), __uint_as_float(sxx1)};
-    const f2 byy = f2{__uint_as_float(syy0), __uint_as_float(syy1)};
-    const f2 fxy = f2{__uint_as_float(sxy0), __uint_as_float(sxy1)} - 12582912.0f;
-    const f2 a = __builtin_elementwise_fma(bxx, f2{kInvCnt, kInvCnt}, f2{-8388608.0f * kInvCnt, -8388608.0f * kInvCnt});
-    const f2 c = __builtin_elementwise_fma(byy, f2{kInvCnt, kInvCnt}, f2{-8388608.0f * kInvCnt, -8388608.0f * kInvCnt});
-    const f2 gate = a + c;
-    const f2 b = fxy * kInvCnt;
-    const f2 d = a - c;
-    const f2 r2 = gate + sqrt_rn_rsq2(__builtin_elementwise_fma(b * b, f2{4.0f, 4.0f}, d * d));
-    f2 res;
-    res.x = gate.x > thr ? r2.x : 0.0f;
-    res.y = gate.y > thr ? r2.y : 0.0f;
-    return res;
-}
 
 // Byte K of w as a float (v_cvt_f32_ubyteK; as asm so that differences of converted bytes stay float
 // subtractions instead of becoming an integer subtraction plus a conversion).
@@ -59,8 +33,9 @@ __device__ __forceinline__ float add_from_right_f(float a, float b) {
     return r;
 }
 
-// The same responses from float tensor sums (exact integers < 2^24 held as floats, FD_LP_FP), G1 form,
-// gate test as a sign mask (thr - gate < 0 <=> gate > thr): full-rate float ops only.
+// corner_response2<KIND, G1 = true> from float tensor sums (exact integers < 2^24 held as floats). Shi-Tomasi
+// returns 2r = gate + sqrt(d*d + 4b*b), i.e. the reference's fl(fl(gate + common) * 0.5) times two (exact),
+// one multiply fewer per pixel. Harris: gate test as a sign mask (thr - gate < 0 <=> gate > thr): full-rate float ops only.
 // Shi-Tomasi: sqrt_rn_rsq2 (fd_device.h), verified exhaustively. (Folding its halving into rsq's output
 // modifier was tried: gfx950 does not apply div:2 to v_rsq_f32 -- 1-ulp errors.) This translation unit
 // flushes f32 denormals; none occur (products and sums are integers, q is 0 or >= 2^-54).
@@ -76,7 +51,6 @@ __device__ __forceinline__ f2 corner_response_fp(f2 sxx, f2 syy, f2 sxy, float t
         gate = a + c;
         const f2 d = a - c;
         r = gate + sqrt_rn_rsq2(__builtin_elementwise_fma(b * b, f2{4.0f, 4.0f}, d * d));
-#if FD_LP_GFMA
         // The gate as a clamp: min(2r, fl(66 gate - 64 thr)). gate > thr: 66g - 64t = 2g + 64(g - t) >=
         // 2g + 32 ulp(g) > 2r (the tensor is positive semidefinite, so sqrt(d^2 + 4b^2) <= gate up to ~6
         // ulp of rounding), i.e. 2r itself. gate <= thr: the value is <= 2 gate <= 2 thr, which neither
@@ -87,7 +61,6 @@ __device__ __forceinline__ f2 corner_response_fp(f2 sxx, f2 syy, f2 sxy, float t
         res.x = __builtin_fminf(r.x, cl.x);
         res.y = __builtin_fminf(r.y, cl.y);
         return res;
-#endif
     }
     const f2 g = f2{thr, thr} - gate;  // < 0 exactly when gate > thr
     f2 res;
@@ -95,14 +68,6 @@ __device__ __forceinline__ f2 corner_response_fp(f2 sxx, f2 syy, f2 sxy, float t
     res.y = __int_as_float(__float_as_int(r.y) & (__float_as_int(g.y) >> 31));
     return res;
 }
-
-#ifndef FD_LP_FP
-#define FD_LP_FP 1
-#endif
-#ifndef FD_LP_PKQ
-#define FD_LP_PKQ 1
-#endif
-
 
 // ---------------------------------------------------------------------------------------------------
 // K1 (list mode, lane-private emission): the per-pixel kernel of fd_points_detect / fd_points_response.
@@ -122,20 +87,16 @@ __device__ __forceinline__ f2 corner_response_fp(f2 sxx, f2 syy, f2 sxy, float t
 // Only for thr >= 0 (the single-gate form); negative thresholds use k_corner.
 // ---------------------------------------------------------------------------------------------------
 constexpr int kLpSlots = FD_LP_SLOTS;  // lane-private slots per lane (LDS: 8 B x 64 lanes each)
-// With the selection histogram (16 KiB) the workgroup's LDS is slots + histogram: FD_LP_SLOTS_H slots
-// keep it (with the sorted-segment words) under 40 KiB: 4 workgroups per CU instead of 3 at 48 KiB.
-#ifndef FD_LP_SLOTS_H
-#define FD_LP_SLOTS_H 11
-#endif
+// With the selection histogram (16 KiB) the workgroup's LDS is slots + histogram: 11 slots keep it (with
+// the sorted-segment words) under 40 KiB: 4 workgroups per CU instead of 3 at 48 KiB.
+constexpr int kLpSlotsHist = 11;
 template <bool HIST>
-constexpr int lp_slots() { return HIST ? FD_LP_SLOTS_H : kLpSlots; }
+constexpr int lp_slots() { return HIST ? kLpSlotsHist : kLpSlots; }
 
 // Occupancy the register allocation must allow: LDS admits 5 workgroups (20 waves) per CU without the
-// histogram, 4 with it (FD_LP_SLOTS_H = 11); the allocator then keeps <= 96 / <= 128 VGPRs (8 columns
+// histogram, 4 with it (kLpSlotsHist); the allocator then keeps <= 96 / <= 128 VGPRs (8 columns
 // per lane and the unaligned no-histogram variants would spill at those limits: no target).
-#ifndef FD_LP_WAVES
 #define FD_LP_WAVES(PX, HIST, ALIGNED) __attribute__((amdgpu_waves_per_eu((PX) == 8 ? 1 : (HIST) || !(ALIGNED) ? 4 : 5)))
-#endif
 
 template <int PX>
 struct LpGeom {
@@ -169,19 +130,6 @@ __device__ __forceinline__ void lp_load_row(uint32_t (&w)[LpGeom<PX>::NW], __amd
 #pragma unroll
         for (int q = 0; q < LpGeom<PX>::NW; ++q) w[q] = load_px4<ALIGNED>(r, off + 4 * q);
     }
-}
-
-// Byte j (compile-time, -LB <= j < PX + LB) of the row window [L | P | R]: L = the left lane's last
-// LB columns, R = the right lane's first LB columns.
-template <int PX>
-__device__ __forceinline__ int lp_byte(uint32_t L, const uint32_t (&P)[LpGeom<PX>::NW], uint32_t R, int j) {
-    constexpr int LB = LpGeom<PX>::LB;
-    uint32_t w;
-    int b;
-    if (j < 0) w = L, b = j + LB;
-    else if (j < PX) w = P[j >> 2], b = j & 3;
-    else w = R, b = j - PX;
-    return static_cast<int>((w >> (8 * b)) & 0xFFu);
 }
 
 template <int PX>
@@ -227,8 +175,8 @@ __device__ __forceinline__ void lp_flush(uint32_t &n, const uint32_t *sl, const 
             const float r = lp_resp<KIND>(sl, j);
             if (hist) atomicAdd(&hist[((float_key(r) - a.key_base) << a.key_lz) >> 20], 1u);
             const uint32_t pos4 = static_cast<uint32_t>(mbcnt64(b, static_cast<int>(off))) << 2;
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rr, static_cast<int>(pos4), 0, FD_LIST_NT ? 2 : 0);
-            __builtin_amdgcn_raw_buffer_store_b32(sl[j * 128 + 64], ri, static_cast<int>(pos4), 0, FD_LIST_NT ? 2 : 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rr, static_cast<int>(pos4), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(sl[j * 128 + 64], ri, static_cast<int>(pos4), 0, 0);
         }
         off += static_cast<uint32_t>(popc64(b));
     }
@@ -353,19 +301,12 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
         const float thr_n = (KIND == 1 ? 2.0f : 1.0f) * a.thr;
         const float thrv = (lane >= G::HL && lane <= 63 - G::HL) ? thr_n : __builtin_inff();
 
-#if FD_LP_FP
         f2 hxx[3][PX / 2], hyy[3][PX / 2], hxy[3][PX / 2];  // column pairs: the vertical sums are packed adds
         float fpx[3][PX];  // the rows in use as floats, same 3-slot roles as the sums
-#else
-        uint32_t hxx[3][PX], hyy[3][PX], hxy[3][PX];
-#endif
         float rsp[3][PX];
-#if FD_LP_FP
         // vertical pair sums shared by two consecutive output rows: an even step forms
         // h(ri-2) + h(ri-1) and adds h(ri-3), the next step adds h(ri) to the same pair (exact integers)
         f2 pxx[PX / 2], pyy[PX / 2], pxy[PX / 2];
-#endif
-#if FD_LP_FP
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -373,12 +314,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                 if (m % 2 == 0) hxx[s][m / 2] = hyy[s][m / 2] = hxy[s][m / 2] = f2{0.0f, 0.0f};
                 fpx[s][m] = rsp[s][m] = 0.0f;
             }
-#else
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int m = 0; m < PX; ++m) hxx[s][m] = hyy[s][m] = hxy[s][m] = 0, rsp[s][m] = 0.0f;
-#endif
 
         const int n_in = (y1 - y0) + 6;
         uint32_t ring[6][NW];
@@ -399,12 +334,7 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                 const int ri = y0 - 3 + i0 + t;
                 lp_load_row<PX, ALIGNED>(ring[(t + 3) % 6], rs, (ri + 3) * cols + c0);
                 const uint32_t(&P_s)[NW] = ring[t];
-#if !FD_LP_FP
-                const uint32_t(&P_su)[NW] = ring[(t + 4) % 6];
-                const uint32_t(&P_sc)[NW] = ring[(t + 5) % 6];
-#endif
 
-#if FD_LP_FP
                 // row ri as floats (each row is converted once and used at three steps)
 #pragma unroll
                 for (int m = 0; m < PX; m += 4) {
@@ -419,7 +349,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                 // float integers; the halo pixels and the halo columns' products from the neighbour lanes
                 const float fL = from_left_f(fpx[sc][PX - 1]), fR = from_right_f(fpx[sc][0]);
                 float qxx[PX + 2], qyy[PX + 2], qxy[PX + 2];
-#if FD_LP_PKQ
                 // column pairs: iy and the three products as packed ops (2 results per issue slot;
                 // separate full-rate ops pair up only when two waves offer them in the same cycle)
 #pragma unroll
@@ -432,16 +361,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                     qyy[m + 1] = pyy2.x, qyy[m + 2] = pyy2.y;
                     qxy[m + 1] = pxy2.x, qxy[m + 2] = pxy2.y;
                 }
-#else
-#pragma unroll
-                for (int m = 0; m < PX; ++m) {
-                    const float ix = (m + 1 < PX ? fpx[sc][m + 1] : fR) - (m > 0 ? fpx[sc][m - 1] : fL);
-                    const float iy = fpx[s][m] - fpx[su][m];
-                    qxx[m + 1] = ix * ix;
-                    qyy[m + 1] = iy * iy;
-                    qxy[m + 1] = ix * iy;
-                }
-#endif
                 qxx[0] = from_left_f(qxx[PX]);
                 qyy[0] = from_left_f(qyy[PX]);
                 qxy[0] = from_left_f(qxy[PX]);
@@ -462,34 +381,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                         hxy[sc][m / 2].y = add_from_right_f(txy, qxy[1]);
                     }
                 }
-#else
-                // gradients of row ri-1 (feature_point_harris_detector.cpp:35-62) and biased products at
-                // the lane's columns; the halo columns' products come from the neighbour lanes
-                const uint32_t Lc = from_left(P_sc[NW - 1]), Rc = from_right(P_sc[0]);
-                uint32_t qxx[PX + 2], qyy[PX + 2], qxy[PX + 2];
-                uint32_t bsq = kBiasSq, bxy = kBiasXy;
-                asm volatile("" : "+s"(bsq), "+s"(bxy));
-#pragma unroll
-                for (int m = 0; m < PX; ++m) {
-                    const int ix = lp_byte<PX>(Lc, P_sc, Rc, m + 1) - lp_byte<PX>(Lc, P_sc, Rc, m - 1);
-                    const int iy = lp_byte<PX>(0, P_s, 0, m) - lp_byte<PX>(0, P_su, 0, m);
-                    qxx[m + 1] = static_cast<uint32_t>(ix * ix) + bsq;
-                    qyy[m + 1] = static_cast<uint32_t>(iy * iy) + bsq;
-                    qxy[m + 1] = static_cast<uint32_t>(ix * iy) + bxy;
-                }
-                qxx[0] = from_left(qxx[PX]);
-                qyy[0] = from_left(qyy[PX]);
-                qxy[0] = from_left(qxy[PX]);
-                qxx[PX + 1] = from_right(qxx[1]);
-                qyy[PX + 1] = from_right(qyy[1]);
-                qxy[PX + 1] = from_right(qxy[1]);
-#pragma unroll
-                for (int m = 0; m < PX; ++m) {
-                    hxx[sc][m] = add3u(qxx[m], qxx[m + 1], qxx[m + 2]);
-                    hyy[sc][m] = add3u(qyy[m], qyy[m + 1], qyy[m + 2]);
-                    hxy[sc][m] = add3u(qxy[m], qxy[m + 1], qxy[m + 2]);
-                }
-#endif
 
                 // response of row rr = ri-2 (Shi-Tomasi: 2r)
                 const int rr = ri - 2;
@@ -497,7 +388,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                 float r[PX];
 #pragma unroll
                 for (int m = 0; m < PX; m += 2) {
-#if FD_LP_FP
                     const int k = m / 2;
                     f2 sxx, syy, sxy;
                     if constexpr (t % 2 == 0) {
@@ -513,13 +403,6 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                         sxy = pxy[k] + hxy[sc][k];
                     }
                     const f2 v = corner_response_fp<KIND>(sxx, syy, sxy, a.thr);
-#else
-                    const f2 v = corner_response_lp<KIND>(
-                        add3u(hxx[s][m], hxx[su][m], hxx[sc][m]), add3u(hxx[s][m + 1], hxx[su][m + 1], hxx[sc][m + 1]),
-                        add3u(hyy[s][m], hyy[su][m], hyy[sc][m]), add3u(hyy[s][m + 1], hyy[su][m + 1], hyy[sc][m + 1]),
-                        add3u(hxy[s][m], hxy[su][m], hxy[sc][m]), add3u(hxy[s][m + 1], hxy[su][m + 1], hxy[sc][m + 1]),
-                        a.thr);
-#endif
                     r[m] = v.x;
                     r[m + 1] = v.y;
                 }
@@ -557,11 +440,7 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                         const float xl = m == 0 ? lft : rsp[s][m - 1];
                         const float xr = m == PX - 1 ? rgt : rsp[s][m + 1];
                         const float nb = max3f(max3f(xl, xr, thrv), rsp[sc][m], rsp[su][m]);
-#if defined(FD_LP_KO) && FD_LP_KO == 1  // diagnostic build only: no emission (the knockout timing)
-                        asm volatile("" : : "v"(x), "v"(nb));
-#else
                         lp_emit(A, x, nb, id0 + m);
-#endif
                     }
                 }
         };

@@ -22,15 +22,6 @@ __device__ __forceinline__ bool grid_pk15(int rows, int cols, int d) { return ro
 __device__ __forceinline__ uint32_t grid_empty(int rows, int cols, int d) { return grid_pk15(rows, cols, d) ? 0x7FFF7FFFu : kEmpty; }
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));  // packed (x, y) of a (y << 16) | x position
 
-#ifndef FD_SEQ_CONFLICTS
-#define FD_SEQ_CONFLICTS 0
-#endif
-// greedy batch: ordered scalar pass up to this many conflicted lanes, else the fixed point. Sweep at the
-// headline (profiles/r03_select_rejected.txt): 0 (always the fixed point) 19.3-19.5 us, 2: 19.6-20.0,
-// 4: 19.5-19.7, 12: 20.1-20.2 -- the fixed point's passes (the longest conflict chain, ~2-3) cost less
-// than one ordered step per conflicted lane.
-constexpr int kSeqConflicts = FD_SEQ_CONFLICTS;
-
 // A batch's conflicted lanes (conf) decided by a fixed point on wave-uniform masks: each pass decides
 // every undecided lane whose earlier ok neighbours (C, already restricted to ok lanes) are all decided
 // -- accepted iff none of them was. Passes = the longest conflict chain; each decides at least the
@@ -193,20 +184,12 @@ __device__ __forceinline__ void greedy_chunk(const SelectArgs &a, int f, int cnt
         C &= m;
         // Resolution in scan order: a lane with no earlier ok neighbour in the batch is accepted; the
         // conflicted ones are decided by a fixed point, where each pass decides every lane whose earlier
-        // neighbours are all decided (passes = the longest chain) -- accepted iff none of them was. (With
-        // FD_SEQ_CONFLICTS > 0, up to that many conflicted lanes are instead decided one by one in
-        // ascending order on the scalar unit: slower at every threshold measured, see kSeqConflicts.)
+        // neighbours are all decided (passes = the longest chain) -- accepted iff none of them was. (Deciding
+        // up to 2, 4 or 12 conflicted lanes one by one in ascending order on the scalar unit instead measured
+        // slower at the headline, 19.5-20.2 vs 19.3-19.5 us: profiles/r03_select_rejected.txt.)
         const uint64_t conf = ballot(C != 0ull) & m;
         uint64_t acc_m = m & ~conf;
-        if (popc64(conf) <= kSeqConflicts) {
-            for (uint64_t rest = conf; rest; rest &= rest - 1ull) {
-                const int i = __builtin_ctzll(rest);
-                const uint64_t free_m = ballot((C & acc_m) == 0ull);
-                acc_m |= free_m & (1ull << i);
-            }
-        } else {
-            acc_m = resolve_batch(a, f, C, conf, acc_m);
-        }
+        if (conf != 0ull) acc_m = resolve_batch(a, f, C, conf, acc_m);
         gst(27);  // resolution
         // need cutoff (:67-69): features.size() >= need is checked after every append
         const uint32_t have = prior + static_cast<uint32_t>(acc);

@@ -11,14 +11,8 @@ namespace fdk {
 constexpr int kTileW = 248;
 constexpr int kSegCorner = kTileW / 2;  // strict 4-neighbour NMS: <= 1 candidate per 2 columns
 constexpr int kSegFast = kTileW;        // FAST has no NMS
-#ifndef FD_LIST_NT
-#define FD_LIST_NT 0  // candidate list stores with the nt (streaming) cache policy
-#endif
 constexpr int kSelectChunk = 2048;      // candidates sorted per greedy chunk (LDS)
-#ifndef FD_SELECT_THREADS
-#define FD_SELECT_THREADS 1024
-#endif
-constexpr int kSelectThreads = FD_SELECT_THREADS;  // k_select workgroup size (sorted segments: <= this many per frame)
+constexpr int kSelectThreads = 1024;    // k_select workgroup size (sorted segments: <= this many per frame)
 constexpr int kGridLdsCells = 16384;    // occupancy grid kept in LDS up to this many cells
 constexpr int kMaxOffsetSegs = 48;
 constexpr int kSegHead = 64;           // selection keys kept per sorted segment head (PointsArgs::seghead)
@@ -138,8 +132,6 @@ struct SelectArgs {
     int nseg;               // segments per frame
     uint64_t *wide_keys;  // [batch][kWideKeys] scratch of the wide pass, or null (one list pass per chunk)
     int wide_eager;       // wide pass with the first chunk (FAST) instead of at the first later list pass
-    int fast_sub;         // FAST's selection shape (k_select<.., true>, whole-superchunk sub-chunks) without a wide
-                          // pass (wide_keys null): the short lists of the emission cut
     // k_wide_cut + k_wide_gather (batch x wide_groups workgroups of 256 threads, before k_select): the wide pass of a
     // wide_eager frame spread over the frame's list, keys into wide_keys, their number into wide_count
     // (reset by k_select); null wide_count: k_select makes the pass itself, one workgroup per frame
@@ -154,7 +146,6 @@ struct SelectArgs {
     uint32_t *cut_next;
     const uint32_t *redo_status;
     int batch;  // frames of the call (the redo pass's workgroups loop over them)
-    int first_sub;     // sorted-segment corner frames: first chunk cut at one sub-chunk (kSubChunk keys)
     int grid_at_d0;    // distance 0 still tests the grid (1-pixel cells): caller lists may name a pixel twice
     int dup_keys;      // equal selection keys possible (caller lists): the orderings rank them stably
     uint64_t *stamps;  // diagnostic only (FD_SELECT_STAMPS): per-frame phase clocks, never read back by kernels
@@ -260,13 +251,11 @@ struct LsdArgs {
     float *norm, *angle;
     uint8_t *valid;
     int pitch;          // dense maps: entries per map row (>= cols-1; a multiple of 4 keeps the row stores aligned)
-    uint32_t *rowbits;  // [batch][chunks][words][cols-1]: valid rows of each (column, chunk), bit r - r0
-                        // (column fastest: a wave's stores and loads are contiguous)
-    int words;          // ceil(chunk_h / 32)
-    int chunk_fastest;  // k_lsd_map wave order: chunk index fastest (else strip fastest)
-    int scatter_cols;   // k_lsd_scatter columns per wave (16, 32 or 64)
+    uint32_t *rowbits;  // [batch][chunks][cols-1]: valid rows of each (column, chunk), bit r - r0 (chunk_h <= 32;
+                        // column fastest: a wave's stores and loads are contiguous)
     int32_t *col_cnt;   // [batch][chunks][cols-1]
-    int32_t *col_base;  // same layout, exclusive scan in column-major order (column outer, chunk inner)
+    int32_t *col_base;  // same size; only the chunk-0 row is written: per column, the exclusive scan of the
+                        // columns' totals (all chunks) in column order, i.e. where the column's run starts in the list
     int32_t *idx;
     int64_t idx_cap;
     int64_t *counts;

@@ -23,7 +23,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <thread>
@@ -38,11 +37,6 @@ constexpr float kPi = 3.14159265358979323846f;  // kPai (slam_basic_math.h)
 constexpr float k2Pi = 2.0f * kPi;               // k2Pai
 constexpr uint8_t kUsed = 1, kOccupied = 2, kSeen = 4;  // (kSeen: order_seeds' permutation check only)
 constexpr int kRing = 1000;  // CircularBuffer<PixelParam *, 1000> (feature_line_detector.h:76-77)
-#ifdef FD_LINES_PHASES
-}  // namespace
-std::atomic<long long> g_phase_ns[3];  // load (incl. sort), sort, grow + fit
-namespace {
-#endif
 
 float wrap_diff(float a, float b) {  // Utility::AngleDiffInRad (assumed: wrap a - b into [-pi, pi])
     float d = a - b;
@@ -92,15 +86,8 @@ public:
     // the frame's setup.
     template <typename GetOrder>
     int32_t run(const FrameList &fl, fd_lsd_rect *out, int32_t stride, uint8_t *used_out, GetOrder get_order) {
-#ifdef FD_LINES_PHASES  // diagnostic build only (tools/calib/lines_host_timing.cpp)
-        const auto t0 = std::chrono::steady_clock::now();
-#endif
         load(fl);
         order_seeds(get_order());
-#ifdef FD_LINES_PHASES
-        const auto t1 = std::chrono::steady_clock::now();
-        g_phase_ns[0] += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-#endif
         int32_t nrect = 0;
         for (const auto &seed : seeds_) {  // :27-46
             const int32_t s = seed.second;
@@ -120,9 +107,6 @@ public:
             if (nrect < stride) out[nrect] = r;
             ++nrect;
         }
-#ifdef FD_LINES_PHASES
-        g_phase_ns[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count();
-#endif
         if (used_out)
             for (int64_t k = 0; k < fl.n; ++k) used_out[k] = (state_[k] & kUsed) ? 1 : 0;
         for (int64_t k = 0; k < fl.n; ++k) mask_[static_cast<size_t>(fl.idx[k]) >> 6] = 0ull;  // clean for the next frame
@@ -160,9 +144,6 @@ private:
     // permutation of this frame's valid pixels in non-increasing norm; otherwise (a broken emulation,
     // a stale buffer), and without one, std::sort here.
     void order_seeds(const uint32_t *ord) {
-#ifdef FD_LINES_PHASES
-        const auto ts = std::chrono::steady_clock::now();
-#endif
         const size_t n = seeds_.size();
         bool ok = ord != nullptr;
         for (size_t k = 0; ok && k < n; ++k) {
@@ -189,9 +170,6 @@ private:
             std::sort(seeds_.begin(), seeds_.end(),
                       [](const std::pair<float, int32_t> &a, const std::pair<float, int32_t> &b) { return a.first > b.first; });
         }
-#ifdef FD_LINES_PHASES
-        g_phase_ns[1] += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ts).count();
-#endif
     }
 
     // TryToAddPixelIntoCandidates (:156-161) for the 8 neighbours of entry e, in the reference's order

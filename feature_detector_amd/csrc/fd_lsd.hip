@@ -178,9 +178,7 @@ __device__ __forceinline__ void lsd_map_tile(const LsdArgs &a, const int f, cons
     const auto ra = make_rsrc(amap, amap ? 4 * mbytes : 0u);
     const auto rv = make_rsrc(a.valid ? a.valid + mbase : nullptr, a.valid ? mbytes : 0u);
 
-#ifndef FD_LSD_STORE_AUX
-#define FD_LSD_STORE_AUX 2  // nt: streaming map stores (1.55 -> 1.43 ms at 1080p x256, profiles/r04_lsd_nt_ab.txt)
-#endif
+    constexpr int kStoreAux = 2;  // nt: streaming map stores (1.55 -> 1.43 ms at 1080p x256, profiles/r04_lsd_nt_ab.txt)
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     struct alignas(4) F4 { float x, y, z, w; };
     // one map row's 4 angle entries of this lane
@@ -188,7 +186,7 @@ __device__ __forceinline__ void lsd_map_tile(const LsdArgs &a, const int f, cons
         if constexpr (INTERIOR) {
             __builtin_amdgcn_raw_buffer_store_b128(
                 u4{__float_as_uint(av[0]), __float_as_uint(av[1]), __float_as_uint(av[2]), __float_as_uint(av[3])}, ra,
-                4 * (r * mp + c0), 0, FD_LSD_STORE_AUX);
+                4 * (r * mp + c0), 0, kStoreAux);
             return;
         }
         if (!a.angle) return;
@@ -208,8 +206,8 @@ __device__ __forceinline__ void lsd_map_tile(const LsdArgs &a, const int f, cons
             const int o = r * mp + c0;  // < 2^31: checked on the host
             __builtin_amdgcn_raw_buffer_store_b128(
                 u4{__float_as_uint(nv[0]), __float_as_uint(nv[1]), __float_as_uint(nv[2]), __float_as_uint(nv[3])}, rn,
-                4 * o, 0, FD_LSD_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(vb, rv, o, 0, FD_LSD_STORE_AUX);
+                4 * o, 0, kStoreAux);
+            __builtin_amdgcn_raw_buffer_store_b32(vb, rv, o, 0, kStoreAux);
             return;
         }
         const int64_t i = mbase + static_cast<int64_t>(r) * mp + c0;
@@ -278,7 +276,7 @@ __device__ __forceinline__ void lsd_map_tile(const LsdArgs &a, const int f, cons
             if (!INTERIOR && !colv[m]) nv[m] = 0.0f;
             vb |= static_cast<uint32_t>(vv[m]) << (8 * m);
             cnt[m] += vv[m] ? 1 : 0;
-            word[m] |= static_cast<uint32_t>(vv[m]) << ((rr - r0) & 31);
+            word[m] |= static_cast<uint32_t>(vv[m]) << (rr - r0);
         }
         put(rr, nv, vb);
         if (amap) {  // zero angle row in LDS; queue the valid pixels' (s, d) and row position
@@ -328,19 +326,14 @@ __device__ __forceinline__ void lsd_map_tile(const LsdArgs &a, const int f, cons
                 put_angle(r + i, av);
             }
         }
-        // rows r0 + 32k .. r0 + 32k + 31 share a bitmask word (kLsdGroup divides 32)
-        const int done = r + kLsdGroup - r0;
-        if ((done & 31) == 0 || r + kLsdGroup >= r1) {
+        if (r + kLsdGroup >= r1) {  // the chunk's last group: its row-bit word (chunk_h <= 32: one per chunk)
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                if (INTERIOR || colv[m])
-                    a.rowbits[((static_cast<int64_t>(f) * a.chunks + chunk) * a.words + ((done - 1) >> 5)) * mc + c0 + m] =
-                        word[m];
-                word[m] = 0;
+                if (INTERIOR || colv[m]) a.rowbits[(static_cast<int64_t>(f) * a.chunks + chunk) * mc + c0 + m] = word[m];
+                word[m] = 0;  // (dead from here on; left live across the loop it costs ~45 more SGPR spills)
             }
         }
     };
-    static_assert(32 % kLsdGroup == 0, "bitmask words hold whole groups");
     uint32_t A[kLsdGroup + 1], AE[kLsdGroup + 1], B[kLsdGroup + 1], BE[kLsdGroup + 1];
 #pragma unroll
     for (int i = 0; i <= kLsdGroup; ++i) ld(r0 + i, A[i], AE[i]);
@@ -363,19 +356,11 @@ template <bool ALIGNED>
 __global__ __launch_bounds__(256) void k_lsd_map(LsdArgs a) {
     __shared__ LsdQueue Q;
     int w = __builtin_amdgcn_readfirstlane(logical_block() * 4 + (threadIdx.x >> 6));
-    int strip, chunk;
-    if (a.chunk_fastest) {
-        chunk = w % a.chunks;
-        w /= a.chunks;
-        strip = w % a.strips4;
-        w /= a.strips4;
-    } else {
-        strip = w % a.strips4;
-        w /= a.strips4;
-        chunk = w % a.chunks;
-        w /= a.chunks;
-    }
-    const int f = w;
+    // consecutive waves take consecutive chunks of a strip
+    const int chunk = w % a.chunks;
+    w /= a.chunks;
+    const int strip = w % a.strips4;
+    const int f = w / a.strips4;
     if (f >= a.batch) return;
     if (strip * 256 >= 1 && strip * 256 + 255 <= a.cols - 3) lsd_map_tile<ALIGNED, true>(a, f, strip, chunk, Q);
     else lsd_map_tile<ALIGNED, false>(a, f, strip, chunk, Q);
@@ -422,8 +407,8 @@ __global__ __launch_bounds__(1024) void k_lsd_scan(LsdArgs a) {
 // pass 1 (a few words per lane instead of re-reading the valid map row by row).
 // Pass 3: the column-major valid list. The list holds each column's valid rows in order, chunk after
 // chunk, so one column's entries (all chunks) are one contiguous run starting at its chunk-0 base. A wave
-// owns NC columns and writes them one column at a time: its lanes take the column's (chunk, row word)
-// items in row order, a wave prefix of their popcounts places every lane's entries inside the run, so
+// owns NC columns and writes them one column at a time: its lanes take the column's chunks (one row-bit
+// word each) in row order, a wave prefix of their popcounts places every lane's entries inside the run, so
 // each store instruction covers a few adjacent cache lines (a lane per column, as before, made every
 // store touch 64 lines; the row-bit words of adjacent columns share lines, so the per-column loads hit
 // L1 after the first column of a line).
@@ -434,42 +419,38 @@ __global__ __launch_bounds__(256) void k_lsd_scatter(LsdArgs a) {
     const int strip = __builtin_amdgcn_readfirstlane(w4 % nstrips), f = __builtin_amdgcn_readfirstlane(w4 / nstrips);
     if (f >= a.batch) return;
     const int lane = lane_id();
-    const int rows = a.rows, cols = a.cols, mc = cols - 1, words = a.words, chunks = a.chunks;
-    const int items = chunks * words;
+    const int cols = a.cols, mc = cols - 1, chunks = a.chunks;
     const int64_t n = static_cast<int64_t>(mc) * chunks;
     const int32_t *cbase = a.col_base + static_cast<int64_t>(f) * n;  // [chunk][column] of this frame
-    const uint32_t *fbits = a.rowbits + static_cast<int64_t>(f) * chunks * words * mc;
+    const uint32_t *fbits = a.rowbits + static_cast<int64_t>(f) * n;
     int32_t *out = a.frame_base ? a.idx + a.frame_base[f] : a.idx + static_cast<int64_t>(f) * a.idx_cap;
     const int64_t cap = a.frame_base ? INT64_MAX : a.idx_cap;
     // the NC columns' run starts (lane = column), read once
     const int coll = lane < NC ? strip * NC + lane : -1;
     const int64_t basel = coll >= 1 && coll <= cols - 3 ? cbase[coll] : 0;
-    auto put = [&](int col, int i, uint32_t m, int64_t &run) {
-        const int c = i / words, w = i - c * words;
+    auto put = [&](int col, int c, uint32_t m, int64_t &run) {  // chunk c's rows of the column
         const int r0 = 1 + c * a.chunk_h;
         const uint32_t cnt = static_cast<uint32_t>(__popc(m));
         const uint32_t incl = wave_incl_add(cnt);
         int64_t pos = run + (incl - cnt);
         while (m) {
-            const int rr = r0 + 32 * w + __builtin_ctz(m);
+            const int rr = r0 + __builtin_ctz(m);
             m &= m - 1u;
             if (pos < cap) out[pos] = static_cast<int32_t>(static_cast<int64_t>(rr) * mc + col);
             ++pos;
         }
         run += static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incl), kWave - 1));
     };
-    auto word = [&](int col, int i) -> uint32_t {
-        const int c = i / words, w = i - c * words;
-        const int r0 = 1 + c * a.chunk_h;
-        if (col < 1 || col > cols - 3 || i >= items || r0 + 32 * w >= min(r0 + a.chunk_h, rows - 2)) return 0u;
-        return fbits[(static_cast<int64_t>(c) * words + w) * mc + col];
+    auto word = [&](int col, int c) -> uint32_t {
+        if (col < 1 || col > cols - 3 || c >= chunks) return 0u;
+        return fbits[static_cast<int64_t>(c) * mc + col];
     };
-    if (items <= kWave) {
-        // the wave's row-bit words, [item][column], read row by row (lane = column: 256 contiguous bytes per
-        // load) into LDS, 16 loads in flight; then one item per lane and column from LDS
+    if (chunks <= kWave) {
+        // the wave's row-bit words, [chunk][column], read row by row (lane = column: 256 contiguous bytes per
+        // load) into LDS, 16 loads in flight; then one chunk per lane and column from LDS
         __shared__ uint32_t sb[4][kWave][NC + 1];
         uint32_t(*const wb)[NC + 1] = sb[threadIdx.x >> 6];
-        for (int i0 = 0; i0 < items; i0 += 16) {
+        for (int i0 = 0; i0 < chunks; i0 += 16) {
             uint32_t v[16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) v[k] = word(coll, i0 + k);
@@ -485,7 +466,7 @@ __global__ __launch_bounds__(256) void k_lsd_scatter(LsdArgs a) {
         for (int g = 0; g < NC; g += kG) {
             uint32_t mv[kG];
 #pragma unroll
-            for (int k = 0; k < kG; ++k) mv[k] = lane < items ? wb[lane][g + k] : 0u;
+            for (int k = 0; k < kG; ++k) mv[k] = lane < chunks ? wb[lane][g + k] : 0u;
 #pragma unroll
             for (int k = 0; k < kG; ++k) {
                 const int col = strip * NC + g + k;
@@ -502,7 +483,7 @@ __global__ __launch_bounds__(256) void k_lsd_scatter(LsdArgs a) {
         const int col = strip * NC + cc;
         if (col < 1 || col > cols - 3) continue;  // (wave-uniform)
         int64_t run = cbase[col];
-        for (int i0 = 0; i0 < items; i0 += kWave) put(col, i0 + lane, word(col, i0 + lane), run);
+        for (int i0 = 0; i0 < chunks; i0 += kWave) put(col, i0 + lane, word(col, i0 + lane), run);
     }
 }
 
@@ -544,14 +525,12 @@ __global__ __launch_bounds__(64) void k_lsd_frames(const int64_t *counts, int ba
 
 namespace {
 
-// k_lsd_scatter with a.scatter_cols columns per wave (32; 16 or 64 for A/B)
+// k_lsd_scatter, 32 columns per wave: 1080p x256 scatter 116 -> 111 us dense, 106 -> 99 us compact against 64
+// (16: 130 / 124; profiles/r06_lsd_rows.txt)
 hipError_t launch_scatter(const LsdArgs &a, hipStream_t s) {
-    const int nc = a.scatter_cols == 64 ? 64 : a.scatter_cols == 16 ? 16 : 32;
-    const int64_t waves = static_cast<int64_t>(a.batch) * ((a.cols - 1 + nc - 1) / nc);
-    const dim3 grid(static_cast<unsigned>((waves + 3) / 4)), block(256);
-    if (nc == 64) hipLaunchKernelGGL(k_lsd_scatter<64>, grid, block, 0, s, a);
-    else if (nc == 16) hipLaunchKernelGGL(k_lsd_scatter<16>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(k_lsd_scatter<32>, grid, block, 0, s, a);
+    constexpr int kCols = 32;
+    const int64_t waves = static_cast<int64_t>(a.batch) * ((a.cols - 1 + kCols - 1) / kCols);
+    hipLaunchKernelGGL(k_lsd_scatter<kCols>, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -81,19 +81,10 @@ __global__ __launch_bounds__(256) void k_bias_relu_pool(const u4 *x, const u4 *b
 // float FMA accumulation in tap order, the sum rounded to half, then + bias in float rounded to half and
 // the ReLU (as the bias-free convolution + fd_nn_bias_relu path rounds), one 16-byte store.
 constexpr int kConv1MaxW = 4096;  // frame width the row staging holds
-#ifndef FD_NN_NT_STORES
-#define FD_NN_NT_STORES 1  // conv1a's activation written with nontemporal stores (A/B: 0): 589 -> 449 us
-#endif
-#ifndef FD_C64_NT_STORES
-#define FD_C64_NT_STORES 1  // K10's outputs likewise (A/B: 0): conv2a / conv1b +22 / +27 us alone, but the forward
-                            // 4.54-4.61 vs 4.69-4.71 ms (the layers after them find the caches unpolluted)
-#endif
+// K10's outputs are written with nontemporal stores: conv2a / conv1b +22 / +27 us alone, but the forward
+// 4.54-4.61 vs 4.69-4.71 ms (the layers after them find the caches unpolluted)
 __device__ __forceinline__ void nn_store(u4 *p, u4 v) {
-#if FD_C64_NT_STORES
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 __global__ __launch_bounds__(256) void k_conv3x3_c1_bias_relu(const _Float16 *x, const _Float16 *wt,
@@ -145,11 +136,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c1_bias_relu(const _Float16 *x,
                 }
                 o[k2] = packed;
             }
-#if FD_NN_NT_STORES
-            __builtin_nontemporal_store(o, &yrow[xx * cvec + cv]);  // (2.5 GB per SuperPoint batch: streamed past the caches)
-#else
-            yrow[xx * cvec + cv] = o;
-#endif
+            __builtin_nontemporal_store(o, &yrow[xx * cvec + cv]);  // (2.5 GB per SuperPoint batch: streamed past the caches, 589 -> 449 us)
         }
         __syncthreads();  // (rin reused by the next row)
     }

@@ -23,9 +23,6 @@ namespace {
 // bytes over and only 4 fit.
 constexpr int kStage = FD_STAGE_CORNER;
 constexpr int kStageFast = FD_STAGE_FAST;  // FAST: fewer flushes (each drains the wave's stores)
-#ifndef FD_FAST_PIPE
-#define FD_FAST_PIPE 1  // k_fast: score-table loads consumed one row step after they are issued (0: same step, A/B)
-#endif
 
 // Per-wave candidate sink. Detect mode: stage in LDS, append to the frame's list with one atomic per
 // flush. Raster mode: write the (row, tile) segment in column order.
@@ -56,13 +53,8 @@ __device__ __forceinline__ void sink_flush(Sink &sk, const PointsArgs &a, int f)
         if (sk.hist) atomicAdd(&sk.hist[((float_key(r) - a.key_base) << a.key_lz) >> 20], 1u);
         const int64_t pos = static_cast<int64_t>(base) + i;
         if (pos < a.list_cap) {
-#if FD_LIST_NT
-            __builtin_nontemporal_store(r, &dr[pos]);
-            __builtin_nontemporal_store(sk.idx[i], &di[pos]);
-#else
             dr[pos] = r;
             di[pos] = sk.idx[i];
-#endif
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -192,13 +184,8 @@ __device__ __forceinline__ void seg_flush(Sink &sk, const PointsArgs &a, int f, 
         const uint32_t lp = atomicAdd(&L.hist[k32 >> 20], 1u);
         const int64_t pos = base + lp;
         if (pos < a.list_cap) {
-#if FD_LIST_NT
-            __builtin_nontemporal_store(r, &dr[pos]);
-            __builtin_nontemporal_store(sk.idx[i], &di[pos]);
-#else
             dr[pos] = r;
             di[pos] = sk.idx[i];
-#endif
         }
         // the segment's head as selection keys (k32, ~idx): k_select's first read, no list hop
         if (lp < static_cast<uint32_t>(kSegHead)) head[lp] = (static_cast<uint64_t>(k32) << 32) | static_cast<uint64_t>(~sk.idx[i]);
@@ -214,17 +201,8 @@ __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, 
 // c0 = tx*kTileW + 4(l-1) .. c0+3 and walks the rows keeping 3-row sliding windows in registers:
 // pixels (+ DPP halo dwords), horizontal tensor sums, responses.
 // ---------------------------------------------------------------------------------------------------
-#ifdef FD_K1_CLOCKS  // diagnostic build only (tools/k1_wg_clock.py): per-workgroup s_memrealtime phase clocks
-}  // namespace
-__device__ unsigned long long g_fdk_k1_clocks[4096];
-namespace {
-#define FD_K1_CLOCK(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime()
-#else
-#define FD_K1_CLOCK(v)
-#endif
 template <int KIND, bool RASTER, bool MASKED, bool ALIGNED, bool G1>
 __global__ __launch_bounds__(256) void k_corner(PointsArgs a) {
-    FD_K1_CLOCK(t_entry);
     __shared__ DetectLds lds_all[1];
     int f, ty, tx;
     const bool active = decode_tile(a, f, ty, tx);
@@ -237,24 +215,11 @@ __global__ __launch_bounds__(256) void k_corner(PointsArgs a) {
         if (a.hist0) hist_clear(lds_all[0].hist);
         else __syncthreads();
     }
-    FD_K1_CLOCK(t_clr);
     if (active) corner_tile<KIND, RASTER, MASKED, ALIGNED, G1>(a, f, ty, tx, sk);
-    FD_K1_CLOCK(t_tile);
     if constexpr (!RASTER) {
         if (a.segdesc) {
             __shared__ uint32_t seg_wtot[4], seg_base;
             seg_flush(sk, a, f, active, lds_all[0], seg_wtot, seg_base);
-#ifdef FD_K1_CLOCKS
-            __syncthreads();
-            FD_K1_CLOCK(t_end);
-            if (threadIdx.x == 0 && blockIdx.x < 1024) {
-                unsigned long long *c = g_fdk_k1_clocks + 4 * blockIdx.x;
-                c[0] = t_entry;
-                c[1] = t_clr;
-                c[2] = t_tile;
-                c[3] = t_end;
-            }
-#endif
         } else {
             if (active) sink_flush(sk, a, f);
             if (a.hist0) hist_flush(lds_all[0].hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);
@@ -628,7 +593,6 @@ __device__ __forceinline__ void fast_tile(const PointsArgs &a, const FastOffsets
             }
         }
     };
-#if FD_FAST_PIPE
     // Software pipeline over the rows: a row's score-table loads (L1/L2 hits, several hundred cycles) are
     // issued in the step that classifies it and consumed in the next step, after that step's own row
     // load and table loads are in flight -- not waited for at once in the step that issued them.
@@ -642,7 +606,6 @@ __device__ __forceinline__ void fast_tile(const PointsArgs &a, const FastOffsets
         for (int m = 0; m < 4; ++m) score[m] = ((p_pass >> (8 * m + 7)) & 1u) ? static_cast<int>(max(p_sb[m], p_sd[m])) : 0;
         finish_row(p_orow, p_live, score);
     };
-#endif
 
     const int n_in = (y1 - y0) + 6;
     uint32_t nxt = load_px4<ALIGNED>(rs, (y0 - 3) * cols + c0);  // one row of prefetch
@@ -717,7 +680,6 @@ __device__ __forceinline__ void fast_tile(const PointsArgs &a, const FastOffsets
                 }
             }
 #undef ROW
-#if FD_FAST_PIPE
             if (pend) finish_pending();  // the previous row, its table loads issued one step ago
             pend = true;
             p_orow = orow;
@@ -728,17 +690,9 @@ __device__ __forceinline__ void fast_tile(const PointsArgs &a, const FastOffsets
                 p_sb[m] = sb[m];
                 p_sd[m] = sd[m];
             }
-#else
-            int score[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) score[m] = ((pass >> (8 * m + 7)) & 1u) ? static_cast<int>(max(sb[m], sd[m])) : 0;
-            finish_row(orow, live, score);
-#endif
         }
     }
-#if FD_FAST_PIPE
     if (pend) finish_pending();
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -920,10 +874,3 @@ hipError_t launch_compact(const CompactArgs &a, int batch, hipStream_t s) {
 }
 
 }  // namespace fdk
-
-#ifdef FD_K1_CLOCKS
-extern "C" int fd_debug_k1_clocks(unsigned long long *out, int n) {
-    return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(fdk::g_fdk_k1_clocks), sizeof(unsigned long long) * n, 0,
-                                                hipMemcpyDeviceToHost));
-}
-#endif

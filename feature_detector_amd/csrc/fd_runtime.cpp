@@ -95,7 +95,7 @@ struct fd_ctx {
 
 namespace {
 
-// A/B and diagnostic switches (FD_PX, FD_TILE_H, FD_SELECT_STAMPS, ...) take effect only when FD_DEBUG_AB is
+// Test and diagnostic switches (FD_PX, FD_SEG_LISTS, FD_SELECT_STAMPS, ...) take effect only when FD_DEBUG_AB is
 // set as well, so a stray variable in a user's environment cannot change the library's code path.
 const char *ab_env(const char *name) {
     const char *on = std::getenv("FD_DEBUG_AB");
@@ -173,9 +173,7 @@ T *as(DevBuf &b) {
 // Tile height: a multiple of `period` (3 for the corner walk, 7 for FAST) that still gives the launch
 // enough waves to fill 256 CUs, capped so halo rows stay a small overhead.
 int choose_tile_h(int64_t batch, int tiles_x, int out_rows, int period, int max_mult) {
-    int64_t target_waves = 10240;  // ~2 rounds of resident waves at 256 CUs (measured sweep)
-    if (const char *e = ab_env("FD_TARGET_WAVES")) target_waves = std::max<int64_t>(1, std::atoll(e));  // tuning
-    if (const char *e = ab_env("FD_TILE_MULT")) max_mult = std::max(1, std::atoi(e));                   // tuning
+    const int64_t target_waves = 10240;  // ~2 rounds of resident waves at 256 CUs (measured sweep)
     int64_t h = (batch * tiles_x * static_cast<int64_t>(out_rows)) / target_waves;
     if (h < period && period == 6) {
         // small launches: the tile's serial row chain is the latency; 3 rows (9 steps of the 6-row
@@ -187,7 +185,6 @@ int choose_tile_h(int64_t batch, int tiles_x, int out_rows, int period, int max_
         h = ((h + period - 1) / period) * period;
     }
     h = std::min<int64_t>(h, static_cast<int64_t>(period) * max_mult);
-    if (const char *e = ab_env("FD_TILE_H")) h = std::max(1, std::atoi(e));  // tuning (A/B)
     return static_cast<int>(h);
 }
 
@@ -510,8 +507,7 @@ int ref_buffers(fd_ctx *c, int batch, int rows, int cols, int64_t cap, fdk::RefS
 // (the order ComputeCandidates pushes them, feature_point_harris_detector.cpp:120-137,
 // feature_point_fast_detector.cpp:83-98), sorted here with std::sort and the reference comparator,
 // and the resulting visiting order goes back to the GPU for the greedy pass (k_select_ordered).
-// `which` selects the frames: FD_FRAME_TIES (FD_TIES_HOST=1: the host path for every flagged frame) or
-// FD_FRAME_UNRESOLVED (the frames k_select_reference left to the host).
+// `which` selects the frames: FD_FRAME_UNRESOLVED (the frames k_select_reference left to the host).
 int resolve_ties(fd_ctx *c, fdk::SelectArgs s, int batch, const SelectBufs &sb, bool push_order, uint32_t which) {
     // The status read below synchronises the stream, which a stream being captured into a graph cannot
     // do (and the host sort could not be replayed): refuse before touching the capture.
@@ -596,21 +592,82 @@ int resolve_ties(fd_ctx *c, fdk::SelectArgs s, int batch, const SelectBufs &sb, 
     return FD_OK;
 }
 
-bool host_ties_env() {  // FD_TIES_HOST=1: the round-3 host path for every flagged frame (A/B and checker)
-    static const bool v = ab_env("FD_TIES_HOST") && std::atoi(ab_env("FD_TIES_HOST")) != 0;
-    return v;
+// Diagnostics of the selection (FD_SELECT_STAMPS: phase clocks of k_select and k_select_reference, 32 words
+// per frame; FD_REF_DEBUG: k_select_reference's broken invariants, 8 words per frame), both in c->dbg.
+int diag_words(fd_ctx *c, size_t bytes) {
+    FD_HIP_TRY(c, ensure(c, c->dbg, bytes));
+    FD_HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, bytes, c->stream));
+    return FD_OK;
 }
 
-// Calls that will synchronise the context stream (host outputs, or the host tie path) cannot run while
-// that stream is being captured into a graph: refuse at entry, before any work is enqueued, so that a
+enum DiagKind { kDiagSelect, kDiagReference, kDiagRefChecks };
+
+// Copies the diagnostic words back (synchronises) and prints them to stderr.
+int print_diag(fd_ctx *c, int batch, DiagKind kind) {
+    using ull = unsigned long long;
+    if (kind == kDiagRefChecks) {
+        std::vector<uint32_t> h(static_cast<size_t>(8) * batch);
+        FD_HIP_TRY(c, hipMemcpyAsync(h.data(), c->dbg.p, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
+        FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < batch; ++b)
+            if (h[8 * b])
+                std::fprintf(stderr, "k_select_reference frame %d: check %u idx %u bound %u m_act %u T %u\n", b, h[8 * b],
+                             h[8 * b + 1], h[8 * b + 2], h[8 * b + 3], h[8 * b + 4]);
+        return FD_OK;
+    }
+    std::vector<uint64_t> all(static_cast<size_t>(batch) * 32);
+    FD_HIP_TRY(c, hipMemcpyAsync(all.data(), c->dbg.p, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost, c->stream));
+    FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (kind == kDiagReference) {  // k_select_reference's phase clocks (slots 16-30) of the flagged frames
+        for (int b = 0; b < batch; ++b) {
+            const uint64_t *q = all.data() + static_cast<size_t>(b) * 32;
+            if (!q[18]) continue;
+            std::fprintf(stderr, "k_select_reference frame %d cycles: push %llu | levels %llu sumT %llu: pivots %llu "
+                                 "pass1 %llu bases %llu pass2 %llu (K) %llu pass3 %llu children %llu | leaves %llu "
+                                 "wave-local %llu greedy %llu windows %llu\n", b, (ull)q[16], (ull)q[18], (ull)q[19],
+                         (ull)q[24], (ull)q[25], (ull)q[26], (ull)q[27], (ull)q[28], (ull)q[29], (ull)q[30], (ull)q[20],
+                         (ull)q[23], (ull)q[21], (ull)q[22]);
+            std::fprintf(stderr, "  levels (T:cycles):");
+            for (int l = 0; l < 16 && l < static_cast<int>(q[18]); ++l)
+                std::fprintf(stderr, " %llu:%llu", (ull)(q[l] >> 40), (ull)(q[l] & ((1ull << 40) - 1)));
+            std::fprintf(stderr, "\n");
+        }
+        return FD_OK;
+    }
+    const uint64_t *h = all.data();  // k_select's phase clocks: frame 0, then the spread over the frames
+    std::fprintf(stderr, "k_select cycles: init %llu hist0 %llu gather %llu subkeys %llu greedy %llu descent %llu "
+                         "control %llu | chunks %llu descents %llu subchunks %llu | extract %llu runsort %llu merges %llu place %llu cmask %llu\n",
+                 (ull)h[1], (ull)h[2], (ull)h[3], (ull)h[4], (ull)h[5], (ull)h[6], (ull)h[7], (ull)h[8], (ull)h[9],
+                 (ull)h[0], (ull)h[10], (ull)h[11], (ull)h[12], (ull)h[13], (ull)h[14]);
+    std::fprintf(stderr, "  fine:");
+    for (int i = 16; i < 32; ++i) std::fprintf(stderr, " %llu", (ull)h[i]);
+    std::fprintf(stderr, "\n");
+    if (batch > 1) {  // the kernel lasts as long as its slowest frame
+        uint64_t mn = ~0ull, mx = 0, gmx = 0, grmx = 0;
+        int fmx = 0;
+        for (int b = 0; b < batch; ++b) {
+            const uint64_t *q = all.data() + static_cast<size_t>(b) * 32;
+            const uint64_t t = q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7];
+            if (t > mx) mx = t, fmx = b;
+            mn = std::min(mn, t);
+            gmx = std::max(gmx, q[3]);
+            grmx = std::max(grmx, q[5]);
+        }
+        std::fprintf(stderr, "  frames: total cycles min %llu max %llu (frame %d), max gather %llu, max greedy %llu\n",
+                     (ull)mn, (ull)mx, fmx, (ull)gmx, (ull)grmx);
+    }
+    return FD_OK;
+}
+
+// Calls that will synchronise the context stream (host outputs) cannot run while that stream is being
+// captured into a graph: refuse at entry, before any work is enqueued, so that a
 // failed call leaves nothing half-recorded in the capture.
 int refuse_sync_under_capture(fd_ctx *c, int outputs_on_device) {
-    const bool syncs = !outputs_on_device || (c->tie_order == FD_TIES_REFERENCE && host_ties_env());
-    if (!syncs || !c->stream) return FD_OK;
+    if (outputs_on_device || !c->stream) return FD_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     FD_HIP_TRY(c, hipStreamIsCapturing(c->stream, &cap));
     if (cap != hipStreamCaptureStatusNone)
-        return fail(c, FD_ERR_INVALID, "this call synchronises the stream (host outputs or FD_TIES_HOST): not allowed "
+        return fail(c, FD_ERR_INVALID, "this call synchronises the stream (host outputs): not allowed "
                                        "during stream capture; pass device outputs");
     return FD_OK;
 }
@@ -662,8 +719,7 @@ int run_select(fd_ctx *c, const SelectCall &q, const PriorInfo &pi, const Select
     // In the raster tie order nothing after k_select changes the outputs: the kernel writes the features
     // and counts straight into the pinned result buffer and mirrors the status words there (no copy after
     // the kernel: ~6 us per 640x480 host frame). The reference order's pass rewrites them: copied as before.
-    static const bool no_direct = ab_env("FD_HOST_DIRECT") && std::atoi(ab_env("FD_HOST_DIRECT")) == 0;  // (A/B)
-    const bool direct = !outputs_on_device && c->tie_order != FD_TIES_REFERENCE && !no_direct;
+    const bool direct = !outputs_on_device && c->tie_order != FD_TIES_REFERENCE;
     if (!outputs_on_device) {
         if (c->status.n < res_bytes) {  // (grow: the selection's status words move with it)
             FD_HIP_TRY(c, ensure(c, c->status, res_bytes));
@@ -693,41 +749,30 @@ int run_select(fd_ctx *c, const SelectCall &q, const PriorInfo &pi, const Select
     s.pre_count = sb.pre_count;
     s.pre_keys = s.gather_groups > 1 ? sb.pre_keys : nullptr;
     s.seg_bad = sb.seg_bad;
-    s.wide_keys = ab_env("FD_NO_WIDE") ? nullptr : sb.wide_keys;  // (A/B switch)
+    s.wide_keys = sb.wide_keys;
     // FAST's top responses are scores plus a slowly growing offset: thousands of candidates share the
     // top bins and the greedy scan runs over several chunks (1280x720 noise: ~5k), so the wide pass
     // comes with the first chunk; the corner detectors usually finish within it (wide pass deferred).
     s.wide_eager = q.wide_eager ? 1 : 0;
-    if (q.skipped && ab_env("FD_CUT_NO_WIDE")) {  // (A/B: the cut's short lists gathered chunk by chunk instead)
-        s.wide_keys = nullptr;
-        s.wide_eager = 0;
-        s.fast_sub = 1;
-    }
     // ... and its list pass is spread over the frame's list by k_wide_gather, ~16k entries per workgroup
     // at FAST's ~30 % candidate density on noise (one workgroup read the whole list before: 1280x720,
-    // ~55k of k_select's ~130k cycles per frame). FD_WIDE_GROUPS=0: off (A/B).
+    // ~55k of k_select's ~130k cycles per frame).
     // (not under FAST's emission cut: its lists of a few tens of thousands of keys are cheaper to pass once
     // inside k_select -- 85 us vs 73 + 13 + 5 us for k_select, k_wide_gather and k_wide_cut at configs[2])
     if (s.wide_eager && s.wide_keys && !s.pre_keys && !q.value_flag && !q.skipped) {
         const int64_t est = static_cast<int64_t>(rows) * cols * 3 / 10;
         s.wide_groups = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(64, (est + 16383) / 16384)));
-        if (const char *e = ab_env("FD_WIDE_GROUPS")) s.wide_groups = std::max(0, std::atoi(e));
-        if (s.wide_groups > 0) {
-            s.wide_count = sb.wide_count;
-            s.wide_cut = sb.wide_cut;
-        }
+        s.wide_count = sb.wide_count;
+        s.wide_cut = sb.wide_cut;
     }
     if (q.segdesc && !s.pre_keys) {
         s.segdesc = q.segdesc;
         s.seghead = q.seghead;
         s.nseg = q.nseg;
     }
-    s.first_sub = 1;
-    if (const char *e = ab_env("FD_FIRST_SUB")) s.first_sub = std::atoi(e) != 0;  // (A/B switch)
     static const bool stamps = ab_env("FD_SELECT_STAMPS") != nullptr;
-    if (stamps) {  // diagnostic build-free switch: phase clocks of k_select for frame 0
-        FD_HIP_TRY(c, ensure(c, c->dbg, sizeof(uint64_t) * 32 * batch));
-        FD_HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, sizeof(uint64_t) * 32 * batch, c->stream));
+    if (stamps) {  // diagnostic: phase clocks of k_select and k_select_reference
+        if (const int rc = diag_words(c, sizeof(uint64_t) * 32 * batch)) return rc;
         s.stamps = as<uint64_t>(c->dbg);
     }
     s.skipped = q.skipped;
@@ -754,98 +799,31 @@ int run_select(fd_ctx *c, const SelectCall &q, const PriorInfo &pi, const Select
     }
     c->sel_dirty = false;
     c->status_batch = batch;
-    if (stamps) {
-        uint64_t h[32];
-        FD_HIP_TRY(c, hipMemcpyAsync(h, c->dbg.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::fprintf(stderr, "k_select cycles: init %llu hist0 %llu gather %llu subkeys %llu greedy %llu descent %llu "
-                             "control %llu | chunks %llu descents %llu subchunks %llu | extract %llu runsort %llu merges %llu place %llu cmask %llu\n",
-                     (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3],
-                     (unsigned long long)h[4], (unsigned long long)h[5], (unsigned long long)h[6],
-                     (unsigned long long)h[7], (unsigned long long)h[8], (unsigned long long)h[9],
-                     (unsigned long long)h[0], (unsigned long long)h[10], (unsigned long long)h[11], (unsigned long long)h[12],
-                     (unsigned long long)h[13], (unsigned long long)h[14]);
-        std::fprintf(stderr, "  fine:");
-        for (int i = 16; i < 32; ++i) std::fprintf(stderr, " %llu", (unsigned long long)h[i]);
-        std::fprintf(stderr, "\n");
-        if (batch > 1) {  // spread over the frames: the kernel lasts as long as its slowest frame
-            std::vector<uint64_t> all(static_cast<size_t>(batch) * 32);
-            FD_HIP_TRY(c, hipMemcpyAsync(all.data(), c->dbg.p, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost,
-                                         c->stream));
-            FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            uint64_t mn = ~0ull, mx = 0, gmx = 0, grmx = 0;
-            int fmx = 0;
-            for (int b = 0; b < batch; ++b) {
-                const uint64_t *q = all.data() + static_cast<size_t>(b) * 32;
-                const uint64_t t = q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7];
-                if (t > mx) mx = t, fmx = b;
-                mn = std::min(mn, t);
-                gmx = std::max(gmx, q[3]);
-                grmx = std::max(grmx, q[5]);
-            }
-            std::fprintf(stderr, "  frames: total cycles min %llu max %llu (frame %d), max gather %llu, max greedy %llu\n",
-                         (unsigned long long)mn, (unsigned long long)mx, fmx, (unsigned long long)gmx,
-                         (unsigned long long)grmx);
-        }
-    }
+    if (stamps)
+        if (const int rc = print_diag(c, batch, kDiagSelect)) return rc;
     if (c->tie_order == FD_TIES_REFERENCE && !q.tie_idx_desc) {
-        if (host_ties_env()) {  // the round-3 host path (A/B and checker): every flagged frame sorted on the host
-            const int rc = resolve_ties(c, s, batch, sbl, q.push_order, FD_FRAME_TIES);
-            if (rc) return rc;
-        } else {
-            fdk::RefSortArgs r{};
-            const int rc = ref_buffers(c, batch, rows, cols, q.cap, r);
-            if (rc) return rc;
-            r.push_order = q.push_order ? 1 : 0;
-            static const bool ref_debug = ab_env("FD_REF_DEBUG") != nullptr;  // diagnostic: broken invariants
-            if (ref_debug) {
-                FD_HIP_TRY(c, ensure(c, c->dbg, sizeof(uint32_t) * 8 * batch));
-                FD_HIP_TRY(c, hipMemsetAsync(c->dbg.p, 0, sizeof(uint32_t) * 8 * batch, c->stream));
-                r.dbg = as<uint32_t>(c->dbg);
-            }
-            // frames of >= 1 Mpx: the multi-workgroup prelude (push order, first levels); FD_REF_WIDE=0/1
-            // forces it off / on (A/B)
-            const char *wide_env = ab_env("FD_REF_WIDE");
-            const bool wide = wide_env ? std::atoi(wide_env) != 0
-                                       : static_cast<int64_t>(rows) * cols >= (int64_t{1} << 20);
-            FD_HIP_TRY(c, fdk::launch_select_reference(s, r, batch, wide, c->stream));
-            if (stamps) {  // k_select_reference's phase clocks (slots 16-30) of the flagged frames
-                std::vector<uint64_t> all(static_cast<size_t>(batch) * 32);
-                FD_HIP_TRY(c, hipMemcpyAsync(all.data(), c->dbg.p, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost,
-                                             c->stream));
-                FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                for (int b = 0; b < batch; ++b) {
-                    const uint64_t *q = all.data() + static_cast<size_t>(b) * 32;
-                    if (q[18])
-                        std::fprintf(stderr, "k_select_reference frame %d cycles: push %llu | levels %llu sumT %llu: pivots %llu "
-                                             "pass1 %llu bases %llu pass2 %llu (K) %llu pass3 %llu children %llu | leaves %llu "
-                                             "wave-local %llu greedy %llu windows %llu\n", b, (unsigned long long)q[16], (unsigned long long)q[18],
-                                     (unsigned long long)q[19], (unsigned long long)q[24], (unsigned long long)q[25],
-                                     (unsigned long long)q[26], (unsigned long long)q[27], (unsigned long long)q[28],
-                                     (unsigned long long)q[29], (unsigned long long)q[30], (unsigned long long)q[20],
-                                     (unsigned long long)q[23], (unsigned long long)q[21], (unsigned long long)q[22]);
-                    if (q[18]) {
-                        std::fprintf(stderr, "  levels (T:cycles):");
-                        for (int l = 0; l < 16 && l < static_cast<int>(q[18]); ++l)
-                            std::fprintf(stderr, " %llu:%llu", (unsigned long long)(q[l] >> 40),
-                                         (unsigned long long)(q[l] & ((1ull << 40) - 1)));
-                        std::fprintf(stderr, "\n");
-                    }
-                }
-            }
-            if (ref_debug) {
-                std::vector<uint32_t> h(static_cast<size_t>(8) * batch);
-                FD_HIP_TRY(c, hipMemcpyAsync(h.data(), c->dbg.p, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost, c->stream));
-                FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                for (int b = 0; b < batch; ++b)
-                    if (h[8 * b])
-                        std::fprintf(stderr, "k_select_reference frame %d: check %u idx %u bound %u m_act %u T %u\n", b, h[8 * b],
-                                     h[8 * b + 1], h[8 * b + 2], h[8 * b + 3], h[8 * b + 4]);
-            }
-            if (!outputs_on_device) {  // the call synchronises anyway: frames left to the host
-                const int rc2 = resolve_ties(c, s, batch, sbl, q.push_order, FD_FRAME_UNRESOLVED);
-                if (rc2) return rc2;
-            }
+        fdk::RefSortArgs r{};
+        const int rc = ref_buffers(c, batch, rows, cols, q.cap, r);
+        if (rc) return rc;
+        r.push_order = q.push_order ? 1 : 0;
+        static const bool ref_debug = ab_env("FD_REF_DEBUG") != nullptr;  // diagnostic: broken invariants
+        if (ref_debug) {
+            if (const int rc2 = diag_words(c, sizeof(uint32_t) * 8 * batch)) return rc2;
+            r.dbg = as<uint32_t>(c->dbg);
+        }
+        // frames of >= 1 Mpx: the multi-workgroup prelude (push order, first levels); FD_REF_WIDE=0/1
+        // forces it off / on (tests)
+        const char *wide_env = ab_env("FD_REF_WIDE");
+        const bool wide = wide_env ? std::atoi(wide_env) != 0
+                                   : static_cast<int64_t>(rows) * cols >= (int64_t{1} << 20);
+        FD_HIP_TRY(c, fdk::launch_select_reference(s, r, batch, wide, c->stream));
+        if (stamps)
+            if (const int rc2 = print_diag(c, batch, kDiagReference)) return rc2;
+        if (ref_debug)
+            if (const int rc2 = print_diag(c, batch, kDiagRefChecks)) return rc2;
+        if (!outputs_on_device) {  // the call synchronises anyway: frames left to the host
+            const int rc2 = resolve_ties(c, s, batch, sbl, q.push_order, FD_FRAME_UNRESOLVED);
+            if (rc2) return rc2;
         }
     }
     if (!outputs_on_device) {
@@ -886,18 +864,8 @@ void lsd_geometry(fdk::LsdArgs &a, int batch, int rows, int cols, const uint8_t 
     // chunks of a strip: the shortest chunks whose scatter stays on its one-pass path (chunks <= 64 at 1080p);
     // 1080p x256 map + scan + scatter 1.514 -> 1.469 ms against 67-row chunks strip-fastest
     // (profiles/r06_lsd_rows.txt). 16 rows when 32 would leave fewer than 4096 waves (small batches).
-    int64_t ch = static_cast<int64_t>(batch) * a.strips4 * ((work_rows + 31) / 32) < 4096 ? 16 : 32;
-    a.chunk_fastest = 1;
-    if (const char *e = ab_env("FD_LSD_WAVES"))  // A/B: rows per chunk from a target wave count
-        ch = std::max<int64_t>(16, std::min<int64_t>(static_cast<int64_t>(batch) * a.strips4 * work_rows /
-                                                         std::max<int64_t>(64, std::atoll(e)), 256));
-    if (const char *e = ab_env("FD_LSD_CH")) ch = std::max(16, std::min(256, std::atoi(e)));  // A/B
-    a.chunk_h = static_cast<int>(ch);
-    if (const char *e = ab_env("FD_LSD_ORDER")) a.chunk_fastest = std::atoi(e);  // A/B
-    a.scatter_cols = 32;  // scatter 116 -> 111 us dense, 106 -> 99 us compact vs 64 (16: 130 / 124; r06_lsd_rows.txt)
-    if (const char *e = ab_env("FD_LSD_SC")) a.scatter_cols = std::atoi(e);  // A/B: 16, 32 or 64
+    a.chunk_h = static_cast<int64_t>(batch) * a.strips4 * ((work_rows + 31) / 32) < 4096 ? 16 : 32;
     a.chunks = (work_rows + a.chunk_h - 1) / a.chunk_h;
-    a.words = (a.chunk_h + 31) / 32;
 }
 
 // Host threads of the line stage: all hardware threads, capped by the process's thread budget
@@ -1151,9 +1119,8 @@ int fd_points_detect(fd_ctx *c, int kind, const uint8_t *frames, int frames_on_d
     key_map(kind, opts->min_valid_response, kind == FD_FAST && !g.empty ? &c->off : nullptr,
             static_cast<int64_t>(rows - 6) * (cols - 6), a.key_base, a.key_lz);
     // FAST's emission cut (PointsArgs::emit_cut): only in the raster tie order (the
-    // reference order's emulation needs every candidate in push order). FD_FAST_CUT=0: off (A/B).
-    const bool fast_cut = kind == FD_FAST && !g.empty && c->tie_order == FD_TIES_RASTER &&
-                          !(ab_env("FD_FAST_CUT") && std::atoi(ab_env("FD_FAST_CUT")) == 0);
+    // reference order's emulation needs every candidate in push order).
+    const bool fast_cut = kind == FD_FAST && !g.empty && c->tie_order == FD_TIES_RASTER;
     if (fast_cut && !c->fast_cut.p) {  // (zero: no cut, until a selection proposes one)
         FD_HIP_TRY(c, ensure(c, c->fast_cut, 2 * sizeof(uint32_t)));
         FD_HIP_TRY(c, hipMemsetAsync(c->fast_cut.p, 0, c->fast_cut.n, c->stream));
@@ -1549,7 +1516,7 @@ int fd_lsd_map_pitched(fd_ctx *c, const uint8_t *frames, int frames_on_device, i
         const size_t ncnt = static_cast<size_t>(batch) * mc * a.chunks;
         FD_HIP_TRY(c, ensure(c, c->l_cnt, sizeof(int32_t) * ncnt));
         FD_HIP_TRY(c, ensure(c, c->l_base, sizeof(int32_t) * ncnt));
-        FD_HIP_TRY(c, ensure(c, c->l_bits, sizeof(uint32_t) * ncnt * a.words));
+        FD_HIP_TRY(c, ensure(c, c->l_bits, sizeof(uint32_t) * ncnt));
         a.rowbits = as<uint32_t>(c->l_bits);
         a.col_cnt = as<int32_t>(c->l_cnt);
         a.col_base = as<int32_t>(c->l_base);
@@ -1658,7 +1625,8 @@ int fd_lsd_lines(fd_ctx *c, const uint8_t *frames, int frames_on_device, int bat
     if (c->aux) FD_HIP_TRY(c, hipStreamSynchronize(c->aux));  // (a failed earlier call's seed sort: drained)
     const bool timing = ab_env("FD_LINES_TIMING") != nullptr;  // diagnostic: phase times to stderr
     // FD_LSD_HOST_SORT=1 (A/B): the seed order by std::sort on the host workers instead of the GPU
-    const bool host_sort = ab_env("FD_LSD_HOST_SORT") && std::atoi(ab_env("FD_LSD_HOST_SORT")) != 0;
+    const char *host_sort_env = ab_env("FD_LSD_HOST_SORT");
+    const bool host_sort = host_sort_env && std::atoi(host_sort_env) != 0;
     bool gpu_seeds = false;
     int64_t ord_stride = 0;
     // Once the seed sort is launched on the side stream it uses the context's shared scratch (the
@@ -1684,7 +1652,7 @@ int fd_lsd_lines(fd_ctx *c, const uint8_t *frames, int frames_on_device, int bat
         const size_t ncnt = static_cast<size_t>(batch) * (cols - 1) * a.chunks;
         FD_HIP_TRY(c, ensure(c, c->l_cnt, sizeof(int32_t) * ncnt));
         FD_HIP_TRY(c, ensure(c, c->l_base, sizeof(int32_t) * ncnt));
-        FD_HIP_TRY(c, ensure(c, c->l_bits, sizeof(uint32_t) * ncnt * a.words));
+        FD_HIP_TRY(c, ensure(c, c->l_bits, sizeof(uint32_t) * ncnt));
         FD_HIP_TRY(c, ensure(c, c->l_counts, sizeof(int64_t) * batch));
         FD_HIP_TRY(c, ensure(c, c->l_fbase, sizeof(int64_t) * (static_cast<size_t>(batch) + 1)));
         a.rowbits = as<uint32_t>(c->l_bits);

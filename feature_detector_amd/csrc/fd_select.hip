@@ -85,31 +85,10 @@ constexpr int kPassUnroll = 8;  // independent list loads in flight per thread
 // corner selection prefers 512: 768 -> 78 us vs ~74).
 constexpr int kSubChunk = 512;
 constexpr int kSubChunkFast = kSelectChunk;
-#ifndef FD_KO
-#define FD_KO 0
-#endif
-// Phase-cost diagnostic builds only (-DFD_KO=mask; results are wrong): 1 = no greedy (the frame stops
-// after its first sub-chunk), 2 = no conflict masks, 4 = no tie bits, 16 = place() without the
-// position decode.
-constexpr int kKnockOut = FD_KO;
-#ifndef FD_EXIT
-#define FD_EXIT 0
-#endif
-// Phase-cost diagnostic builds only (-DFD_EXIT=n; no outputs): k_select returns after phase n (1 the
-// histogram scan and first cut, 2 the first gather, 3 the first sub-chunk's ordering), so that the
-// differences of the kernel times are the phases' costs without clock stamps.
-constexpr int kExitAt = FD_EXIT;
-// FAST emission cut's margin (SelectArgs::cut_next): the proposal keeps max(FD_CUT_MUL x V, V + FD_CUT_ADD)
+// FAST emission cut's margin (SelectArgs::cut_next): the proposal keeps max(kCutMul x V, V + kCutAdd)
 // emitted keys, V = the keys down to the lowest level-0 bin the frame's scan gathered
-#ifndef FD_PICK_U
-#define FD_PICK_U 2  // wide-scratch keys per thread in flight in wide_pick
-#endif
-#ifndef FD_CUT_MUL
-#define FD_CUT_MUL 4
-#endif
-#ifndef FD_CUT_ADD
-#define FD_CUT_ADD 4096
-#endif
+constexpr uint32_t kCutMul = 4, kCutAdd = 4096;
+constexpr int kPickU = 2;  // wide-scratch keys per thread in flight in wide_pick
 constexpr int kBucketMax = 64;  // largest bin of a sub-chunk ordered by bucket placement (else merge sort)
 // k_select workgroup size (launch_select). Its phases are chains of dependent LDS operations per wave;
 // with 256 threads (4x the items per wave) the headline frame's selection measured 1.3x slower.
@@ -283,7 +262,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         }
         return;
     }
-    if (kExitAt == 9) return;  // (diagnostic: launch and prologue only)
 
     // In-place suffix sums of S[0..nb) by the whole block; S[nb] = 0.
     auto suffix = [&](uint32_t *S, int nb) {
@@ -529,7 +507,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         __syncthreads();
         // kPickU keys per thread loaded before any is used: one memory round trip per kPickU x 1024 keys
         // (all 8 at once spill registers in this instance)
-        constexpr int kPickU = FD_PICK_U;
         for (uint32_t i0 = static_cast<uint32_t>(wave) * kWave; i0 < wide_n; i0 += static_cast<uint32_t>(kPickU * nthr)) {
             uint64_t kv[kPickU];
 #pragma unroll
@@ -649,14 +626,13 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
     {
         // Sorted-segment frames (small, corner detectors) cut the first chunk at one sub-chunk: it is
         // then ordered in place (no sub-chunk extract), and frames whose greedy runs past it take the
-        // next chunk through the main loop's list pass. FD_FIRST_SUB=0: the old cut (A/B).
+        // next chunk through the main loop's list pass.
         int lo_b = kHistBins;
-        if (!WIDE && seg_mode && a.first_sub) lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSubChunk));
+        if (!WIDE && seg_mode) lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSubChunk));
         if (lo_b >= kHistBins)  // (or the top bin alone exceeds a sub-chunk)
             lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSelectChunk));
         first_lo = lo_b;
         FD_STAMP(21);
-        if (kExitAt == 1) return;
         if (lo_b < kHistBins && suf0[lo_b] > 0) {
             const uint32_t want = suf0[lo_b];
             if (a.pre_keys && a.pre_count[f] == want) {  // k_gather's result (previous kernel)
@@ -684,7 +660,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         }
     }
     FD_STAMP(22);
-    if (kExitAt == 2) return;
     if (use_grid && grid_in_lds) {  // the first round's LDS-direct loads are consumed (or never used)
         // vmcnt(0): no load still landing in this space (only if they were issued: the wait would
         // also hold for this thread's outstanding global stores and atomics, a memory round trip)
@@ -694,7 +669,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         __syncthreads();
     }
     FD_STAMP(3);
-    if (kExitAt == 4) return;
     int level = 0;
     int hi = (1 << lvl_width(0)) - 1;
     for (int64_t iter = 0;; ++iter) {
@@ -712,7 +686,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         const uint32_t *S = suf(level);
         const uint32_t base = S[hi + 1];
         // (sorted-segment corner frames: chunks of one sub-chunk, each a cheap segment-prefix gather)
-        const uint32_t lim = static_cast<uint32_t>((!WIDE && seg_mode && a.first_sub && seg_bad == 0 && level == 0)
+        const uint32_t lim = static_cast<uint32_t>((!WIDE && seg_mode && seg_bad == 0 && level == 0)
                                                        ? kSubChunk : kSelectChunk);
         // smallest lo in [0, hi] with S[lo] - base <= lim (S is non-increasing in b)
         // (level 0, top of the histogram: the cut computed for the first chunk above)
@@ -804,12 +778,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
             const uint32_t s1 = static_cast<uint32_t>(d + 1);
             const float rcp_cols = 1.0f / static_cast<float>(cols), rcp_s1 = 1.0f / static_cast<float>(s1);
             auto place = [&](int pos, uint64_t sk) {  // decode position, prior mask, grid cell
-                if (kKnockOut & 16) {  // (diagnostic build: keys only)
-                    pxy[pos] = static_cast<uint32_t>(sk) & 0x00FF00FFu;
-                    L.pk32[pos] = static_cast<uint32_t>(sk >> 32);
-                    pcell[pos] = static_cast<uint32_t>(gw2 + 1);
-                    return;
-                }
                 uint32_t idx = a.tie_idx_desc ? static_cast<uint32_t>(sk) : ~static_cast<uint32_t>(sk);
                 bool ok = true;
                 if (idx >= static_cast<uint32_t>(rows) * static_cast<uint32_t>(cols)) {  // consistency guard
@@ -826,7 +794,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                     pcell[pos] = (udiv16q(y, s1, rcp_s1) + 1) * static_cast<uint32_t>(gw2) + (udiv16q(x, s1, rcp_s1) + 1);
             };
             // Sub-chunks of <= kSubChunk keys from the top bins of the superchunk (already in LDS):
-            const uint32_t sub_lim = static_cast<uint32_t>((WIDE && (a.wide_eager || a.fast_sub)) ? kSubChunkFast : kSubChunk);
+            const uint32_t sub_lim = static_cast<uint32_t>((WIDE && a.wide_eager) ? kSubChunkFast : kSubChunk);
             // the greedy usually stops within the first few hundred keys.
             int shi = hi;
             while (shi >= lo && !s_done) {
@@ -970,7 +938,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                         s_b1 = S[bin + 1];
                         big = s_b - s_b1 > static_cast<uint32_t>(kBucketMax);
                     }
-                    if (kExitAt == 5) return;
                     if (ballot(big) != 0ull && lane == 0) L.vote[0] = 1u;
                     if (scan_fast && tid < kScanBatches) sl.cnt[tid] = 0u;  // (the last scan's reads are barriers ago)
                     __syncthreads();
@@ -982,7 +949,6 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                         }
                         __syncthreads();
                         FD_STAMP(11);  // bucket scatter
-                        if (kExitAt == 6) return;
                         if (tid < c) {
                             const uint32_t g0 = s_b1 - sbase, gn = s_b - s_b1;
                             uint32_t r = 0;
@@ -1145,7 +1111,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                     FD_STAMP(13);  // place
                     }
                     }
-                    if (!a.tie_idx_desc && !(kKnockOut & 4) && !scan_fast) {  // tie bits over the ordered sub-chunk (wave-aligned 64-blocks)
+                    if (!a.tie_idx_desc && !scan_fast) {  // tie bits over the ordered sub-chunk (wave-aligned 64-blocks)
                         const int c64 = ((c + kWave - 1) & ~(kWave - 1)) + kWave;
                         for (int i = opaque(tid); i < c64; i += nthr) {
                             const bool t = i > 0 && i < c && L.pk32[i] == L.pk32[i - 1];
@@ -1155,7 +1121,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                     }
                     // conflict masks: earlier candidates of the same 64-batch within distance d
                     // (the pipelined scan computes both per batch, beside the scan)
-                    if (use_grid && !(kKnockOut & 2) && !scan_fast) conflict_masks(pxy, c, d, rows, cols, buf, tid, nthr);
+                    if (use_grid && !scan_fast) conflict_masks(pxy, c, d, rows, cols, buf, tid, nthr);
                 }
                 if (!scan_fast) __syncthreads();
                 if (tid == 0) {  // (read before the placement's last barrier; the next placement is barriers away)
@@ -1163,12 +1129,9 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                     L.vote[1] = 0u;
                 }
                 FD_STAMP(14);  // conflict masks
-                if (kExitAt == 3) return;
                 // greedy scan in order by wave 0 (SelectGoodFeatures :62-72); ties checked unless the
                 // order of equal responses is defined (SuperPoint's multimap)
-                if (kKnockOut & 1) {  // (phase-cost diagnostic build: no greedy, the frame ends here)
-                    if (tid == 0) s_done = 1;
-                } else if (scan_fast) {
+                if (scan_fast) {
                     // wave 0 scans batch b once waves 1.. have its conflict masks in LDS
                     if (wave == 0)
                         greedy_scan(a, f, c_sort, pxy, pcell, buf, grid_lds, gw2, prior, s_acc, s_done, sl,
@@ -1218,7 +1181,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         uint32_t prop = 0u;
         if (done && L.have_prev_min) {
             const uint32_t vis = suf0[min(static_cast<int>(L.prev_min >> 20), kHistBins - 1)];
-            const uint32_t target = max(static_cast<uint32_t>(FD_CUT_MUL) * vis, vis + static_cast<uint32_t>(FD_CUT_ADD));
+            const uint32_t target = max(kCutMul * vis, vis + kCutAdd);
             const int x0 = first_le(suf0, 0, kHistBins, 0u, target - 1u);  // (all threads: barriers)
             if (x0 > 0) {
                 const uint32_t fk = a.key_base + ((static_cast<uint32_t>(x0 - 1) << 20) >> a.key_lz);
@@ -1558,7 +1521,7 @@ hipError_t launch_select(const SelectArgs &a, int batch, hipStream_t s) {
     }
     // the wide pass (k_select<.., true>) for FAST and for list mode; the corner detectors' small frames
     // (sorted segments) keep the leaner instance
-    if ((a.wide_keys && (a.wide_eager || !a.segdesc)) || a.fast_sub)
+    if (a.wide_keys && (a.wide_eager || !a.segdesc))
         hipLaunchKernelGGL((k_select<kSelectThreads, true>), dim3(sel_grid), dim3(kSelectThreads), 0, s, a);
     else
         hipLaunchKernelGGL((k_select<kSelectThreads, false>), dim3(sel_grid), dim3(kSelectThreads), 0, s, a);

@@ -49,19 +49,13 @@ constexpr int kRefThreads = 1024;
 constexpr int kRefWaves = kRefThreads / kWave;
 constexpr int kRefMaxRanges = 256;  // unresolved ranges (> 16) in the list; bound: DESIGN.md
 constexpr int kRefLeaf = 16;        // libstdc++ _S_threshold
-#ifndef FD_REF_U
-#define FD_REF_U 4
-#endif
-constexpr int kRefU = FD_REF_U;     // 64-element rounds per wave whose global loads are issued together
+constexpr int kRefU = 4;            // 64-element rounds per wave whose global loads are issued together
 constexpr uint32_t kRefRidCap = 8192;  // flat elements per level whose range index pass 1 caches for passes 2-3
 // A range of <= kRefWaveLocal elements is partitioned to the end (its whole subtree) by one wave in LDS,
 // with no workgroup barriers, in 12 B per element of the 96 KiB greedy span per wave (elements + stopper
 // positions). A/B on the bench tie frames (tools/gpu_r04f.sh): off / 64 / 128 / 256 / 512 = headline
 // 52.3 / 51.3 / 50.1 / 48.4 / 52.5 us per call, north star 1.48 / 1.54 / 1.53 / 1.52 / 1.53 ms.
-#ifndef FD_REF_WL
-#define FD_REF_WL 256
-#endif
-constexpr uint32_t kRefWaveLocal = FD_REF_WL;  // (0: off)
+constexpr uint32_t kRefWaveLocal = 256;
 constexpr int kRefStack = 64;  // pending subranges per wave (depth-first: <= 2 per level)
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;
 
@@ -1020,7 +1014,7 @@ __global__ __launch_bounds__(NT) void k_select_reference(SelectArgs a, RefSortAr
                 uint32_t w_at = 0, l_at = 0;
                 // before the first greedy scan, children of <= kRefWaveLocal elements go to the wave-local
                 // list (while it has room) instead of the next level
-                const bool wl_on = kRefWaveLocal > 0u && !grid_ready;
+                const bool wl_on = !grid_ready;
                 uint32_t v_at = static_cast<uint32_t>(L.n_wl);
                 for (int b = 0; b < m; b += kWave) {
                     const int j = b + lane;

@@ -174,14 +174,6 @@ def nn_select_list(keypoints, scores, rows: int, cols: int, counts=None, options
     return xy, cnt, dout
 
 
-def _ab_env(name: str, default=None):
-    """A/B switch of the network's layer paths (FD_SP_*): read only with FD_DEBUG_AB set, so a stray
-    variable in a user's environment does not change the code path."""
-    if os.environ.get("FD_DEBUG_AB", "0") in ("", "0"):
-        return default
-    return os.environ.get(name, default)
-
-
 def bias_relu(x, bias, pool: bool = False, out=None, ctx: Context | None = None):
     """fd_nn_bias_relu: relu(x + bias) (and the 2x2 max pool when pool) of a channels-last fp16
     activation [N, C, H, W] on the device, in one pass (torch's current stream). x is the output of a
@@ -452,16 +444,13 @@ def build_net(seed: int = 0, head_gain: float = 100.0, nms: bool = False, top_k:
             three or four elementwise passes over the activation); other inputs take the torch modules."""
             if x.dtype == torch.float16 and x.is_cuda and conv.in_channels == 1 and conv.kernel_size == (3, 3) \
                     and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.out_channels in (8, 16, 32, 64, 128, 256) \
-                    and x.dim() == 4 and x.shape[1] == 1 and not pool and not _ab_env("FD_SP_UNFUSED") \
-                    and not _ab_env("FD_SP_NO_CONV1"):  # (A/B switches)
+                    and x.dim() == 4 and x.shape[1] == 1 and not pool:
                 # first layer: write-bound (9 MACs per output), one pass instead of convolution + bias pass
                 return conv1_bias_relu(x.contiguous(), conv.weight, conv.bias)
             if x.dtype == torch.float16 and x.is_cuda and conv.in_channels == 64 and conv.out_channels % 64 == 0 \
                     and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) \
                     and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) \
-                    and (not pool or (x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)) \
-                    and not _ab_env("FD_SP_UNFUSED") and not _ab_env("FD_SP_NO_C64") \
-                    and (conv.out_channels == 64 or not _ab_env("FD_SP_C64_ONLY64")):  # (A/B switches)
+                    and (not pool or (x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)):
                 # 64 -> 64 k layers on the matrix cores with bias, ReLU and pooling in the epilogue
                 # one packed copy per layer, replaced when the weight changes (in-place update, reload, device)
                 tag = (conv.weight.data_ptr(), conv.weight._version, x.device)
@@ -473,7 +462,7 @@ def build_net(seed: int = 0, head_gain: float = 100.0, nms: bool = False, top_k:
                     cache[id(conv)] = hit
                 return conv64_bias_relu(x, conv.weight, conv.bias, pool, packed=hit[1])
             if x.dtype == torch.float16 and x.is_cuda and x.is_contiguous(memory_format=torch.channels_last) \
-                    and conv.out_channels % 8 == 0 and not _ab_env("FD_SP_UNFUSED"):  # (A/B switch)
+                    and conv.out_channels % 8 == 0:
                 y = torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding)
                 if y.is_contiguous(memory_format=torch.channels_last):
                     return bias_relu(y, conv.bias, pool, out=None if pool else y)
@@ -486,12 +475,11 @@ def build_net(seed: int = 0, head_gain: float = 100.0, nms: bool = False, top_k:
         @staticmethod
         def fused_heads(semi, desc):
             """The heads' output stages run as fd_nn_heat_softmax / fd_nn_desc_normalize when the logits are
-            channels-last fp16 on the device (FD_SP_UNFUSED=1 or FD_SP_TORCH_HEADS=1: PyTorch's ops, A/B)."""
+            channels-last fp16 on the device."""
             return (semi.is_cuda and semi.dtype == torch.float16 and semi.shape[1] == 65
                     and semi.is_contiguous(memory_format=torch.channels_last)
                     and desc.is_cuda and desc.dtype == torch.float16 and desc.shape[1] % 8 == 0
-                    and desc.is_contiguous(memory_format=torch.channels_last)
-                    and not _ab_env("FD_SP_UNFUSED") and not _ab_env("FD_SP_TORCH_HEADS"))
+                    and desc.is_contiguous(memory_format=torch.channels_last))
 
         def first_layers(self, x):
             """conv1a -> ReLU -> conv1b -> ReLU -> MaxPool2d(2, 2), layer by layer through cbr (conv1a's
@@ -510,8 +498,7 @@ def build_net(seed: int = 0, head_gain: float = 100.0, nms: bool = False, top_k:
             x = self.cbr(self.conv4b, self.cbr(self.conv4a, x))
             xp, xd = self.cbr(self.convPa, x), self.cbr(self.convDa, x)
             semi = desc = None
-            if xp.is_cuda and xp.dtype == torch.float16 and xd.dtype == torch.float16 \
-                    and not _ab_env("FD_SP_UNFUSED") and not _ab_env("FD_SP_TORCH_HEADS"):  # (A/B switches)
+            if xp.is_cuda and xp.dtype == torch.float16 and xd.dtype == torch.float16:
                 # bias-free head convolutions: their biases go into the output stages below
                 semi = torch.nn.functional.conv2d(xp, self.convPb.weight, None, self.convPb.stride, self.convPb.padding)
                 desc = torch.nn.functional.conv2d(xd, self.convDb.weight, None, self.convDb.stride, self.convDb.padding)
@@ -649,11 +636,11 @@ class NNFeaturePointDetector:
         self.net = net.to(memory_format=torch.channels_last)
         # MIOpen solver choice (measured with tools/sp_find_probe.py, 64x640x480 fp16): exhaustive find
         # (benchmark=True) picks solvers worth 14.3 ms per 64 frames against 17.1 ms for immediate mode
-        # (FD_SP_FIND_EXHAUSTIVE=0), but its first use also times the naive direct solver on every
+        # (benchmark=False), but its first use also times the naive direct solver on every
         # conv shape (~30 s). That solver never wins, so it is left out of the search unless the caller
         # set the variable: first find ~10 s, ~0.6 s once MIOpen's user find-db holds the shapes.
         os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "0")
-        torch.backends.cudnn.benchmark = _ab_env("FD_SP_FIND_EXHAUSTIVE", "1") == "1"
+        torch.backends.cudnn.benchmark = True
         ones = torch.ones((1, self._options.kMaxImageRows, self._options.kMaxImageCols), dtype=torch.uint8, device=dev)
         self.InferenceSession(ones)
         return True

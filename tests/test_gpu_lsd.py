@@ -46,6 +46,26 @@ def test_ragged(fd, oracle, shape):
     check_lsd(fd, oracle, img, 20.0)
 
 
+def test_ragged_height_both_chunk_heights(fd, oracle):
+    """37x70 frames (34 scanned rows, one 256-column strip): a single frame takes 16-row chunks (16 + 16 + 2
+    rows), and from 2048 frames on (batch x strips x ceil(34 / 32) >= 4096 waves) the launch takes 32-row
+    chunks (32 + 2 rows): the last chunk's row-bit word is partial in both. Dense maps and the column-major
+    list of every frame against the oracle, bit for bit."""
+    rows, cols, batch = 37, 70, 2048
+    assert (batch - 1) * 1 * ((rows - 3 + 31) // 32) < 4096 <= batch * 1 * ((rows - 3 + 31) // 32)
+    frames = np.random.default_rng(3770).integers(0, 256, (batch, rows, cols), dtype=np.uint8)
+    check_lsd(fd, oracle, frames[0])
+    res = fd.lsd_map(frames)
+    assert len(res) == batch
+    for b in range(batch):
+        n, a, v, idx = res[b]
+        en, ea, ev, eidx = oracle.lsd_map(frames[b])
+        assert np.array_equal(n.view(np.uint32), en.view(np.uint32)), b
+        assert np.array_equal(v, ev), b
+        assert np.array_equal(a.view(np.uint32), ea.view(np.uint32)), b
+        assert np.array_equal(idx, eidx), b
+
+
 @pytest.mark.parametrize("min_norm", [0.0, 5.0, 100.0, 400.0])
 def test_thresholds(fd, oracle, min_norm):
     img = np.random.default_rng(3).integers(0, 256, (120, 200), dtype=np.uint8)

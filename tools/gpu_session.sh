@@ -9,7 +9,7 @@
 #                      rocprofv3 --kernel-trace --stats; FD_DEBUG_AB=1 is set so the library honours its switches
 #   bench=ARGS         one bench.py line (ARGS: comma-separated bench.py flags) -> gpurun_out/bench_<n>.json
 #   stamps[=LIB,E..]   k_select phase clocks (FD_SELECT_STAMPS) at the bench shapes (LIB: FD_LIB_PATH, e.g.
-#                      abvar/new.so, may be empty; E: VAR=V settings, e.g. FD_SELECT_REPEAT=1)
+#                      abvar/new.so, may be empty; E: VAR=V settings)
 #   py=SCRIPT          python3 SCRIPT (comma-separated args), output to gpurun_out/py_<n>.log
 set -e
 cd "$GRAFT_REPO_ROOT"

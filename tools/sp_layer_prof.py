@@ -1,5 +1,5 @@
 """Kernel-level profile driver (run under rocprofv3 --kernel-trace --stats): the SuperPoint forward on 64
-640x480 frames, 5 calls, in the current configuration (FD_SP_* switches apply)."""
+640x480 frames, 5 calls."""
 import os
 import sys
 
