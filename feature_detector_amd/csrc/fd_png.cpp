@@ -1,7 +1,7 @@
 // fd_png.cpp -- PNG decode for the ingest front end: the reference loads its frames
 // with Visualizor2D::LoadImage (test/test_feature_point_detector.cpp:104, un-vendored).
 //
-// Host part of fd_png_decode / fd_png_to_frames (fd_runtime.cpp): zlib inflate of the IDAT stream and
+// Host part of fd_png_decode / fd_png_to_frames (fd_rt_stages.cpp): zlib inflate of the IDAT stream and
 // the per-row PNG filters (None / Sub / Up / Average / Paeth, PNG spec §9), which are serial along a
 // row and from row to row -- CPU work, done per image on worker threads. The output is the image's
 // samples as stored (gray or RGB / RGBA / gray+alpha, 8 bits); colour images become gray on the GPU

@@ -1,6 +1,6 @@
 """Host-output selection calls (fd_points_detect with outputs_on_device = 0): in the raster tie order k_select
 writes the features and counts straight into the context's pinned result buffer and mirrors the frames'
-status words there (fd_runtime.cpp run_select, SelectArgs::status_host); the reference order copies them
+status words there (fd_rt_select.cpp run_select, SelectArgs::status_host); the reference order copies them
 after its pass. Either way the host outputs must equal the device-output call on the same frames, and the
 status words fd_ctx_frame_status returns (the cached host copy) must equal the device ones -- for every
 detector, a batch with a blank frame (no candidates: the kernel's early exit), a noise frame and a
