@@ -132,6 +132,23 @@ __device__ __forceinline__ int mbcnt64(uint64_t m, int acc) {
     return static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), lo));
 }
 
+// Exclusive prefix of v over a workgroup of NT threads; the total in tot (every thread). wsum: LDS
+// [NT / kWave]. One wave scan of the wave sums, two barriers.
+template <int NT>
+__device__ __forceinline__ uint32_t wg_excl_add(uint32_t v, uint32_t *wsum, uint32_t &tot) {
+    constexpr int kWaves = NT / kWave;
+    const int lane = lane_id(), w = threadIdx.x / kWave;
+    const uint32_t incl = wave_incl_add(v);
+    if (lane == kWave - 1) wsum[w] = incl;
+    __syncthreads();
+    const uint32_t ws = lane < kWaves ? wsum[lane] : 0u;
+    const uint32_t wincl = wave_incl_add(ws);
+    const uint32_t wbase = static_cast<uint32_t>(__shfl(static_cast<int>(wincl - ws), w));
+    tot = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wincl), kWaves - 1));
+    __syncthreads();
+    return wbase + incl - v;
+}
+
 // Order-preserving map of an IEEE float to an unsigned key (larger float -> larger key).
 __device__ __forceinline__ uint32_t float_key(float f) {
     const uint32_t u = __float_as_uint(f);

@@ -1,5 +1,5 @@
-// Greedy min-distance scan shared by the selection kernels (fd_select.hip: k_select,
-// k_select_ordered; fd_select_ref.hip: k_select_reference): SelectGoodFeatures'
+// Greedy min-distance scan shared by the selection kernels (fd_select.hip: k_select;
+// fd_select_ref.hip: k_select_reference, k_select_ordered): SelectGoodFeatures'
 // (feature_point_detector.cpp:62-72) in-order walk over a chunk of candidates, one wave per chunk in
 // batches of 64, against an occupancy grid of (d+1)-sized cells, with the batch's conflict masks
 // computed beforehand by the whole workgroup.
@@ -347,6 +347,94 @@ __device__ __forceinline__ void conflict_masks(const uint32_t *pxy, int c, int d
         if (e != kEmpty && 16 * q < me) bits = near16(e, pxy + bb + 16 * q, me - 16 * q, d, pk16, w2);
         cm16[4 * p + q] = static_cast<uint16_t>(bits);
     }
+}
+
+// ---- greedy in a given order (fd_select_ref.hip: k_select_reference, k_select_ordered) ----------------
+// LDS of the scan: a chunk's positions, cells and conflict masks, the occupancy grid when it fits, and
+// the scan state carried from chunk to chunk.
+struct alignas(16) OrderedLds {
+    uint32_t pxy[kSelectChunk];
+    uint32_t pcell[kSelectChunk];
+    uint64_t cmask[kSelectChunk];
+    uint32_t grid_lds[kGridLdsCells];
+    int s_done, s_acc;
+    uint32_t tie_prev;
+    int tie_has_prev;
+};
+
+// A frame's greedy set-up: grid mode and geometry, prior count, prior mask.
+struct GreedyFrame {
+    bool use_grid;
+    int gw2, cells;
+    bool grid_in_lds;
+    uint32_t *grid;
+    uint32_t prior;
+    const uint32_t *fmask;
+    uint32_t npx, s1;
+    __device__ __forceinline__ GreedyFrame(const SelectArgs &a, int f, uint32_t *grid_lds) {
+        const int rows = a.rows, cols = a.cols, d = a.dist;
+        use_grid = d >= 1 || (d == 0 && a.grid_at_d0);
+        gw2 = a.grid_w + 2;
+        cells = gw2 * (a.grid_h + 2);
+        grid_in_lds = cells <= kGridLdsCells;
+        uint32_t *const grid_g = a.grid_global ? a.grid_global + static_cast<int64_t>(f) * cells : nullptr;
+        grid = grid_in_lds ? grid_lds : grid_g;
+        prior = a.prior_counts ? static_cast<uint32_t>(a.prior_counts[f]) : 0u;
+        fmask = a.mask ? a.mask + static_cast<int64_t>(f) * rows * a.mask_wpr : nullptr;
+        npx = static_cast<uint32_t>(rows) * static_cast<uint32_t>(cols);
+        s1 = static_cast<uint32_t>(d + 1);
+    }
+};
+
+// (thread 0, before the first chunk)
+__device__ __forceinline__ void ordered_reset(OrderedLds &G) {
+    G.s_done = 0;
+    G.s_acc = 0;
+    G.tie_prev = 0;
+    G.tie_has_prev = 0;
+}
+
+// (all threads, before the first chunk; a barrier follows at the caller)
+__device__ __forceinline__ void ordered_grid_init(const SelectArgs &a, const GreedyFrame &g, int tid, int nthr) {
+    if (g.use_grid)
+        for (int i = tid; i < g.cells; i += nthr) g.grid[i] = grid_empty(a.rows, a.cols, a.dist);
+}
+
+// One chunk of cn <= kSelectChunk candidates, idx_at(i) = the raster index of the i-th in visiting order,
+// with the same greedy as k_select (SelectGoodFeatures :62-72): decode, prior mask, grid cell; conflict
+// masks; one wave scans in batches of 64. All threads; ends with a barrier.
+template <class IdxAt>
+__device__ __forceinline__ void ordered_chunk(const SelectArgs &a, int f, const GreedyFrame &g, OrderedLds &G, int cn,
+                                              IdxAt idx_at, int tid, int nthr) {
+    const int rows = a.rows, cols = a.cols, d = a.dist;
+    for (int i = tid; i < cn; i += nthr) {
+        uint32_t idx = idx_at(i);
+        bool ok = true;
+        if (idx >= g.npx) {  // consistency guard
+            ok = false;
+            idx = 0;
+            atomicOr(&a.status[f], 0x80000000u);
+        }
+        const uint32_t y = idx / static_cast<uint32_t>(cols), x = idx - y * static_cast<uint32_t>(cols);
+        if (g.fmask) ok = ok && ((g.fmask[static_cast<int64_t>(y) * a.mask_wpr + (x >> 5)] >> (x & 31)) & 1u);
+        G.pxy[i] = ok ? ((y << 16) | x) : kEmpty;
+        if (g.use_grid) G.pcell[i] = (y / g.s1 + 1) * static_cast<uint32_t>(g.gw2) + (x / g.s1 + 1);
+    }
+    __syncthreads();
+    if (g.use_grid) conflict_masks(G.pxy, cn, d, rows, cols, G.cmask, tid, nthr);
+    __syncthreads();
+    if (tid < kWave) {
+        if (!g.use_grid)
+            greedy_chunk<0>(a, f, cn, G.pxy, G.pcell, G.cmask, g.grid, g.gw2, g.prior, G.s_acc, G.s_done, false, nullptr, 0u,
+                            0u, G.tie_prev, G.tie_has_prev);
+        else if (g.grid_in_lds)
+            greedy_chunk<1>(a, f, cn, G.pxy, G.pcell, G.cmask, g.grid, g.gw2, g.prior, G.s_acc, G.s_done, false, nullptr, 0u,
+                            0u, G.tie_prev, G.tie_has_prev);
+        else
+            greedy_chunk<2>(a, f, cn, G.pxy, G.pcell, G.cmask, g.grid, g.gw2, g.prior, G.s_acc, G.s_done, false, nullptr, 0u,
+                            0u, G.tie_prev, G.tie_has_prev);
+    }
+    __syncthreads();
 }
 
 // ---- k_select's pipelined scan (sorted chunks, occupancy grid in LDS, coordinates with grid_pk15) ----

@@ -322,6 +322,7 @@ hipError_t launch_select_ordered(const SelectArgs &a, const OrderedArgs &o, int 
 // libstdc++ std::sort order emulated on the GPU for the frames k_select flagged (FD_FRAME_TIES)
 // wide: run the multi-workgroup prelude first (r.ctl, r.wcnt set): frames of >= 1 Mpx
 hipError_t launch_select_reference(const SelectArgs &a, const RefSortArgs &r, int batch, bool wide, hipStream_t s);
+hipError_t launch_ref_prelude(const SelectArgs &a, const RefSortArgs &r, int batch, hipStream_t s);  // (its wide prelude: fd_select_refw.hip)
 // fd_lsd_lines: the reference's seed order (std::sort of the scan-ordered valid list by norm, descending,
 // feature_line_detector.cpp:88-94) of every frame into r.ord: the compact lists (frame_base, idx, lnorm)
 // into the list format of `a` (push order), then k_select_reference with order_only.

@@ -14,6 +14,7 @@
 // restated below from the published fdlibm algorithm; tests/test_lsd_atan2.py shows it equals the
 // host atan2f bit for bit over the whole LSD input domain (every half-integer (gx, gy) pair).
 #include "fd_device.h"
+#include "fd_hip.h"
 #include "fd_kernels.h"
 #include "fd_corner_common.h"  // logical_block
 
@@ -569,6 +570,44 @@ hipError_t launch_lsd(const LsdArgs &a, hipStream_t s) {
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_scatter(a, s);
+}
+
+namespace {
+
+// fd_lsd_lines' seed lists: frame f's compact run [frame_base[f], frame_base[f+1]) of (map index, norm)
+// into the list format at [f * list_cap] (the scan order is the push order), the frame flagged for
+// k_select_reference with its count.
+__global__ __launch_bounds__(256) void k_lsd_seed_lists(const int64_t *frame_base, const int32_t *idx, const float *lnorm,
+                                                        float *list_resp, uint32_t *list_idx, SelectArgs a) {
+    const int f = blockIdx.y;
+    const int64_t o = frame_base[f];
+    const int64_t n = min(frame_base[f + 1] - o, a.list_cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.status[f] = FD_FRAME_TIES;
+        a.cand_n[f] = static_cast<uint32_t>(n);
+    }
+    float *lr = list_resp + static_cast<int64_t>(f) * a.list_cap;
+    uint32_t *li = list_idx + static_cast<int64_t>(f) * a.list_cap;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
+        lr[i] = lnorm[o + i];
+        li[i] = static_cast<uint32_t>(idx[o + i]);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_lsd_seed_order(const int64_t *frame_base, const int32_t *idx, const float *lnorm, const SelectArgs &a,
+                                 const RefSortArgs &r0, int batch, bool wide, hipStream_t s) {
+    if (batch <= 0) return hipSuccess;
+    // (the selection reads its lists through const pointers; these are the runtime's list buffers)
+    hipLaunchKernelGGL(k_lsd_seed_lists, dim3(32, static_cast<unsigned>(batch)), dim3(256), 0, s, frame_base, idx, lnorm,
+                       const_cast<float *>(a.list_resp), const_cast<uint32_t *>(a.list_idx), a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    RefSortArgs r = r0;
+    r.push_order = 1;
+    r.order_only = 1;
+    return launch_select_reference(a, r, batch, wide, s);
 }
 
 }  // namespace fdk

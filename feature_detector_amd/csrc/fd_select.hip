@@ -14,7 +14,8 @@
 // Every data-dependent loop is bounded; an inconsistency trips a guard flag in the frame's status word
 // (FD_FRAME_GUARD) that the host reports as an error instead of a hang or an out-of-bounds access.
 // The status word also flags frames whose scan met equal responses (FD_FRAME_TIES); with
-// FD_TIES_REFERENCE the host re-selects those in the reference's std::sort order (k_select_ordered).
+// FD_TIES_REFERENCE k_select_reference re-selects those on the GPU in the reference's std::sort order, and
+// k_select_ordered serves the frames it leaves FD_FRAME_UNRESOLVED on host-output calls (fd_select_ref.hip).
 #include "fd_device.h"
 #include "fd_hip.h"
 #include "fd_kernels.h"
@@ -1413,93 +1414,7 @@ __global__ __launch_bounds__(NT) void k_select_redo(SelectArgs a) {
     }
 }
 
-// Greedy selection in a given order (FD_TIES_REFERENCE): the frame's candidates as raster indices in
-// the order the reference's std::sort leaves them (computed on the host for frames k_select flagged),
-// visited chunk by chunk with the same greedy as k_select (SelectGoodFeatures :62-72): decode, prior
-// mask, grid cell; conflict masks; one wave scans in batches of 64. Overwrites the frame's features.
-struct alignas(16) OrderedLds {
-    uint32_t pxy[kSelectChunk];
-    uint32_t pcell[kSelectChunk];
-    uint64_t cmask[kSelectChunk];
-    uint32_t grid_lds[kGridLdsCells];
-    int s_done, s_acc;
-    uint32_t tie_prev;
-    int tie_has_prev;
-};
-
-template <int NT>
-__global__ __launch_bounds__(NT) void k_select_ordered(SelectArgs a, OrderedArgs o) {
-    __shared__ OrderedLds L;
-    const int j = blockIdx.x, tid = threadIdx.x;
-    const int f = o.frame[j];
-    const uint32_t *ord = o.order + o.offset[j];
-    const int64_t n = o.count[j];
-    const int rows = a.rows, cols = a.cols, d = a.dist;
-    const bool use_grid = d >= 1 || (d == 0 && a.grid_at_d0);
-    const int gw2 = a.grid_w + 2;
-    const int cells = gw2 * (a.grid_h + 2);
-    const bool grid_in_lds = cells <= kGridLdsCells;
-    uint32_t *const grid_g = a.grid_global ? a.grid_global + static_cast<int64_t>(f) * cells : nullptr;
-    uint32_t *const grid = grid_in_lds ? L.grid_lds : grid_g;
-    const uint32_t prior = a.prior_counts ? static_cast<uint32_t>(a.prior_counts[f]) : 0u;
-    const uint32_t *fmask = a.mask ? a.mask + static_cast<int64_t>(f) * rows * a.mask_wpr : nullptr;
-    const uint32_t npx = static_cast<uint32_t>(rows) * static_cast<uint32_t>(cols);
-    const uint32_t s1 = static_cast<uint32_t>(d + 1);
-    if (use_grid)
-        for (int i = tid; i < cells; i += NT) grid[i] = grid_empty(rows, cols, d);
-    if (tid == 0) {
-        L.s_done = 0;
-        L.s_acc = 0;
-        L.tie_prev = 0;
-        L.tie_has_prev = 0;
-    }
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += kSelectChunk) {
-        if (L.s_done) break;
-        const int c = static_cast<int>(min(static_cast<int64_t>(kSelectChunk), n - base));
-        for (int i = tid; i < c; i += NT) {
-            uint32_t idx = ord[base + i];
-            bool ok = true;
-            if (idx >= npx) {  // consistency guard
-                ok = false;
-                idx = 0;
-                atomicOr(&a.status[f], 0x80000000u);
-            }
-            const uint32_t y = idx / static_cast<uint32_t>(cols), x = idx - y * static_cast<uint32_t>(cols);
-            if (fmask) ok = ok && ((fmask[static_cast<int64_t>(y) * a.mask_wpr + (x >> 5)] >> (x & 31)) & 1u);
-            L.pxy[i] = ok ? ((y << 16) | x) : kEmpty;
-            if (use_grid) L.pcell[i] = (y / s1 + 1) * static_cast<uint32_t>(gw2) + (x / s1 + 1);
-        }
-        __syncthreads();
-        if (use_grid) conflict_masks(L.pxy, c, d, rows, cols, L.cmask, tid, NT);
-        __syncthreads();
-        if (tid < kWave) {
-            if (!use_grid)
-                greedy_chunk<0>(a, f, c, L.pxy, L.pcell, L.cmask, grid, gw2, prior, L.s_acc, L.s_done, false, nullptr, 0u, 0u,
-                                L.tie_prev, L.tie_has_prev);
-            else if (grid_in_lds)
-                greedy_chunk<1>(a, f, c, L.pxy, L.pcell, L.cmask, grid, gw2, prior, L.s_acc, L.s_done, false, nullptr, 0u, 0u,
-                                L.tie_prev, L.tie_has_prev);
-            else
-                greedy_chunk<2>(a, f, c, L.pxy, L.pcell, L.cmask, grid, gw2, prior, L.s_acc, L.s_done, false, nullptr, 0u, 0u,
-                                L.tie_prev, L.tie_has_prev);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        a.out_counts[f] = L.s_acc;
-        atomicAnd(&a.status[f], ~FD_FRAME_UNRESOLVED);
-        atomicOr(&a.status[f], FD_FRAME_RESOLVED);
-    }
-}
-
 }  // namespace
-
-hipError_t launch_select_ordered(const SelectArgs &a, const OrderedArgs &o, int n_frames, hipStream_t s) {
-    if (n_frames <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_select_ordered<256>, dim3(static_cast<unsigned>(n_frames)), dim3(256), 0, s, a, o);
-    return hipGetLastError();
-}
 
 hipError_t launch_select(const SelectArgs &a, int batch, hipStream_t s) {
     if (a.pre_keys) {

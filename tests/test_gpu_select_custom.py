@@ -232,3 +232,30 @@ def test_reference_order_guard_failure(fd, oracle, image_png, monkeypatch, guard
             assert np.array_equal(got, exp0), ("resolved", dist, need)
     if guard == 1:  # one iteration cannot finish a frame of thousands of candidates
         assert st & fd.points.FRAME_UNRESOLVED, hex(st)
+
+
+@pytest.mark.parametrize("dist,need", [(-1, 2500), (0, 2500), (7, 3000)])
+def test_host_fallback_grid_modes(fd, oracle, monkeypatch, dist, need):
+    """The host-resolved fallback of the reference order (host std::sort + k_select_ordered) in each grid
+    mode of the ordered greedy, across the 2,048-candidate chunk boundary: k_select_reference is cut
+    short after one iteration (FD_REF_GUARD=1), so host-output calls take the fallback. On a 256x256
+    frame with 3,000 candidates at distinct pixels and 8 response values: dist -1 tests no distance
+    (no grid; every visited candidate is kept, 2,500 of them); dist 0 on caller lists tests the grid
+    with 258x258 bordered cells (> 16,384: grid in global memory); dist 7 gives 34x34 cells (grid in
+    LDS) and never reaches the need, so all 3,000 candidates are visited. Against the oracle's std::sort
+    order (sort_mode 0); the same call on device lists must report FRAME_UNRESOLVED, which shows that
+    the host result came through the fallback."""
+    monkeypatch.setenv("FD_DEBUG_AB", "1")
+    monkeypatch.setenv("FD_REF_GUARD", "1")
+    rows = cols = 256
+    rng = np.random.default_rng(2048)
+    px = rng.permutation(rows * cols)[:3000]
+    lst = (rng.integers(1, 9, 3000).astype(np.float32), (px % cols).astype(np.int32), (px // cols).astype(np.int32))
+    small_prior = np.array([(40, 40), (100, 200), (200, 60)], np.float32)
+    for prior in (None, small_prior):
+        pr = None if prior is None else [prior]
+        exp = oracle.select(*lst, rows, cols, dist, need, prior, sort_mode=0)
+        host = fd.select_points([lst], rows, cols, need, dist, prior=pr, ties="reference")
+        assert np.array_equal(host.features(0), exp), ("host", prior is None)
+        dev = fd.select_points(_dev_lists([lst]), rows, cols, need, dist, prior=pr, ties="reference")
+        assert int(dev.frame_flags()[0]) & fd.points.FRAME_UNRESOLVED, ("device", prior is None)
