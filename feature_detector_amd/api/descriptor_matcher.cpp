@@ -1,0 +1,90 @@
+// BriefMatcher over libfdhip.so (fd_brief_match): an MI355X extension, the reference has no matcher.
+// One call matches every query descriptor against every train descriptor in one kernel launch (two with
+// the cross-check).
+#include "feature_detector/descriptor_matcher.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+#include "fd_hip.h"
+
+namespace feature_detector {
+
+BriefMatcher::~BriefMatcher() {
+    if (ctx_) fd_ctx_destroy(ctx_);
+}
+
+void BriefMatcher::set_device(int device) {
+    if (ctx_ && device != device_) {
+        fd_ctx_destroy(ctx_);
+        ctx_ = nullptr;
+    }
+    device_ = device;
+}
+
+fd_ctx *BriefMatcher::Context() {
+    if (!ctx_) {
+        int dev = device_;
+        if (dev < 0) {
+            const char *e = std::getenv("FD_DEVICE");
+            dev = e ? std::atoi(e) : 0;
+        }
+        if (fd_ctx_create(dev, &ctx_) != FD_OK) {
+            ctx_ = nullptr;
+            Fail("fd_ctx_create failed (no MI355X visible?)");
+        }
+    }
+    return ctx_;
+}
+
+bool BriefMatcher::Fail(const std::string &what) {
+    error_ = what;
+    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
+    return false;
+}
+
+namespace {
+
+// std::vector<bool> descriptors -> [n][words] uint32, bit i = bit i % 32 of word i / 32 (fd_brief_compute's layout)
+bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<uint32_t> &words) {
+    const size_t nw = (length + 31) / 32;
+    words.assign(descriptors.size() * nw, 0u);
+    for (size_t i = 0; i < descriptors.size(); ++i) {
+        if (descriptors[i].size() != length) return false;
+        for (size_t j = 0; j < length; ++j)
+            if (descriptors[i][j]) words[i * nw + (j >> 5)] |= 1u << (j & 31);
+    }
+    return true;
+}
+
+}  // namespace
+
+bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                         std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
+                         const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    train_index.assign(query.size(), -1);
+    if (distance) distance->assign(query.size(), -1);
+    if (query.empty() || train.empty()) return Fail("Match: empty input");
+    const size_t length = query[0].size();
+    if (length < 1 || length > 256) return Fail("Match: descriptor length outside 1..256");
+    std::vector<uint32_t> q, t;
+    if (!Pack(query, length, q) || !Pack(train, length, t)) return Fail("Match: descriptors of unequal length");
+    if ((query_valid && query_valid->size() != query.size()) || (train_valid && train_valid->size() != train.size()))
+        return Fail("Match: one valid flag per descriptor is needed");
+    fd_ctx *ctx = Context();
+    if (!ctx) return false;
+    fd_match_opts o{static_cast<int32_t>(length), options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
+    std::vector<int32_t> dist(2 * query.size(), -1);
+    const int rc = fd_brief_match(ctx, 1, &o, q.data(), query_valid ? query_valid->data() : nullptr, nullptr,
+                                  static_cast<int32_t>(query.size()), t.data(), train_valid ? train_valid->data() : nullptr,
+                                  nullptr, static_cast<int32_t>(train.size()), train_index.data(), dist.data(), nullptr, 0);
+    if (rc != FD_OK) {
+        train_index.assign(query.size(), -1);
+        return Fail(std::string("fd_brief_match: ") + fd_last_error(ctx));
+    }
+    if (distance)
+        for (size_t i = 0; i < query.size(); ++i) (*distance)[i] = dist[2 * i];
+    return true;
+}
+
+}  // namespace feature_detector

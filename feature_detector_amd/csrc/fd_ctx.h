@@ -64,6 +64,9 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     fdrt::DevBuf b_uv, b_counts, b_bits, b_valid;
+    // fd_brief_match: the cross-check's reverse table ([batch][t_stride] best query of every train
+    // descriptor), and the staging of host-pointer calls (query / train inputs, outputs)
+    fdrt::DevBuf m_rev, m_qbits, m_qvalid, m_qcounts, m_tbits, m_tvalid, m_tcounts, m_idx, m_dist, m_counts;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

@@ -278,6 +278,27 @@ struct BriefArgs {
     uint8_t *out_valid;  // [batch][stride] or null
 };
 
+// Hamming matcher (fd_match.hip): every entry of the "a" set against the "b" set of the same frame.
+// Forward pass: a = query, b = train. Cross-check's reverse pass: a = train, b = query, out_idx = the
+// reverse table, no other output and no test.
+struct MatchArgs {
+    const uint32_t *a_bits;   // [batch][a_stride][ceil(length / 32)]
+    const uint8_t *a_valid;   // [batch][a_stride] or null (= all valid)
+    const int32_t *a_counts;  // [batch] or null (= a_stride); bits 25..31 ignored
+    int a_stride;
+    const uint32_t *b_bits;  // the same three arrays of the searched set
+    const uint8_t *b_valid;
+    const int32_t *b_counts;
+    int b_stride;
+    int batch, length;
+    int32_t *out_idx;     // [batch][a_stride]: best b index that passes the tests, else -1
+    int32_t *out_dist;    // [batch][a_stride][2] raw best / second distance (-1: absent), or null
+    int32_t *out_counts;  // [batch] += accepted entries (zeroed by the caller), or null
+    const int32_t *rev;   // [batch][b_stride] best a index of every b entry (cross-check), or null
+    int max_distance;     // < 0: off
+    float max_ratio;      // <= 0: off
+};
+
 // SuperPoint heatmap -> candidate lists (the K1 list format + level-0 histogram), for K4.
 struct HeatArgs {
     const float *heat;  // [batch][rows][cols]
@@ -335,6 +356,7 @@ hipError_t launch_lsd(const LsdArgs &a, hipStream_t s);
 hipError_t launch_lsd_count(const LsdArgs &a, hipStream_t s);    // compact mode: map (counts, row bits) + scans
 hipError_t launch_lsd_scatter(const LsdArgs &a, hipStream_t s);  // compact mode: the lists
 hipError_t launch_brief(const BriefArgs &a, hipStream_t s);
+hipError_t launch_brief_match(const MatchArgs &a, hipStream_t s);
 hipError_t launch_heat_candidates(const HeatArgs &a, hipStream_t s);
 int heat_blocks_per_frame(int64_t npx);
 hipError_t launch_nn_desc(const NnDescArgs &a, hipStream_t s);

@@ -1,0 +1,158 @@
+// Nearest-neighbour Hamming matcher for BRIEF descriptors (fd_brief_match, an MI355X extension: the
+// reference has no matcher) for gfx950.
+//
+// One kernel serves both directions. Its "a" side is the set whose entries get an answer, its "b" side
+// the set that is searched: the forward pass has a = query, b = train; the cross-check's reverse pass has
+// a = train, b = query and writes only the raw best index into a workspace table, which the forward pass
+// then reads once per accepted candidate.
+//
+// Layout: a workgroup of 4 waves covers 64 "a" descriptors of one frame. Every lane owns one of them and
+// keeps its words in VGPRs (lane l of each of the 4 waves owns the same descriptor). The frame's "b"
+// descriptors go through LDS in tiles of 256; wave w scans entries w, w + 4, w + 8, ... of a tile, so the
+// four waves share a tile's work evenly whatever its fill, and every lane of a wave reads the same LDS
+// address each step (a broadcast, no bank conflicts). Per pair: NW xor + popcount-accumulate, then the
+// update of (best, best index, second). The four partial results are merged exactly by wave 0.
+//
+// Exactness. Within a wave the scan is in ascending index order with a strict `<`, so equal distances
+// keep the lowest index; the merge takes the lexicographic minimum of (distance, index), which is that
+// same rule for any partition of the indices. The second distance is a value only (the smallest
+// distance to an entry with another index than the best): per update second = min(second, max(d, best)),
+// per merge the minimum of both seconds and the losing best.
+//
+// Validity costs nothing per pair: an invalid "b" entry starts its popcount sum at kInvalidPenalty
+// instead of 0 (a word per entry in LDS), so it loses against every valid entry (distance <= 256), and
+// a result >= kInvalidPenalty means "absent". Bits above `length` are masked on both sides, once: the
+// lane's own words when they are loaded, the "b" words when a tile is filled.
+#include "fd_device.h"
+#include "fd_kernels.h"
+
+namespace fdk {
+namespace {
+
+constexpr int kMatchWaves = 4;
+constexpr int kMatchThreads = kMatchWaves * kWave;
+constexpr int kMatchTile = kMatchThreads;  // "b" entries per LDS tile (one valid flag per thread)
+constexpr int kInvalidPenalty = 1 << 20;
+constexpr int kAbsent = 0x7FFFFFFF;
+
+// Entries of frame f: the count word without fd_points_detect's guard flags (bits 25..31), at most stride.
+__device__ __forceinline__ int frame_count(const int32_t *counts, int f, int stride) {
+    if (!counts) return stride;
+    return min(static_cast<int>(static_cast<uint32_t>(counts[f]) & 0x01FFFFFFu), stride);
+}
+
+// NW: descriptor words held per lane and per LDS row (words above ceil(length / 32) are zero).
+template <int NW>
+__global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tile[kMatchTile * NW];
+    __shared__ uint32_t pen[kMatchTile];
+    __shared__ int32_t part[3][kMatchWaves - 1][kWave];
+    const int tiles = (a.a_stride + kWave - 1) / kWave;
+    const int f = static_cast<int>(blockIdx.x) / tiles;
+    const int q0 = (static_cast<int>(blockIdx.x) - f * tiles) * kWave;
+    const int na = frame_count(a.a_counts, f, a.a_stride);
+    if (q0 >= na) return;  // (the whole workgroup: nothing of this frame is read or written)
+    const int nb = frame_count(a.b_counts, f, a.b_stride);
+    const int lane = lane_id();
+    const int wave = static_cast<int>(threadIdx.x) >> 6;
+    const int nw = (a.length + 31) >> 5;
+    const uint32_t tail = (a.length & 31) ? (1u << (a.length & 31)) - 1u : ~0u;
+    const int q = q0 + lane;
+    const bool live = q < na;
+    const int64_t aslot = static_cast<int64_t>(f) * a.a_stride + q;
+    uint32_t qw[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        qw[w] = (live && w < nw) ? a.a_bits[aslot * nw + w] : 0u;
+        if (w == nw - 1) qw[w] &= tail;
+    }
+    const uint32_t *bb = a.b_bits + static_cast<int64_t>(f) * a.b_stride * nw;
+    const uint8_t *bv = a.b_valid ? a.b_valid + static_cast<int64_t>(f) * a.b_stride : nullptr;
+    int best = kAbsent, second = kAbsent, bidx = -1;
+    for (int t0 = 0; t0 < nb; t0 += kMatchTile) {
+        const int n = min(kMatchTile, nb - t0);
+        __syncthreads();  // every wave is done with the previous tile
+        for (int i = static_cast<int>(threadIdx.x); i < n * NW; i += kMatchThreads) {
+            const int r = i / NW, w = i % NW;
+            uint32_t v = w < nw ? bb[static_cast<int64_t>(t0 + r) * nw + w] : 0u;
+            if (w == nw - 1) v &= tail;
+            tile[i] = v;
+        }
+        if (static_cast<int>(threadIdx.x) < n)
+            pen[threadIdx.x] = (bv && !bv[t0 + threadIdx.x]) ? static_cast<uint32_t>(kInvalidPenalty) : 0u;
+        __syncthreads();
+#pragma unroll 2
+        for (int j = wave; j < n; j += kMatchWaves) {
+            uint32_t d = pen[j];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) d += static_cast<uint32_t>(__popc(qw[w] ^ tile[j * NW + w]));
+            const int di = static_cast<int>(d);
+            second = min(second, max(di, best));
+            bidx = di < best ? t0 + j : bidx;
+            best = min(best, di);
+        }
+    }
+    if (wave) {
+        part[0][wave - 1][lane] = best;
+        part[1][wave - 1][lane] = bidx;
+        part[2][wave - 1][lane] = second;
+    }
+    __syncthreads();
+    if (wave) return;
+    for (int w = 0; w < kMatchWaves - 1; ++w) {
+        const int ob = part[0][w][lane], oi = part[1][w][lane], os = part[2][w][lane];
+        const bool take = ob < best || (ob == best && oi < bidx);
+        second = min(min(second, os), take ? best : ob);
+        if (take) {
+            best = ob;
+            bidx = oi;
+        }
+    }
+    const bool avalid = live && (!a.a_valid || a.a_valid[aslot]);
+    const int d1 = (avalid && best < kInvalidPenalty) ? best : -1;
+    const int d2 = (avalid && second < kInvalidPenalty) ? second : -1;
+    const int raw = d1 >= 0 ? bidx : -1;
+    bool ok = raw >= 0;
+    if (ok && a.max_distance >= 0 && d1 > a.max_distance) ok = false;
+    // one float multiply and one compare (the file is built without contraction); skipped without a second
+    if (ok && a.max_ratio > 0.0f && d2 >= 0 && !(static_cast<float>(d1) < a.max_ratio * static_cast<float>(d2)))
+        ok = false;
+    if (ok && a.rev && a.rev[static_cast<int64_t>(f) * a.b_stride + raw] != q) ok = false;
+    if (live) {
+        a.out_idx[aslot] = ok ? raw : -1;
+        if (a.out_dist) {
+            a.out_dist[2 * aslot] = d1;
+            a.out_dist[2 * aslot + 1] = d2;
+        }
+    }
+    if (a.out_counts) {
+        const int n_ok = popc64(ballot(ok));
+        if (lane == 0 && n_ok) atomicAdd(a.out_counts + f, n_ok);
+    }
+}
+
+template <int NW>
+void launch_nw(const MatchArgs &a, unsigned blocks, hipStream_t s) {
+    hipLaunchKernelGGL(k_brief_match<NW>, dim3(blocks), dim3(kMatchThreads), 0, s, a);
+}
+
+}  // namespace
+
+hipError_t launch_brief_match(const MatchArgs &a, hipStream_t s) {
+    const int64_t blocks = static_cast<int64_t>(a.batch) * ((a.a_stride + kWave - 1) / kWave);
+    if (blocks == 0) return hipSuccess;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    const int nw = (a.length + 31) / 32;
+    const unsigned g = static_cast<unsigned>(blocks);
+    if (nw <= 1)
+        launch_nw<1>(a, g, s);
+    else if (nw <= 2)
+        launch_nw<2>(a, g, s);
+    else if (nw <= 4)
+        launch_nw<4>(a, g, s);
+    else
+        launch_nw<8>(a, g, s);
+    return hipGetLastError();
+}
+
+}  // namespace fdk

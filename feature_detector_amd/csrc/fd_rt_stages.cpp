@@ -1,6 +1,6 @@
 // Host runtime of libfdhip.so: the remaining stages. PNG ingest (fd_png.cpp decodes, fd_gray.hip
-// converts), BRIEF (fd_brief.hip) and the NN stages (selection over heatmaps and keypoint lists,
-// descriptor sampling, the SuperPoint layers of fd_nn.hip / fd_nn_act.hip).
+// converts), BRIEF (fd_brief.hip) and its matcher (fd_match.hip), and the NN stages (selection over
+// heatmaps and keypoint lists, descriptor sampling, the SuperPoint layers of fd_nn.hip / fd_nn_act.hip).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -124,6 +124,102 @@ int fd_brief_compute(fd_ctx *c, const uint8_t *frames, int frames_on_device, int
                                  {{out_bits, a.out_bits, sizeof(uint32_t) * nw}, {out_valid, a.out_valid, 1}});
     } else if (!frames_on_device) {
         FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host frames must stay valid until copied
+    }
+    return FD_OK;
+}
+
+// Hamming matcher (fd_match.hip): with cross_check the kernel runs twice, first with the roles swapped
+// into the reverse table (the best query of every train descriptor), then forward, where it applies the
+// tests, the reverse table among them; out_counts is zeroed on the stream before it.
+int fd_brief_match(fd_ctx *c, int batch, const fd_match_opts *opts, const uint32_t *q_bits, const uint8_t *q_valid,
+                   const int32_t *q_counts, int32_t q_stride, const uint32_t *t_bits, const uint8_t *t_valid,
+                   const int32_t *t_counts, int32_t t_stride, int32_t *out_idx, int32_t *out_dist, int32_t *out_counts,
+                   int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_bits || !t_bits || !out_idx) return fail(c, FD_ERR_INVALID, "bad arguments");
+    if (batch < 1 || q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "need batch >= 1 and strides >= 0");
+    if (opts->length < 1 || opts->length > 256) return fail(c, FD_ERR_INVALID, "length must be in [1, 256]");
+    if (!std::isfinite(opts->max_ratio)) return fail(c, FD_ERR_INVALID, "max_ratio must be finite");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    if (q_stride == 0) {  // no query slots: every frame has 0 matches
+        if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+        if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
+        return FD_OK;
+    }
+    const size_t nw = static_cast<size_t>((opts->length + 31) / 32);
+    const size_t qslots = static_cast<size_t>(batch) * q_stride, tslots = static_cast<size_t>(batch) * t_stride;
+    fdk::MatchArgs a{};
+    a.a_stride = q_stride;
+    a.b_stride = t_stride;
+    a.batch = batch;
+    a.length = opts->length;
+    a.max_distance = opts->max_distance;
+    a.max_ratio = opts->max_ratio;
+    if (io_on_device) {
+        a.a_bits = q_bits;
+        a.a_valid = q_valid;
+        a.a_counts = q_counts;
+        a.b_bits = t_bits;
+        a.b_valid = t_valid;
+        a.b_counts = t_counts;
+        a.out_idx = out_idx;
+        a.out_dist = out_dist;
+        a.out_counts = out_counts;
+    } else {
+        // one side's three arrays into their staging buffers (absent ones stay null: all valid / stride each)
+        auto stage = [&](const uint32_t *bits, const uint8_t *valid, const int32_t *counts, size_t slots, DevBuf &dbits,
+                         DevBuf &dvalid, DevBuf &dcounts, const uint32_t *&obits, const uint8_t *&ovalid,
+                         const int32_t *&ocounts) -> int {
+            FD_HIP_TRY(c, ensure_as(c, dbits, nw * slots, obits));
+            if (slots) FD_HIP_TRY(c, hipMemcpyAsync(dbits.p, bits, sizeof(uint32_t) * nw * slots, hipMemcpyHostToDevice, c->stream));
+            if (valid) {
+                FD_HIP_TRY(c, ensure_as(c, dvalid, slots, ovalid));
+                if (slots) FD_HIP_TRY(c, hipMemcpyAsync(dvalid.p, valid, slots, hipMemcpyHostToDevice, c->stream));
+            }
+            if (counts) {
+                FD_HIP_TRY(c, ensure_as(c, dcounts, batch, ocounts));
+                FD_HIP_TRY(c, hipMemcpyAsync(dcounts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
+            }
+            return FD_OK;
+        };
+        if ((rc = stage(q_bits, q_valid, q_counts, qslots, c->m_qbits, c->m_qvalid, c->m_qcounts, a.a_bits, a.a_valid,
+                        a.a_counts)))
+            return rc;
+        if ((rc = stage(t_bits, t_valid, t_counts, tslots, c->m_tbits, c->m_tvalid, c->m_tcounts, a.b_bits, a.b_valid,
+                        a.b_counts)))
+            return rc;
+        FD_HIP_TRY(c, ensure_as(c, c->m_idx, qslots, a.out_idx));
+        if (out_dist) FD_HIP_TRY(c, ensure_as(c, c->m_dist, 2 * qslots, a.out_dist));
+        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->m_counts, batch, a.out_counts));
+    }
+    if (opts->cross_check && t_stride > 0) {
+        int32_t *rev = nullptr;
+        FD_HIP_TRY(c, ensure_as(c, c->m_rev, tslots, rev));
+        fdk::MatchArgs r{};
+        r.a_bits = a.b_bits;
+        r.a_valid = a.b_valid;
+        r.a_counts = a.b_counts;
+        r.a_stride = t_stride;
+        r.b_bits = a.a_bits;
+        r.b_valid = a.a_valid;
+        r.b_counts = a.a_counts;
+        r.b_stride = q_stride;
+        r.batch = batch;
+        r.length = opts->length;
+        r.out_idx = rev;
+        r.max_distance = -1;
+        FD_HIP_TRY(c, fdk::launch_brief_match(r, c->stream));
+        a.rev = rev;
+    }
+    if (a.out_counts) FD_HIP_TRY(c, hipMemsetAsync(a.out_counts, 0, sizeof(int32_t) * batch, c->stream));
+    FD_HIP_TRY(c, fdk::launch_brief_match(a, c->stream));
+    if (!io_on_device) {
+        if (out_counts)
+            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
+        return copy_back_written(c, q_counts, batch, q_stride,
+                                 {{out_idx, a.out_idx, sizeof(int32_t)}, {out_dist, a.out_dist, 2 * sizeof(int32_t)}});
     }
     return FD_OK;
 }

@@ -1,0 +1,111 @@
+"""Nearest-neighbour Hamming matching of BRIEF descriptors over the C ABI (fd_brief_match).
+
+An MI355X extension (the reference has no matcher): the stage after detect_points -> brief_compute, on
+the same [batch][stride] layouts, so a detect -> describe -> match chain stays on the GPU. The
+semantics (validity, ties, the three acceptance tests) are in include/fd_hip.h.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import fd_match_opts
+from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
+
+
+@dataclass
+class MatchResult:
+    idx: object     # int32 [B, Sq]: accepted train index per query slot, else -1
+    dist: object    # int32 [B, Sq, 2]: raw best / second-best distance (-1: absent)
+    counts: object  # int32 [B]: accepted matches per frame
+
+
+def _ptr(x):
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def _host_side(bits, valid, counts, nw, name):
+    w = np.asarray(bits)
+    if w.dtype not in (np.uint32, np.int32):
+        raise TypeError(f"{name}_bits must be int32 or uint32 words")
+    w = np.ascontiguousarray(w).view(np.uint32)
+    if w.ndim == 2:
+        w = w[None]
+    if w.ndim != 3 or w.shape[2] != nw:
+        raise ValueError(f"{name}_bits must be [batch, S, {nw}] or [S, {nw}]")
+    b, s = int(w.shape[0]), int(w.shape[1])
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
+    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
+    return w, v, c, b, s
+
+
+def _device_side(bits, valid, counts, nw, name):
+    import torch
+
+    if bits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise TypeError(f"{name}_bits must be int32 or uint32 words")
+    w = bits.contiguous()
+    if w.dim() == 2:
+        w = w.unsqueeze(0)
+    if w.dim() != 3 or w.shape[2] != nw:
+        raise ValueError(f"{name}_bits must be [batch, S, {nw}] or [S, {nw}]")
+    b, s = int(w.shape[0]), int(w.shape[1])
+    v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
+    c = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
+    return w, v, c, b, s
+
+
+def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_valid=None, length: int = 256,
+                max_distance: int = -1, max_ratio: float = 0.0, cross_check: bool = False, out=None,
+                ctx: Context | None = None) -> MatchResult:
+    """fd_brief_match for a batch: frame b of the query set against frame b of the train set.
+
+    q_bits / t_bits: int32 or uint32 words [B, S, ceil(length/32)] or [S, words] (batch 1), as
+    brief_compute returns them; *_counts int32 [B] (None = S each; detect_points' device counts pass as
+    they are); *_valid uint8 [B, S] (None = all valid). Host (numpy) inputs give numpy outputs; torch
+    device inputs give torch outputs, asynchronous on torch's current stream. Slots >= q_counts[b] of
+    idx and dist are -1. Device path only: out = preallocated contiguous int32 tensors (idx [B, Sq],
+    dist [B, Sq, 2], counts [B]); slots >= q_counts[b] then keep their contents and the call is kernels
+    only (graph-capturable once a first call of the shape has run).
+    """
+    ctx = _resolve_ctx(ctx, q_bits, t_bits)
+    nw = (int(length) + 31) // 32 if 1 <= int(length) <= 256 else 0
+    opts = fd_match_opts(int(length), int(max_distance), float(max_ratio), 1 if cross_check else 0)
+    on_dev = _is_torch_device_tensor(q_bits)
+    if on_dev != _is_torch_device_tensor(t_bits):
+        raise ValueError("q_bits and t_bits must both be device tensors or both host arrays")
+    if nw == 0:  # (the library reports the bad length: any word count is taken)
+        nw = int(q_bits.shape[-1])
+    side = _device_side if on_dev else _host_side
+    qw, qv, qc, b, sq = side(q_bits, q_valid, q_counts, nw, "q")
+    tw, tv, tc, tb, st = side(t_bits, t_valid, t_counts, nw, "t")
+    if tb != b:
+        raise ValueError("q_bits and t_bits must have the same batch")
+    if on_dev:
+        import torch
+
+        if out is not None:
+            idx, dist, counts = out
+            for t, shape in ((idx, (b, sq)), (dist, (b, sq, 2)), (counts, (b,))):
+                if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+                    raise ValueError(f"out must be contiguous int32 tensors of shapes {(b, sq)}, {(b, sq, 2)}, {(b,)}")
+        else:
+            idx = torch.full((b, sq), -1, dtype=torch.int32, device=qw.device)
+            dist = torch.full((b, sq, 2), -1, dtype=torch.int32, device=qw.device)
+            counts = torch.zeros((b,), dtype=torch.int32, device=qw.device)
+    else:
+        if out is not None:
+            raise ValueError("out= is for device tensors")
+        idx = np.full((b, sq), -1, np.int32)
+        dist = np.full((b, sq, 2), -1, np.int32)
+        counts = np.zeros((b,), np.int32)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_brief_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qw), _ptr(qv), _ptr(qc), sq, _ptr(tw), _ptr(tv),
+                                    _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return MatchResult(idx, dist, counts)

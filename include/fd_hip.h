@@ -300,6 +300,50 @@ int fd_brief_compute(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, i
                      const fd_brief_opts *opts, const float *uv, const int32_t *counts, int32_t stride,
                      uint32_t *out_bits, uint8_t *out_valid, int io_on_device);
 
+/* ---- Hamming matcher for BRIEF descriptors (MI355X extension: the reference has no matcher) -------- */
+typedef struct fd_match_opts {
+    int32_t length;       /* bits per descriptor, 1..256 (fd_brief_opts::length); words = ceil(length/32) */
+    int32_t max_distance; /* reject a best match with distance > max_distance; < 0: no bound */
+    float   max_ratio;    /* ratio test: accept only if (float)d1 < max_ratio * (float)d2; <= 0: off */
+    int32_t cross_check;  /* 1: accept q -> t only if t's best query is q */
+} fd_match_opts;
+
+/*
+ * fd_brief_match -- nearest neighbour in Hamming distance of every query descriptor among the train
+ * descriptors, frame b of the query set against frame b of the train set. Layouts are what
+ * fd_brief_compute writes: *_bits [batch][stride][ceil(length/32)] uint32, *_valid [batch][stride]
+ * (NULL = all valid), *_counts int32 [batch] (NULL = stride each; bits 25..31 are ignored, so
+ * fd_points_detect's device counts can be passed as they are). Matching frame i of one batch against
+ * its frame i + 1 is the same call with the train pointers advanced by one frame and batch - 1.
+ * Distance: popcount of the xor over bits 0..length-1; the bits above `length` in the last word are
+ * masked here, on both sides. An invalid train descriptor is never a candidate; an invalid query gets
+ * out_idx -1 and both distances -1 (invalid descriptors are all-zero words and would otherwise match
+ * each other at distance 0).
+ * out_dist [batch][q_stride][2] (NULL to skip): [0] the smallest distance to a valid train descriptor,
+ * [1] the smallest distance to a valid train descriptor with another index than the best one (equal to
+ * [0] on a tie); -1 when absent (no valid train descriptor, or only one). Both are raw values, written
+ * whether or not the match is accepted. Equal distances go to the lowest train index (what a serial
+ * scan with `<` gives).
+ * out_idx [batch][q_stride]: the best train index if it passes every enabled test, else -1. Tests:
+ * max_distance (rejects d1 > max_distance); the ratio test, one float multiply and one compare
+ * ((float)d1 < max_ratio * (float)d2, skipped when d2 is absent); cross_check (the train descriptor's
+ * best query -- over the frame's valid queries, smallest distance, lowest query index on ties,
+ * independent of the other two tests -- must be this query).
+ * out_counts [batch] (NULL to skip): accepted matches among slots < q_counts[b]. Slots >= q_counts[b]
+ * of out_idx and out_dist are not written. q_stride 0: nothing but out_counts = 0; t_stride 0: as all
+ * train counts 0.
+ * All pointers are device pointers when io_on_device: the call is then asynchronous on the context's
+ * stream, and graph-capturable once a first call of the shape has sized the workspace (the
+ * cross-check's reverse table; growing it under capture fails). Host pointers otherwise: staged
+ * through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx / opts / q_bits / t_bits / out_idx NULL, length outside 1..256, a negative
+ * stride, batch < 1, a non-finite max_ratio.
+ */
+int fd_brief_match(fd_ctx *ctx, int batch, const fd_match_opts *opts,
+                   const uint32_t *q_bits, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                   const uint32_t *t_bits, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                   int32_t *out_idx, int32_t *out_dist, int32_t *out_counts, int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

@@ -1,0 +1,67 @@
+// BriefMatcher: nearest-neighbour Hamming matching of BriefType descriptors over the MI355X kernel of
+// libfdhip.so (fd_brief_match).
+//
+// MI355X extension: the reference has no matcher (its demos stop at the descriptors). The semantics are
+// those of fd_brief_match (include/fd_hip.h): equal distances go to the lowest train index, an invalid
+// descriptor is neither matched nor a candidate, and a best match is reported only if it passes the
+// enabled tests of Options.
+#ifndef FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
+#define FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "descriptor_brief.h"
+
+struct fd_ctx;
+
+namespace feature_detector {
+
+/* Class BriefMatcher Declaration. */
+class BriefMatcher {
+public:
+    struct Options {
+        int32_t kMaxDistance = -1;  // reject a best match farther than this; < 0: no bound
+        float kMaxRatio = 0.0f;     // accept only if best < kMaxRatio * second best; <= 0: off
+        bool kCrossCheck = false;   // accept q -> t only if t's best query is q
+    };
+
+public:
+    BriefMatcher() = default;
+    virtual ~BriefMatcher();
+    BriefMatcher(const BriefMatcher &) = delete;
+    BriefMatcher &operator=(const BriefMatcher &) = delete;
+
+    // train_index[i]: the train descriptor matched to query[i], or -1. distance (optional): [i] the raw
+    // smallest distance of query[i] to a valid train descriptor, accepted or not (-1: none).
+    // query_valid / train_valid (optional, one flag per descriptor): BriefDescriptor leaves all-zero
+    // descriptors for keypoints it cannot describe; flag them 0 to keep them out of the matching.
+    // False for empty inputs, descriptors of unequal length or a length outside 1..256, flag vectors of
+    // the wrong size, or a libfdhip failure (last_error()).
+    bool Match(const std::vector<BriefType> &query, const std::vector<BriefType> &train, std::vector<int32_t> &train_index,
+               std::vector<int32_t> *distance = nullptr, const std::vector<uint8_t> *query_valid = nullptr,
+               const std::vector<uint8_t> *train_valid = nullptr);
+
+    // Reference for member variables.
+    Options &options() { return options_; }
+    const Options &options() const { return options_; }
+
+    void set_device(int device);
+    int device() const { return device_; }
+    const std::string &last_error() const { return error_; }
+
+private:
+    fd_ctx *Context();
+    bool Fail(const std::string &what);
+
+private:
+    Options options_;
+    fd_ctx *ctx_ = nullptr;
+    int device_ = -1;
+    std::string error_;
+};
+
+}  // namespace feature_detector
+
+#endif  // FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_

@@ -6,6 +6,9 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      (--kind shi_tomasi by default: the north-star kernel)
   --shape fast720    fd_points_detect, FAST, 1280x720 batch 64 (BASELINE configs[2]), 10 calls
   --shape fastbrief  the same + BRIEF-256 on the detected keypoints (fd_brief_compute), 10 calls
+  --shape fastmatch  FAST (need 500, dist 15) + BRIEF-256 + fd_brief_match of frame i against frame i + 1 of
+                     the batch (63 frame pairs, detect's device counts and BRIEF's valid flags in place), 10
+                     calls (--cross-check: with the cross-check, two k_brief_match launches per call)
   --shape lsd        fd_lsd_map (dense) and fd_lsd_lines (compact map + host stage), 1920x1080 batch 256,
                      64-px checker + noise (BASELINE configs[3]), 3 calls each (--kind dense / compact: one;
                      dense_unpitched: dense maps with unpadded rows)
@@ -24,10 +27,11 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
+p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
 g = torch.Generator(device="cuda")
@@ -107,6 +111,17 @@ elif a.shape == "fastbrief":  # BASELINE configs[2]: FAST detect + BRIEF-256 on 
     for _ in range(a.calls or 10):
         res = fd.detect_points(kind, frames, 200, 20, THR[kind])
         fd.brief_compute(frames, res.xy, res.counts, length=256, half_patch_size=8)
+elif a.shape == "fastmatch":  # configs[2]'s shape with need 500, then the matcher on consecutive frames
+    kind = "fast"
+    frames = noise(64, 720, 1280)
+    out = (torch.empty((63, 501), dtype=torch.int32, device="cuda"), torch.empty((63, 501, 2), dtype=torch.int32, device="cuda"),
+           torch.empty((63,), dtype=torch.int32, device="cuda"))
+    for _ in range(a.calls or 10):
+        res = fd.detect_points(kind, frames, 500, 15, THR[kind])
+        bits, valid = fd.brief_compute(frames, res.xy, res.counts, length=256, half_patch_size=8, with_valid=True)
+        fd.brief_match(bits[:-1], bits[1:], res.counts[:-1], res.counts[1:], valid[:-1], valid[1:], max_distance=64,
+                       max_ratio=0.9, cross_check=a.cross_check, out=out)
+    print("matches per frame pair (mean):", float(out[2].float().mean()), "keypoints:", float((res.counts & 0x1FFFFFF).float().mean()))
 else:
     kind = a.kind or "fast"
     frames = noise(64, 720, 1280)
