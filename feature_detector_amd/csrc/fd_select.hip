@@ -126,6 +126,7 @@ struct alignas(16) SelectLds {
     // 1024 threads, tools/calib/wg_probe.hip)
     uint32_t vote[2];
     int s_done, s_acc;
+    int cut0[2];  // the first chunk's level-0 cuts for kSubChunk / kSelectChunk keys (written with suf0)
     uint64_t st[32];  // diagnostic phase clocks (a.stamps only); 16..31 free for ad-hoc probes
 };
 
@@ -239,9 +240,18 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
 
     if (use_grid && !grid_in_lds)
         for (int i = tid; i < cells; i += nthr) grid_g[i] = grid_empty(rows, cols, d);
+    // The LDS grid is initialised here, under the first loads' latency, unless its space is the landing
+    // zone of the list prefetch (then after that round is consumed, below). Nothing reads the grid before
+    // the first sub-chunk's greedy, and the suffix scan's barriers below come first.
+    const bool grid_early = use_grid && grid_in_lds && !list_prefetch;
+    if (grid_early)
+        for (int i = tid; i < cells; i += nthr) grid_lds[i] = grid_empty(rows, cols, d);
     if (tid == 0) {
         s_done = 0;
         s_acc = 0;
+        gcount = 0;  // (the first chunk's seg_gather starts from these without a barrier of its own)
+        L.seg_more[0] = 0;
+        L.seg_more[1] = 0;
         L.vote[0] = 0;
         L.vote[1] = 0;
         prefix[0] = 0;
@@ -369,6 +379,22 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         o.x = o.y + hv[0];
         reinterpret_cast<uint4 *>(suf0)[tid] = o;
         if (tid == 0) suf0[kHistBins] = 0;
+        // The first chunk's cuts, first_le(suf0, 0, kHistBins, 0, lim) for lim = kSubChunk and kSelectChunk,
+        // from the registers: S is non-increasing and S[kHistBins] = 0 <= lim, so exactly one x in
+        // [0, kHistBins] has S[x] <= lim < S[x - 1] (or x = 0), the smallest x with S[x] <= lim; the thread
+        // holding S[x - 1] and S[x] (sv: its four bins and the next thread's first) stores it. The barrier
+        // below publishes it with suf0: first_le's own two barriers and its chain of LDS reads are gone.
+        {
+            const uint32_t sv[5] = {o.x, o.y, o.z, o.w, incl - sacc + after};
+            constexpr uint32_t lims[2] = {static_cast<uint32_t>(kSubChunk), static_cast<uint32_t>(kSelectChunk)};
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (tid == 0 && sv[0] <= lims[k]) L.cut0[k] = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (sv[j + 1] <= lims[k] && sv[j] > lims[k]) L.cut0[k] = 4 * tid + j + 1;
+            }
+        }
         __syncthreads();
     } else {
         for (int j = 0; j < kHistPerThread; ++j) suf0[tid + j * NT] = hv[j];
@@ -557,13 +583,17 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
     // First chunk from the sorted segments (PointsArgs::segdesc): every workgroup segment of the list
     // is ordered by level-0 bin, descending, so the keys of bins >= lo are a prefix of each segment.
     // T threads per segment read its entries T at a time while the last one read is still >= lo.
-    auto seg_gather = [&](int lo, uint32_t k32hi) {  // keys of level-0 bins [lo, k32hi >> 20]
-        if (tid == 0) {
-            gcount = 0;
-            L.seg_more[0] = 0;
-            L.seg_more[1] = 0;
+    auto seg_gather = [&](int lo, uint32_t k32hi, bool first) {  // keys of level-0 bins [lo, k32hi >> 20]
+        // (the first chunk: thread 0 zeroed these words before the suffix scan's barriers and nothing has
+        // touched them since, so no barrier is needed here)
+        if (!first) {
+            if (tid == 0) {
+                gcount = 0;
+                L.seg_more[0] = 0;
+                L.seg_more[1] = 0;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         FD_STAMP(25);
         const uint32_t k32lo = static_cast<uint32_t>(lo) << 20;
         for (int r = 0;; ++r) {
@@ -629,9 +659,14 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         // then ordered in place (no sub-chunk extract), and frames whose greedy runs past it take the
         // next chunk through the main loop's list pass.
         int lo_b = kHistBins;
-        if (!WIDE && seg_mode) lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSubChunk));
-        if (lo_b >= kHistBins)  // (or the top bin alone exceeds a sub-chunk)
-            lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSelectChunk));
+        if constexpr (kHist4) {  // both cuts came with the suffix sums
+            if (!WIDE && seg_mode) lo_b = L.cut0[0];
+            if (lo_b >= kHistBins) lo_b = L.cut0[1];  // (or the top bin alone exceeds a sub-chunk)
+        } else {
+            if (!WIDE && seg_mode) lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSubChunk));
+            if (lo_b >= kHistBins)  // (or the top bin alone exceeds a sub-chunk)
+                lo_b = first_le(suf0, 0, kHistBins, 0u, static_cast<uint32_t>(kSelectChunk));
+        }
         first_lo = lo_b;
         FD_STAMP(21);
         if (lo_b < kHistBins && suf0[lo_b] > 0) {
@@ -642,7 +677,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
                 if (tid == 0) gcount = want;
                 __syncthreads();
             } else if (seg_mode && seg_bad == 0) {
-                seg_gather(lo_b, 0xFFFFFFFFu);
+                seg_gather(lo_b, 0xFFFFFFFFu, true);
             } else if (wk && a.wide_eager) {
                 // long scans expected (FAST: scores plus a slowly growing offset crowd the top bins):
                 // the first list pass already collects the bins below the first chunk
@@ -661,14 +696,16 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
         }
     }
     FD_STAMP(22);
-    if (use_grid && grid_in_lds) {  // the first round's LDS-direct loads are consumed (or never used)
-        // vmcnt(0): no load still landing in this space (only if they were issued: the wait would
-        // also hold for this thread's outstanding global stores and atomics, a memory round trip)
-        if (list_prefetch) __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (use_grid && grid_in_lds && !grid_early) {  // the first round's LDS-direct loads are consumed (or never used)
+        // vmcnt(0): no load still landing in this space
+        __builtin_amdgcn_s_waitcnt(0x0F70);
         __syncthreads();
         for (int i = tid; i < cells; i += nthr) grid_lds[i] = grid_empty(rows, cols, d);
         __syncthreads();
     }
+    // (grid_early: no barrier here. The grid was written before the suffix scan's barriers; the words the
+    // first-chunk gather leaves behind -- sup, gcount, seg_more -- are ordered by that gather's own last
+    // barrier, which every first-chunk path ends with.)
     FD_STAMP(3);
     int level = 0;
     int hi = (1 << lvl_width(0)) - 1;
@@ -728,13 +765,20 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
             const uint32_t k32lo = static_cast<uint32_t>(klo >> 32), k32hi = static_cast<uint32_t>(khi >> 32);
             const bool k32_exact = rem >= 32;  // [klo, khi] == all keys whose top 32 bits are in [k32lo, k32hi]
             // gather the chunk: wave-uniform loop bounds, one LDS atomic per wave per round
+            // (the chunk gathered before the loop: sup holds it, complete since that gather's last barrier,
+            // which also published the gather's count in gcount; nothing below reads gcount again before
+            // rewriting it behind a barrier -- so the two barriers are not run, and the count guard
+            // compares what the gather found, not cnt with itself)
+            const bool pre_gathered = first_ready && level == 0;
+            if (pre_gathered) {
+                first_ready = false;
+                if (tid == 0 && gcount != cnt)  // consistency guard: gathered == histogram count
+                    atomicOr(&a.status[f], 0x04000000u);
+            } else {
             if (tid == 0) gcount = 0;
             __syncthreads();
-            if (first_ready && level == 0) {  // gathered before the loop (sup holds it)
-                first_ready = false;
-                if (tid == 0) gcount = cnt;
-            } else if (!WIDE && seg_mode && seg_bad == 0 && level == 0 && !a.pre_keys) {
-                seg_gather(lo, k32hi);  // a later level-0 chunk: from the sorted segments' prefixes
+            if (!WIDE && seg_mode && seg_bad == 0 && level == 0 && !a.pre_keys) {
+                seg_gather(lo, k32hi, false);  // a later level-0 chunk: from the sorted segments' prefixes
             } else if (level == 0 && (ensure_wide(hi), in_wide(klo))) {
                 wide_pick(klo, khi);
             } else if (in_wide(klo)) {
@@ -775,6 +819,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
             __syncthreads();
             if (tid == 0 && gcount != cnt)  // consistency guard: gathered == histogram count
                 atomicOr(&a.status[f], 0x04000000u);
+            }
             FD_STAMP(3);  // gather
             const uint32_t s1 = static_cast<uint32_t>(d + 1);
             const float rcp_cols = 1.0f / static_cast<float>(cols), rcp_s1 = 1.0f / static_cast<float>(s1);
