@@ -11,8 +11,9 @@
 // gx, gy are half-integers, so gx^2 + gy^2 is exact and the correctly rounded sqrt makes `norm` and
 // `valid` bit-exact. The angle uses the reference's libm: std::atan2(float, float) is glibc 2.35's
 // atan2f, an fdlibm-derived float algorithm (sysdeps/ieee754/flt-32/e_atan2f.c + s_atanf.c). It is
-// restated below from the published fdlibm algorithm; tests/test_lsd_atan2.py shows it equals the
-// host atan2f bit for bit over the whole LSD input domain (every half-integer (gx, gy) pair).
+// restated below from the published fdlibm algorithm; test_angle_domain_exhaustive in
+// tests/test_gpu_lsd.py shows it equals the host atan2f bit for bit over the whole LSD input domain
+// (every half-integer (gx, gy) pair).
 #include "fd_device.h"
 #include "fd_hip.h"
 #include "fd_kernels.h"

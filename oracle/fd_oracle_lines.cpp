@@ -208,19 +208,9 @@ struct Lsd {
     }
 };
 
-}  // namespace
-
-extern "C" {
-
-// DetectGoodFeatures (:12-54) on one frame. opts: kMinValidGradientNorm, kMinToleranceAngleResidualInRad,
-// kMinValidLineLengthInPixel, kMaxToleranceInlierRation. out: up to cap rectangles as 12 floats each
-// (start x, y, end x, y, center x, y, length, width, angle, dir x, y, inlier ratio), start/end offset
-// by 0.5 (:43-44). Returns the number of segments; -1 for the reference's `false` (:14).
-int64_t orc_lsd_lines(const uint8_t *img, int rows, int cols, const float *opts, uint32_t needed, float *out,
-                      int64_t cap) {
-    if (img == nullptr || rows < 2 || cols < 2) return -1;  // :14
-    if (needed == 0) return 0;                              // :15
-    Lsd L;
+// DetectGoodFeatures' body (:18-46) on L: scan, seeds in norm order, grow, fit, filter. Writes up to cap
+// rectangles (12 floats each) and returns their number; L keeps the pixels' final state.
+int64_t Detect(Lsd &L, const uint8_t *img, int rows, int cols, const float *opts, float *out, int64_t cap) {
     L.min_norm = opts[0];
     L.tol = opts[1];
     L.min_len = opts[2];
@@ -249,6 +239,49 @@ int64_t orc_lsd_lines(const uint8_t *img, int rows, int cols, const float *opts,
             std::copy(v, v + 12, out + 12 * n);
         }
         ++n;
+    }
+    return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+// DetectGoodFeatures (:12-54) on one frame. opts: kMinValidGradientNorm, kMinToleranceAngleResidualInRad,
+// kMinValidLineLengthInPixel, kMaxToleranceInlierRation. out: up to cap rectangles as 12 floats each
+// (start x, y, end x, y, center x, y, length, width, angle, dir x, y, inlier ratio), start/end offset
+// by 0.5 (:43-44). Returns the number of segments; -1 for the reference's `false` (:14).
+int64_t orc_lsd_lines(const uint8_t *img, int rows, int cols, const float *opts, uint32_t needed, float *out,
+                      int64_t cap) {
+    if (img == nullptr || rows < 2 || cols < 2) return -1;  // :14
+    if (needed == 0) return 0;                              // :15
+    Lsd L;
+    return Detect(L, img, rows, cols, opts, out, cap);
+}
+
+// The same detection, read out as the per-pixel state it leaves behind: for every valid pixel in the scan's
+// column-major order (:71-72, the order of sorted_pixels_ before its std::sort) its map index
+// (row * (cols-1) + col), gradient norm, level-line angle and final is_used. Writes up to cap entries,
+// returns their number; 0 when nothing is detected (:15), -1 for the reference's `false` (:14).
+int64_t orc_lsd_lines_state(const uint8_t *img, int rows, int cols, const float *opts, uint32_t needed, int32_t *idx,
+                            float *norm, float *angle, uint8_t *used, int64_t cap) {
+    if (img == nullptr || rows < 2 || cols < 2) return -1;  // :14
+    if (needed == 0) return 0;                              // :15
+    Lsd L;
+    Detect(L, img, rows, cols, opts, nullptr, 0);
+    int64_t n = 0;
+    for (int col = 1; col < cols - 2; ++col) {
+        for (int row = 1; row < rows - 2; ++row) {
+            const Px &p = L.at(row, col);
+            if (!p.is_valid) continue;
+            if (n < cap) {
+                idx[n] = row * L.pc + col;
+                norm[n] = p.gradient_norm;
+                angle[n] = p.line_level_angle;
+                used[n] = p.is_used ? 1 : 0;
+            }
+            ++n;
+        }
     }
     return n;
 }

@@ -56,6 +56,7 @@ def lib():
             "orc_nn_select_list": (i32, [_P, _P, i64, i32, i32, i32, i32, i32, _P, i32, _P, _P, i32]),
             "orc_nn_descriptors": (None, [_P, i32, i32, i32, _P, i32, _P]),
             "orc_lsd_lines": (i64, [_P, i32, i32, _P, u32, _P, i64]),
+            "orc_lsd_lines_state": (i64, [_P, i32, i32, _P, u32, _P, _P, _P, _P, i64]),
             "orc_ref_state_new": (_P, []),
             "orc_ref_state_free": (None, [_P]),
             "orc_detect_refflow": (i32, [_P, i32, _P, i32, i32, i32, f32, u32, _P, i32]),
@@ -261,6 +262,19 @@ def lsd_lines(img, needed=1, min_norm=20.0, tol_rad=LSD_TOL_RAD, min_length=20.0
     if n > cap:
         raise RuntimeError(f"cap {cap} < {n} lines")
     return out[:max(n, 0)].copy()
+
+
+def lsd_lines_state(img, needed=1, min_norm=20.0, tol_rad=LSD_TOL_RAD, min_length=20.0, min_inlier=0.6):
+    """The pixel state lsd_lines' detection leaves behind: (idx int32, norm f32, angle f32, used u8) of the
+    valid pixels in the scan's column-major order (feature_line_detector.cpp:71-72), used = final is_used."""
+    img = np.ascontiguousarray(img, np.uint8)
+    R, C = img.shape
+    opts = np.array([min_norm, tol_rad, min_length, min_inlier], np.float32)
+    cap = max((R - 1) * (C - 1), 1)
+    idx, norm, ang, used = np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.float32), np.zeros(cap, np.uint8)
+    n = max(lib().orc_lsd_lines_state(_ptr(img), R, C, _ptr(opts), needed, _ptr(idx), _ptr(norm), _ptr(ang), _ptr(used),
+                                      cap), 0)
+    return idx[:n].copy(), norm[:n].copy(), ang[:n].copy(), used[:n].copy()
 
 
 def lsd_min_region_size(rows, cols, tol_rad=22.5 * 3.14159265358979323846 / 180.0):

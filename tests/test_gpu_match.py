@@ -59,11 +59,25 @@ def assert_same(got, exp):
         assert np.array_equal(g, e), name
 
 
-@pytest.mark.parametrize("length", [256, 1, 31, 32, 33, 100, 255])
+def kernel_words(length):
+    """(nw, NW): a descriptor's words (the row pitch of the bit arrays) and the words per lane and LDS row of the
+    kernel instance launch_brief_match takes for it (1, 2, 4 or 8)."""
+    nw = (length + 31) // 32
+    return nw, 1 if nw <= 1 else 2 if nw <= 2 else 4 if nw <= 4 else 8
+
+
+# every nw in 1..8; 65, 96 (nw 3 in NW 4) and 129 .. 224 (nw 5, 6, 7 in NW 8): the row pitch differs from the
+# LDS pitch, and the tail mask (none at 96, 160, 192, 224) sits in a word other than the last register
+WORDS = {1: (1, 1), 31: (1, 1), 32: (1, 1), 33: (2, 2), 65: (3, 4), 96: (3, 4), 97: (4, 4), 100: (4, 4), 129: (5, 8),
+         160: (5, 8), 161: (6, 8), 192: (6, 8), 224: (7, 8), 255: (8, 8), 256: (8, 8)}
+
+
+@pytest.mark.parametrize("length", [256, 1, 31, 32, 33, 100, 255, 65, 96, 97, 129, 160, 161, 192, 224])
 def test_random_counts_and_unwritten_slots(fd, length):
     """Random words (so the bits above `length` in the last word are garbage on both sides), counts that
     cut the frames, random valid flags; the raw C call on host pointers, then fd.brief_match."""
     rng = np.random.default_rng(1000 + length)
+    assert kernel_words(length) == WORDS[length]
     nw = (length + 31) // 32
     q, t = rand_words(rng, 3, 70, nw), rand_words(rng, 3, 130, nw)
     qc, tc = np.array([70, 0, 65], np.int32), np.array([130, 5, 1], np.int32)
@@ -162,13 +176,14 @@ def test_acceptance_tests(fd, proto_sets, kw, accepted):
     assert_same((res.idx, res.dist, res.counts), match_ref(q, t, **kw))
 
 
-@pytest.mark.parametrize("length", [256, 12])
+@pytest.mark.parametrize("length", [256, 12, 70, 200])
 @pytest.mark.parametrize("nq,nt", [(63, 65), (64, 64), (65, 63), (255, 257), (256, 256), (257, 255), (1025, 1025)])
 def test_tile_edges(fd, nq, nt, length):
     """Counts around the query tile (64), the LDS train tile (256) and several tiles; 12-bit descriptors
     tie constantly, so the tie rule is exercised across waves and tiles, in both directions."""
     rng = np.random.default_rng(nq * 7 + nt + length)
     nw = (length + 31) // 32
+    assert kernel_words(length) == {256: (8, 8), 12: (1, 1), 70: (3, 4), 200: (7, 8)}[length]
     q, t = rand_words(rng, 1, nq, nw), rand_words(rng, 1, nt, nw)
     qv, tv = (rng.random((1, nq)) < 0.9).astype(np.uint8), (rng.random((1, nt)) < 0.9).astype(np.uint8)
     kw = dict(length=length, cross_check=True, max_ratio=0.99)

@@ -36,6 +36,29 @@ def test_needed_zero_and_tiny_frames(oracle, image_png):
         assert len(oracle.lsd_lines(np.zeros(shape, np.uint8))) == 0
 
 
+def test_lines_state(oracle, image_png):
+    """lsd_lines_state: the valid pixels in scan order with the map's own values, and their final is_used
+    (0/1; none used where no line is found, some where lines are). The no-line frames are ones in which no
+    region reaches the minimal region size, so every region is released (:32-35): a flat frame with one bright
+    pixel (4 valid pixels) and a flat frame. (A region that is large enough but fails the length / inlier test
+    keeps its pixels used, :40, so a noise frame without lines may still end with used pixels.)"""
+    spot = np.full((120, 160), 90, np.uint8)
+    spot[60, 80] = 255
+    checker = oracle.make_frame("checker", 7, 240, 320, 24)
+    for img, lines, valid in ((image_png, True, None), (checker, True, None), (spot, False, 4),
+                              (np.zeros((60, 80), np.uint8), False, 0)):
+        assert (len(oracle.lsd_lines(img)) > 0) == lines
+        idx, norm, ang, used = oracle.lsd_lines_state(img)
+        en, ea, ev, eidx = oracle.lsd_map(img)
+        assert valid is None or len(idx) == valid
+        assert np.array_equal(idx, eidx)
+        assert np.array_equal(norm.view(np.uint32), en.reshape(-1)[eidx].view(np.uint32))
+        assert np.array_equal(ang.view(np.uint32), ea.reshape(-1)[eidx].view(np.uint32))
+        assert np.isin(used, (0, 1)).all()
+        assert bool(used.any()) == lines
+    assert len(oracle.lsd_lines_state(image_png, needed=0)[0]) == 0  # :15
+
+
 def test_ramp_overflows_ring_but_is_deterministic(oracle):
     # a smooth diagonal ramp: one huge aligned region whose BFS frontier exceeds the 1000-entry
     # CircularBuffer (overflow policy assumed: drop the oldest); the result must at least be stable
