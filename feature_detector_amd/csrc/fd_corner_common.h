@@ -1,10 +1,9 @@
 // Shared device pieces of the corner kernels (fd_points.hip: k_corner, k_fast; fd_corner_lp.hip:
-// k_corner_lp): workgroup -> tile decoding, frame loads, the LDS histogram, and the exact response
-// arithmetic. Each including translation unit gets its own copy (anonymous namespace).
+// k_corner_lp): workgroup -> tile decoding, frame loads and the exact response arithmetic (the candidate
+// lists they write: fd_emit.h). Each including translation unit gets its own copy (anonymous namespace).
 #pragma once
 
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_emit.h"
 
 namespace fdk {
 namespace {
@@ -43,32 +42,6 @@ __device__ __forceinline__ uint32_t load_px4(__amdgpu_buffer_rsrc_t r, int32_t o
     if constexpr (ALIGNED) return buf_load_u32(r, off);
     return buf_load_u8(r, off) | (buf_load_u8(r, off + 1) << 8) | (buf_load_u8(r, off + 2) << 16) |
            (buf_load_u8(r, off + 3) << 24);
-}
-
-// (the per-pixel kernels run 256-thread workgroups: a constant stride, no blockDim load -- whose wait
-// would also hold for every vector-memory operation in flight, e.g. seg_flush's returning atomic)
-constexpr int kPixWg = 256;
-// LDS accesses all issued before any is used (the histogram loops were chains of one LDS round trip,
-// and in the flush one exec-masked branch, per bin group); the clear by 16-byte stores (h is 16-byte
-// aligned in every LDS layout: DetectLdsT, LpLds).
-constexpr int kHistPer = kHistBins / (4 * kPixWg);  // uint4 groups per thread
-__device__ __forceinline__ void hist_clear(uint32_t *h) {
-    uint4 *h4 = reinterpret_cast<uint4 *>(h);
-#pragma unroll
-    for (int k = 0; k < kHistPer; ++k) h4[threadIdx.x + k * kPixWg] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-}
-// The flush keeps one bin per lane per atomic instruction (64 consecutive dwords: a 4-dwords-per-lane
-// pattern spreads each wave instruction over 4x the 64-B atomic requests, measured +4.9 us at batch 1).
-__device__ __forceinline__ void hist_flush(const uint32_t *h, uint32_t *g) {
-    __syncthreads();
-    constexpr int kPer = kHistBins / kPixWg;
-    uint32_t v[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = h[threadIdx.x + k * kPixWg];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k)
-        if (v[k]) atomicAdd(&g[threadIdx.x + k * kPixWg], v[k]);
 }
 
 // Two pixels' float math at a time: <2 x float> arithmetic compiles to v_pk_mul_f32 / v_pk_add_f32 /

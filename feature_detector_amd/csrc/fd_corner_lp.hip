@@ -107,7 +107,7 @@ struct LpGeom {
 };
 
 template <bool HIST>
-struct alignas(16) LpLds {  // (hist is cleared and read as uint4, fd_corner_common.h)
+struct alignas(16) LpLds {  // (hist is cleared and read as uint4, fd_emit.h)
     uint32_t slot[4][lp_slots<true>()][128];  // [wave][slot][0..63 response bits | 64..127 raster index]
     uint32_t hist[kHistBins];
     uint32_t seg_ovf;  // sorted-segment mode: a wave flushed before the end (the segment is unsorted)
@@ -160,20 +160,21 @@ __device__ __forceinline__ void lp_flush(uint32_t &n, const uint32_t *sl, const 
     }
     if (tot == 0) return;
     uint32_t base = 0;
-    if (lane_id() == 0) base = atomicAdd(&a.list_count[f], tot);
+    if (lane_id() == 0) base = atomicAdd(&a.list.count[f], tot);
     base = __builtin_amdgcn_readfirstlane(base);
     // The frame's list as two buffer resources of list_cap entries: a position past the capacity is
     // outside the range and its store is dropped by the hardware (no compare, no 64-bit address math;
     // the launch keeps list_cap * 4 < 2^32, lp_list_ok).
-    const uint32_t cap_b = static_cast<uint32_t>(a.list_cap) * 4u;
-    const auto rr = make_rsrc(a.list_resp + static_cast<int64_t>(f) * a.list_cap, cap_b);
-    const auto ri = make_rsrc(a.list_idx + static_cast<int64_t>(f) * a.list_cap, cap_b);
+    const uint32_t cap_b = static_cast<uint32_t>(a.list.cap) * 4u;
+    const ListFrame d = list_frame(a.list, f);
+    const auto rr = make_rsrc(d.resp, cap_b);
+    const auto ri = make_rsrc(d.idx, cap_b);
     uint32_t off = base;
     for (int j = 0; j < jmax; ++j) {
         const uint64_t b = ballot(n > static_cast<uint32_t>(j));
         if (n > static_cast<uint32_t>(j)) {
             const float r = lp_resp<KIND>(sl, j);
-            if (hist) atomicAdd(&hist[((float_key(r) - a.key_base) << a.key_lz) >> 20], 1u);
+            if (hist) atomicAdd(&hist[level0_bin(r, a.list.key_base, a.list.key_lz)], 1u);
             const uint32_t pos4 = static_cast<uint32_t>(mbcnt64(b, static_cast<int>(off))) << 2;
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rr, static_cast<int>(pos4), 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(sl[j * 128 + 64], ri, static_cast<int>(pos4), 0, 0);
@@ -185,70 +186,23 @@ __device__ __forceinline__ void lp_flush(uint32_t &n, const uint32_t *sl, const 
     n = 0;
 }
 
-// Sorted-segment flush of the lane-private slots (small launches, PointsArgs::segdesc): as seg_flush.
+// The lane-private slots of a wave as a source of the sorted-segment flush (seg_list_flush, fd_emit.h).
 template <int KIND>
-__device__ __forceinline__ void lp_seg_flush(uint32_t &n, const uint32_t *sl, const PointsArgs &a, int f, bool active,
-                                             LpLds<true> &L, uint32_t *ovf, uint32_t (&wtot)[4], uint32_t &wg_base) {
-    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
-    __syncthreads();
-    if (*ovf) {  // part of the workgroup's list is already out unsorted: plain flush (frame marked)
-        if (active) lp_flush<KIND>(n, sl, a, f, L.hist);
-        hist_flush(L.hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);
-        return;
-    }
-    if (!active) n = 0;
-    auto bin_of = [&](float r) { return ((float_key(r) - a.key_base) << a.key_lz) >> 20; };
-    for (int j = 0; j < lp_slots<true>(); ++j) {
-        if (ballot(n > static_cast<uint32_t>(j)) == 0) break;
-        if (n > static_cast<uint32_t>(j)) atomicAdd(&L.hist[bin_of(lp_resp<KIND>(sl, j))], 1u);
-    }
-    hist_flush(L.hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);  // (leads with a barrier)
-    __syncthreads();
-    constexpr int kPer = kHistBins / 256;
-    uint32_t v[kPer], sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) sum += (v[k] = L.hist[kHistBins - 1 - (tid * kPer + k)]);
-    const uint32_t incl = wave_incl_add(sum);
-    if (lane == kWave - 1) wtot[wv] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum, total = 0;
-    for (int q = 0; q < 4; ++q) {
-        run += q < wv ? wtot[q] : 0u;
-        total += wtot[q];
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        L.hist[kHistBins - 1 - (tid * kPer + k)] = run;
-        run += v[k];
-    }
-    if (tid == 0) {
-        wg_base = total ? atomicAdd(&a.list_count[f], total) : 0u;
-        const int g = logical_block() % a.blocks_per_frame;
-        a.segdesc[static_cast<int64_t>(f) * a.blocks_per_frame + g] = make_uint2(wg_base, total);
-    }
-    __syncthreads();
-    float *dr = a.list_resp + static_cast<int64_t>(f) * a.list_cap;
-    uint32_t *di = a.list_idx + static_cast<int64_t>(f) * a.list_cap;
-    const int64_t base = wg_base;
-    const int g = logical_block() % a.blocks_per_frame;
-    uint64_t *head = a.seghead + (static_cast<int64_t>(f) * a.blocks_per_frame + g) * kSegHead;
-    for (int j = 0; j < lp_slots<true>(); ++j) {
-        if (ballot(n > static_cast<uint32_t>(j)) == 0) break;
-        if (n > static_cast<uint32_t>(j)) {
-            const float r = lp_resp<KIND>(sl, j);
-            const uint32_t id = sl[j * 128 + 64];
-            const uint32_t k32 = (float_key(r) - a.key_base) << a.key_lz;
-            const uint32_t lp = atomicAdd(&L.hist[k32 >> 20], 1u);
-            const int64_t pos = base + lp;
-            if (pos < a.list_cap) {
-                dr[pos] = r;
-                di[pos] = id;
-            }
-            if (lp < static_cast<uint32_t>(kSegHead)) head[lp] = (static_cast<uint64_t>(k32) << 32) | static_cast<uint64_t>(~id);
+struct LpSource {
+    uint32_t &n;         // this lane's used slots
+    const uint32_t *sl;  // its slot 0
+    uint32_t *hist;
+    __device__ __forceinline__ uint32_t wave_total() const { return wave_total_add(n); }
+    __device__ __forceinline__ bool counted() const { return false; }
+    template <class F>
+    __device__ __forceinline__ void visit(F &&fn) const {
+        for (int j = 0; j < lp_slots<true>(); ++j) {
+            if (ballot(n > static_cast<uint32_t>(j)) == 0) break;
+            if (n > static_cast<uint32_t>(j)) fn(lp_resp<KIND>(sl, j), sl[j * 128 + 64]);
         }
     }
-    n = 0;
-}
+    __device__ __forceinline__ void flush(const PointsArgs &a, int f) { lp_flush<KIND>(n, sl, a, f, hist); }
+};
 
 // One column's candidate: if x > nb, (x, id) goes to the lane's next slot (LDS byte address A: response
 // word, index word 256 B later) and A advances one slot. Exec-masked to the hit lanes, so only
@@ -470,10 +424,11 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
     uint32_t n = (A - sl_addr) >> 9;  // this lane's used slots
     if constexpr (SEG) {
         __shared__ uint32_t seg_wtot[4], seg_base;
-        lp_seg_flush<KIND>(n, sl, a, f, active, L, &L.seg_ovf, seg_wtot, seg_base);
+        LpSource<KIND> src{n, sl, L.hist};
+        seg_list_flush(src, a, f, logical_block() % a.blocks_per_frame, active, L.hist, &L.seg_ovf, seg_wtot, seg_base);
     } else {
         if (active) lp_flush<KIND>(n, sl, a, f, lhist);
-        if constexpr (HIST) hist_flush(L.hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);
+        if constexpr (HIST) hist_flush(L.hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
     }
 }
 
@@ -481,7 +436,7 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
 
 template <int KIND, int PX>
 static void launch_corner_lp(const PointsArgs &a, dim3 grid, hipStream_t s) {
-    const bool masked = a.mask != nullptr, aligned = a.aligned4 != 0, hist = a.hist0 != nullptr, seg = a.segdesc != nullptr;
+    const bool masked = a.mask != nullptr, aligned = a.aligned4 != 0, hist = a.list.hist0 != nullptr, seg = a.segdesc != nullptr;
 #define FD_LP(M, AL, H, SG) hipLaunchKernelGGL((k_corner_lp<KIND, PX, M, AL, H, SG>), grid, dim3(256), 0, s, a)
 #define FD_LP_A(M, H, SG)              \
     do {                               \
@@ -497,7 +452,7 @@ static void launch_corner_lp(const PointsArgs &a, dim3 grid, hipStream_t s) {
 
 hipError_t launch_corner_lp_any(int kind, const PointsArgs &a, hipStream_t s) {
     const dim3 grid(a.batch * a.blocks_per_frame);
-    if (a.mask != nullptr && a.hist0 == nullptr) return hipErrorInvalidValue;
+    if (a.mask != nullptr && a.list.hist0 == nullptr) return hipErrorInvalidValue;
 #define FD_LPK(K)                                                   \
     do {                                                            \
         if (a.px == 2) launch_corner_lp<K, 2>(a, grid, s);          \

@@ -180,14 +180,17 @@ struct SelectBufs {
 
 // Candidate lists, the (self-resetting) control block and the status words for `batch` frames.
 int select_buffers(fd_ctx *c, int batch, int64_t cap, SelectBufs &sb);
-// The list fields of a candidate kernel's argument block: the lists and level-0 histogram of `sb`.
-template <typename A>
-void list_outputs(fd_ctx *c, A &a, int64_t cap, const SelectBufs &sb) {
-    a.list_resp = as<float>(c->list_resp);
-    a.list_idx = as<uint32_t>(c->list_idx);
-    a.list_cap = cap;
-    a.list_count = sb.list_count;
-    a.hist0 = sb.hist0;
+// The list fields of a candidate kernel's argument block (the key map goes into the same object, key_map):
+// the caller's arrays (fd_points_response), or the context's lists and the level-0 histogram of `sb`.
+inline void list_outputs(fdk::CandList &l, float *resp, uint32_t *idx, int64_t cap, uint32_t *count, uint32_t *hist0) {
+    l.resp = resp;
+    l.idx = idx;
+    l.cap = cap;
+    l.count = count;
+    l.hist0 = hist0;
+}
+inline void list_outputs(fd_ctx *c, fdk::CandList &l, int64_t cap, const SelectBufs &sb) {
+    list_outputs(l, as<float>(c->list_resp), as<uint32_t>(c->list_idx), cap, sb.list_count, sb.hist0);
 }
 // Scratch of k_select_reference for `batch` frames of lists of `cap` entries.
 int ref_buffers(fd_ctx *c, int batch, int rows, int cols, int64_t cap, fdk::RefSortArgs &r);

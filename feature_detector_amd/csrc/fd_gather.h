@@ -1,25 +1,13 @@
 // First-chunk gather of the per-frame selection (SelectGoodFeatures, feature_point_detector.cpp:54-88),
-// shared by k_gather (its own kernel, fd_select.hip) and the fused tail of the candidate kernels
-// (fd_points.hip, small batches): G workgroups of one frame each derive the frame's first level-0
-// chunk (the highest histogram bins holding <= kSelectChunk candidates) and append the 64-bit keys of
-// their slice of the candidate list to pre_keys[f]; k_select then starts from those keys instead of a
-// pass over the whole list by one workgroup.
+// for k_gather (fd_select.hip): G workgroups of one frame each derive the frame's
+// first level-0 chunk (the highest histogram bins holding <= `limit` candidates) and append the 64-bit
+// keys of their slice of the candidate list to the frame's key buffer; k_select then starts from those
+// keys instead of a pass over the whole list by one workgroup.
 #pragma once
 
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_emit.h"
 
 namespace fdk {
-
-// Selection key: the response through the frame's key map (order-preserving, injective on the
-// candidates' response range; see SelectArgs::key_base), then ~idx so that equal responses order by
-// ascending raster index (tie_idx_desc: idx, descending, SuperPoint's multimap walk order).
-__device__ __forceinline__ uint32_t sel_key32(float resp, uint32_t key_base, int key_lz) {
-    return (float_key(resp) - key_base) << key_lz;
-}
-__device__ __forceinline__ uint64_t sel_key64(float resp, uint32_t idx, uint32_t key_base, int key_lz, int tie_desc) {
-    return (static_cast<uint64_t>(sel_key32(resp, key_base, key_lz)) << 32) | static_cast<uint64_t>(tie_desc ? idx : ~idx);
-}
 
 constexpr int kGatherPerThread = 16;  // list responses per thread and round
 

@@ -1,7 +1,8 @@
-// Kernel argument blocks and host-side launchers (defined in fd_points.hip / fd_select.hip / fd_lsd.hip).
+// Kernel argument blocks and the host-side launchers of every kernel file (fd_*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace fdk {
@@ -44,6 +45,23 @@ struct FastOffsets {
     const uint8_t *run_lut;
 };
 
+// The selection's list format, as a candidate kernel's outputs: unordered per-frame lists (SoA) and the
+// level-0 key histogram. The producers write it through fd_emit.h; k_select, k_gather, k_wide_gather and
+// k_select_reference read it (SelectArgs names the same arrays).
+// Key map: 32-bit key = (float_key(response) - key_base) << key_lz; all candidates have responses >
+// min_valid_response, so key_base = float_key(min_valid_response) and key_lz spreads the possible response
+// range over the full 32 bits (finer level-0 bins). Level-0 bin = key >> 20 (fd_emit.h: level0_bin).
+struct CandList {
+    float *resp;      // [batch][cap]
+    uint32_t *idx;    // [batch][cap] raster index, row * cols + col
+    int64_t cap;      // entries per frame; candidates past it are counted, not stored
+    uint32_t *count;  // [batch]
+    uint32_t *hist0;  // [batch][kHistBins] or null
+    uint32_t key_base;
+    int key_lz;
+};
+static_assert(sizeof(CandList) == 48, "kernel-argument layout");
+
 struct PointsArgs {
     const uint8_t *frames;
     int batch, rows, cols;
@@ -54,14 +72,7 @@ struct PointsArgs {
     float thr;
     const uint32_t *mask;  // prior-feature bitmap [batch][rows][mask_wpr], bit = mask true; null = all ones
     int mask_wpr;
-    // detect mode: unordered per-frame lists (SoA) + level-0 key histogram
-    float *list_resp;
-    uint32_t *list_idx;
-    int64_t list_cap;
-    uint32_t *list_count;
-    uint32_t *hist0;  // [batch][kHistBins] or null
-    uint32_t key_base;  // level-0 bin = ((float_key(resp) - key_base) << key_lz) >> 20 (see SelectArgs)
-    int key_lz;
+    CandList list;  // detect mode
     // raster mode: per (frame, row, tile_x) segments
     int32_t *seg_cnt;
     Cand *seg;
@@ -84,12 +95,16 @@ struct PointsArgs {
     uint32_t *skipped;
     const uint32_t *redo_status;
 };
+static_assert(offsetof(PointsArgs, list) == 64 && offsetof(PointsArgs, seg_cnt) == 112 && sizeof(PointsArgs) == 208,
+              "kernel-argument layout");
 
 // Internal status bit (SelectArgs::status): the selection ran out of emitted keys of a frame whose
 // per-pixel pass skipped some (FAST emission cut); the frame is detected and selected again in the same
 // call (redo pass), which clears the bit.
 constexpr uint32_t kFrameRedo = 0x00000100u;
 
+// (Its list fields are not a CandList: they sit in another order, and the order is the measured one -- a
+// reordered block cost the headline 0.16 us and more SGPR spills, profiles/r07_select_chain_ab.txt.)
 struct SelectArgs {
     const float *list_resp;
     const uint32_t *list_idx;
@@ -114,10 +129,7 @@ struct SelectArgs {
     // [batch] candidate count of the frame (kept for a tie resolution after the list count is reset)
     uint32_t *status;
     uint32_t *cand_n;
-    // key map: 32-bit key = (float_key(response) - key_base) << key_lz; all candidates have
-    // responses > min_valid_response, so key_base = float_key(min_valid_response) and key_lz spreads
-    // the possible response range over the full 32 bits (finer level-0 bins).
-    uint32_t key_base;
+    uint32_t key_base;  // the key map (CandList)
     int key_lz;
     int tie_idx_desc;  // equal responses by descending raster index (SuperPoint) instead of ascending
     int value_flag;    // pre_count bit 31 set by the candidate kernel -> guard flag 0x40000000 (out of key range)
@@ -200,13 +212,7 @@ struct CandInArgs {
     const int64_t *counts;  // [batch] (device)
     int64_t stride;
     int batch, rows, cols;
-    float *list_resp;
-    uint32_t *list_idx;
-    int64_t list_cap;
-    uint32_t *list_count;
-    uint32_t *hist0;
-    uint32_t key_base;
-    int key_lz;
+    CandList list;
     uint32_t *bad;  // [batch] bit 31: a candidate outside the frame, a NaN response or a bad count
     // keypoint-list models (fd_nn_select_list): (u, v) int64 pairs instead of x / y, and candidates
     // within `border` of the frame edge dropped (CreateMask's zero rows/cols). The list is then
@@ -214,6 +220,8 @@ struct CandInArgs {
     const int64_t *kp;
     int border;  // < 0: keep push order at list position i (fd_points_select)
 };
+static_assert(offsetof(CandInArgs, list) == 56 && offsetof(CandInArgs, bad) == 104 && sizeof(CandInArgs) == 128,
+              "kernel-argument layout");
 
 // fd_nn_select_list: descriptor rows of the selected keypoints. Per (frame f, feature k), the
 // candidate at that pixel visited first by the selection (highest score, then highest index).
@@ -308,16 +316,12 @@ struct HeatArgs {
     int border;            // kInvalidBoundary: rows/cols within it are masked out
     const uint32_t *mask;  // prior-feature bitmap (null = none)
     int mask_wpr;
-    float *list_resp;
-    uint32_t *list_idx;
-    int64_t list_cap;
-    uint32_t *list_count;
-    uint32_t *hist0;
-    uint32_t key_base;
-    int key_lz;
+    CandList list;
     float vmax;           // values above it set bit 31 of value_flag[f] (the key map assumes <= vmax)
     uint32_t *value_flag;  // [batch], the selection control block's pre_count words (gather disabled)
 };
+static_assert(offsetof(HeatArgs, list) == 48 && offsetof(HeatArgs, vmax) == 96 && sizeof(HeatArgs) == 112,
+              "kernel-argument layout");
 
 // Bilinear descriptor sampling from the 1/8-resolution descriptor map.
 struct NnDescArgs {

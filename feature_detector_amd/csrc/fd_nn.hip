@@ -10,13 +10,13 @@
 //       raster index descending (equal keys are inserted at the upper bound of their range)
 //   ExtractDescriptorsForSelectedFeatures (:163-193) -> k_nn_desc: bilinear sampling of the
 //       1/8-resolution descriptor map, the reference's float sequence (-ffp-contract=off)
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_emit.h"
 
 namespace fdk {
 namespace {
 
 constexpr int kHeatBlock = 256;
+static_assert(kHeatBlock == kPixWg, "hist_clear / hist_flush");
 constexpr int kHeatRounds = 64;  // pixels per thread: a workgroup covers 16,384 consecutive pixels
 constexpr int kHeatUnroll = 4;   // loads in flight per thread
 
@@ -28,31 +28,19 @@ constexpr int kHeatStage = 1024;  // candidates a wave stages in LDS before appe
 // wave stages its candidates in LDS and appends them with one atomic per flush, and the workgroup's
 // histogram is accumulated in LDS and flushed once (one atomic per non-empty bin).
 __global__ __launch_bounds__(kHeatBlock) void k_heat_candidates(HeatArgs a) {
-    __shared__ uint32_t hist[kHistBins];
+    __shared__ alignas(16) uint32_t hist[kHistBins];
     __shared__ float st_r[kHeatBlock / kWave][kHeatStage];
     __shared__ uint32_t st_i[kHeatBlock / kWave][kHeatStage];
     const int f = blockIdx.y;
-    const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-    for (int b = tid; b < kHistBins; b += kHeatBlock) hist[b] = 0;
-    __syncthreads();
+    const int tid = threadIdx.x, w = tid >> 6;
+    hist_clear(hist);
     const int64_t npx = static_cast<int64_t>(a.rows) * a.cols;
     const float *h = a.heat + static_cast<int64_t>(f) * npx;
     const int64_t blk0 = static_cast<int64_t>(blockIdx.x) * (kHeatRounds * kHeatBlock);
     const uint32_t *fmask = a.mask ? a.mask + static_cast<int64_t>(f) * a.rows * a.mask_wpr : nullptr;
-    float *dr = a.list_resp + static_cast<int64_t>(f) * a.list_cap;
-    uint32_t *di = a.list_idx + static_cast<int64_t>(f) * a.list_cap;
     int staged = 0;  // wave-uniform
-    auto flush = [&]() {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&a.list_count[f], static_cast<uint32_t>(staged));
-        base = __builtin_amdgcn_readfirstlane(base);
-        for (int k = lane; k < staged; k += kWave) {
-            const uint64_t pos = static_cast<uint64_t>(base) + k;
-            if (pos < static_cast<uint64_t>(a.list_cap)) {
-                dr[pos] = st_r[w][k];
-                di[pos] = st_i[w][k];
-            }
-        }
+    auto flush = [&]() {  // (the histogram is counted as the candidates are staged)
+        wave_append(a.list, f, st_r[w], st_i[w], staged, nullptr);
         staged = 0;
     };
     bool over = false;
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(kHeatBlock) void k_heat_candidates(HeatArgs a) {
                 st_r[w][k] = v[j];
                 st_i[w][k] = static_cast<uint32_t>(p);
                 over = over || v[j] > a.vmax;
-                atomicAdd(&hist[((float_key(v[j]) - a.key_base) << a.key_lz) >> 20], 1u);
+                atomicAdd(&hist[level0_bin(v[j], a.list.key_base, a.list.key_lz)], 1u);
             }
             staged += popc64(m);
             if (staged > kHeatStage - kWave) flush();
@@ -89,11 +77,7 @@ __global__ __launch_bounds__(kHeatBlock) void k_heat_candidates(HeatArgs a) {
     }
     if (staged) flush();
     if (__syncthreads_or(over) && tid == 0) atomicOr(&a.value_flag[f], 0x80000000u);  // outside the key map
-    uint32_t *gh = a.hist0 + static_cast<int64_t>(f) * kHistBins;
-    for (int b = tid; b < kHistBins; b += kHeatBlock) {
-        const uint32_t n = hist[b];
-        if (n) atomicAdd(&gh[b], n);
-    }
+    hist_flush(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
 }
 
 // One wave per (frame, feature slot); lanes over descriptor channels.

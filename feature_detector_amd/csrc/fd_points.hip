@@ -41,22 +41,7 @@ __device__ __forceinline__ void sink_flush(Sink &sk, const PointsArgs &a, int f)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint32_t base = 0;
-    if (lane_id() == 0) base = atomicAdd(&a.list_count[f], static_cast<uint32_t>(sk.n));
-    base = __builtin_amdgcn_readfirstlane(base);
-    float *dr = a.list_resp + static_cast<int64_t>(f) * a.list_cap;
-    uint32_t *di = a.list_idx + static_cast<int64_t>(f) * a.list_cap;
-    // The level-0 histogram is counted here, once per staged candidate, rather than in the per-row
-    // emit path where every (row, column-of-4) slot would pay for the key computation.
-    for (int i = lane_id(); i < sk.n; i += kWave) {
-        const float r = sk.resp[i];
-        if (sk.hist) atomicAdd(&sk.hist[((float_key(r) - a.key_base) << a.key_lz) >> 20], 1u);
-        const int64_t pos = static_cast<int64_t>(base) + i;
-        if (pos < a.list_cap) {
-            dr[pos] = r;
-            di[pos] = sk.idx[i];
-        }
-    }
+    wave_append(a.list, f, sk.resp, sk.idx, sk.n, sk.hist);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -65,6 +50,19 @@ __device__ __forceinline__ void sink_flush(Sink &sk, const PointsArgs &a, int f)
     __builtin_amdgcn_s_waitcnt(0x0F70);
     sk.n = 0;
 }
+
+// The wave's Sink as a source of the sorted-segment flush (seg_list_flush, fd_emit.h).
+struct SinkSource {
+    Sink &sk;
+    int &n = sk.n;
+    __device__ __forceinline__ uint32_t wave_total() const { return static_cast<uint32_t>(n); }
+    __device__ __forceinline__ bool counted() const { return sk.ehist != nullptr; }  // (FAST counted its candidates at emit time)
+    template <class F>
+    __device__ __forceinline__ void visit(F &&fn) const {
+        for (int i = lane_id(); i < n; i += kWave) fn(sk.resp[i], sk.idx[i]);
+    }
+    __device__ __forceinline__ void flush(const PointsArgs &a, int f) { sink_flush(sk, a, f); }
+};
 
 // Emit up to 4 candidates of this lane (columns c0..c0+3 of row `row`), preserving column order.
 // The lane's slot is the count of candidates in lower lanes: one v_mbcnt pair per column ballot.
@@ -97,7 +95,7 @@ __device__ __forceinline__ void emit_row(Sink &sk, const PointsArgs &a, int f, i
 #pragma unroll
         for (int m = 0; m < 4; ++m)
             if (fl[m]) {
-                if (sk.ehist) atomicAdd(&sk.ehist[((float_key(v[m]) - a.key_base) << a.key_lz) >> 20], 1u);
+                if (sk.ehist) atomicAdd(&sk.ehist[level0_bin(v[m], a.list.key_base, a.list.key_lz)], 1u);
                 sk.resp[pos] = v[m];
                 sk.idx[pos] = id0 + m;
                 ++pos;
@@ -114,84 +112,13 @@ __device__ __forceinline__ uint32_t mask_bits4(const PointsArgs &a, int f, int r
 
 // Workgroup-shared staging + level-0 histogram (detect mode).
 template <int S>
-struct alignas(16) DetectLdsT {  // (16-byte aligned: hist is cleared and read as uint4, fd_corner_common.h)
+struct alignas(16) DetectLdsT {  // (16-byte aligned: hist is cleared and read as uint4, fd_emit.h)
     float resp[4][S];
     uint32_t idx[4][S];
     uint32_t hist[kHistBins];
 };
 using DetectLds = DetectLdsT<kStage>;
 static_assert(sizeof(DetectLds) % 16 == 0 && offsetof(DetectLds, hist) % 16 == 0, "uint4 histogram access");
-
-// Sorted-segment flush (PointsArgs::segdesc; small launches whose tiles never overflow the staging):
-// the workgroup's candidates, all still staged in LDS, go to the frame's list as one contiguous
-// segment ordered by level-0 bin, descending (a counting sort on the workgroup's LDS histogram), and
-// the segment is described in segdesc[f][g]. k_select then reads only each segment's prefix at or
-// above its first-chunk cut (a few entries per workgroup) instead of scanning the whole list.
-template <class LdsT>
-__device__ __forceinline__ void seg_flush(Sink &sk, const PointsArgs &a, int f, bool active, LdsT &L,
-                                          uint32_t (&wtot)[4], uint32_t &wg_base) {
-    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
-    const int n = active ? sk.n : 0;
-    if (lane == 0) wtot[wv] = static_cast<uint32_t>(n);
-    __syncthreads();
-    if (*sk.ovf) {  // part of the workgroup's list is already out unsorted: plain flush (frame marked)
-        if (active) sink_flush(sk, a, f);
-        hist_flush(L.hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);
-        return;
-    }
-    // The segment's place in the list: one returning atomic, issued before the histogram work so that
-    // its round trip overlaps the counting sort's scan (thread 0 waits for it only at its LDS store).
-    uint32_t seg_base_early = 0;
-    const uint32_t seg_total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    if (tid == 0 && seg_total) seg_base_early = atomicAdd(&a.list_count[f], seg_total);
-    auto bin_of = [&](float r) { return ((float_key(r) - a.key_base) << a.key_lz) >> 20; };
-    if (!sk.ehist)  // (FAST counted its candidates at emit time)
-        for (int i = lane; i < n; i += kWave) atomicAdd(&L.hist[bin_of(sk.resp[i])], 1u);
-    hist_flush(L.hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);  // (leads with a barrier)
-    __syncthreads();
-    // in place: hist[b] = entries of bins above b (exclusive scan in descending bin order)
-    constexpr int kPer = kHistBins / 256;
-    uint32_t v[kPer], sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) sum += (v[k] = L.hist[kHistBins - 1 - (tid * kPer + k)]);
-    const uint32_t incl = wave_incl_add(sum);
-    if (lane == kWave - 1) wtot[wv] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum, total = 0;
-    for (int q = 0; q < 4; ++q) {
-        run += q < wv ? wtot[q] : 0u;
-        total += wtot[q];
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        L.hist[kHistBins - 1 - (tid * kPer + k)] = run;
-        run += v[k];
-    }
-    if (tid == 0) {
-        wg_base = seg_base_early;
-        const int g = logical_block() % a.blocks_per_frame;
-        a.segdesc[static_cast<int64_t>(f) * a.blocks_per_frame + g] = make_uint2(wg_base, total);
-    }
-    __syncthreads();
-    float *dr = a.list_resp + static_cast<int64_t>(f) * a.list_cap;
-    uint32_t *di = a.list_idx + static_cast<int64_t>(f) * a.list_cap;
-    const int64_t base = wg_base;
-    const int g = logical_block() % a.blocks_per_frame;
-    uint64_t *head = a.seghead + (static_cast<int64_t>(f) * a.blocks_per_frame + g) * kSegHead;
-    for (int i = lane; i < n; i += kWave) {
-        const float r = sk.resp[i];
-        const uint32_t k32 = (float_key(r) - a.key_base) << a.key_lz;
-        const uint32_t lp = atomicAdd(&L.hist[k32 >> 20], 1u);
-        const int64_t pos = base + lp;
-        if (pos < a.list_cap) {
-            dr[pos] = r;
-            di[pos] = sk.idx[i];
-        }
-        // the segment's head as selection keys (k32, ~idx): k_select's first read, no list hop
-        if (lp < static_cast<uint32_t>(kSegHead)) head[lp] = (static_cast<uint64_t>(k32) << 32) | static_cast<uint64_t>(~sk.idx[i]);
-    }
-    sk.n = 0;
-}
 
 template <int KIND, bool RASTER, bool MASKED, bool ALIGNED, bool G1>
 __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, int tx, Sink &sk);
@@ -210,19 +137,20 @@ __global__ __launch_bounds__(256) void k_corner(PointsArgs a) {
     Sink sk{nullptr, nullptr, nullptr, 0, &seg_ovf};
     if constexpr (!RASTER) {
         const int wv = threadIdx.x >> 6;
-        sk = Sink{lds_all[0].resp[wv], lds_all[0].idx[wv], a.hist0 ? lds_all[0].hist : nullptr, 0, &seg_ovf};
+        sk = Sink{lds_all[0].resp[wv], lds_all[0].idx[wv], a.list.hist0 ? lds_all[0].hist : nullptr, 0, &seg_ovf};
         if (threadIdx.x == 0) seg_ovf = 0;
-        if (a.hist0) hist_clear(lds_all[0].hist);
+        if (a.list.hist0) hist_clear(lds_all[0].hist);
         else __syncthreads();
     }
     if (active) corner_tile<KIND, RASTER, MASKED, ALIGNED, G1>(a, f, ty, tx, sk);
     if constexpr (!RASTER) {
         if (a.segdesc) {
             __shared__ uint32_t seg_wtot[4], seg_base;
-            seg_flush(sk, a, f, active, lds_all[0], seg_wtot, seg_base);
+            SinkSource src{sk};
+            seg_list_flush(src, a, f, logical_block() % a.blocks_per_frame, active, lds_all[0].hist, &seg_ovf, seg_wtot, seg_base);
         } else {
             if (active) sink_flush(sk, a, f);
-            if (a.hist0) hist_flush(lds_all[0].hist, a.hist0 + static_cast<int64_t>(f) * kHistBins);
+            if (a.list.hist0) hist_flush(lds_all[0].hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
         }
     }
 }
@@ -449,12 +377,12 @@ __global__ __launch_bounds__(256) void k_fast(PointsArgs a, FastOffsets off) {
         Sink sk{nullptr, nullptr, nullptr, 0, &seg_ovf};
         if constexpr (!RASTER) {
             const int wv = threadIdx.x >> 6;
-            sk = Sink{lds_all[0].resp[wv], lds_all[0].idx[wv], a.hist0 ? lds_all[0].hist : nullptr, 0, &seg_ovf};
+            sk = Sink{lds_all[0].resp[wv], lds_all[0].idx[wv], a.list.hist0 ? lds_all[0].hist : nullptr, 0, &seg_ovf};
             sk.ehist = sk.hist;  // FAST: histogram counted at emit time (measured faster than at flush)
             sk.hist = nullptr;
             sk.cap = kStageFast;
             if (threadIdx.x == 0) seg_ovf = 0;
-            if (a.hist0) hist_clear(lds_all[0].hist);  // (includes the barrier for the segment table)
+            if (a.list.hist0) hist_clear(lds_all[0].hist);  // (includes the barrier for the segment table)
             else __syncthreads();
         } else {
             __syncthreads();
@@ -463,10 +391,11 @@ __global__ __launch_bounds__(256) void k_fast(PointsArgs a, FastOffsets off) {
         if (a.skipped && skip && lane_id() == 0) atomicAdd(&a.skipped[fr], skip);
         if constexpr (!RASTER) {
             if (a.segdesc) {
-                seg_flush(sk, a, fr, active, lds_all[0], seg_wtot, seg_base);
+                SinkSource src{sk};
+                seg_list_flush(src, a, fr, logical_block() % a.blocks_per_frame, active, lds_all[0].hist, &seg_ovf, seg_wtot, seg_base);
             } else {
                 if (active) sink_flush(sk, a, fr);
-                if (a.hist0) hist_flush(lds_all[0].hist, a.hist0 + static_cast<int64_t>(fr) * kHistBins);
+                if (a.list.hist0) hist_flush(lds_all[0].hist, a.list.hist0 + static_cast<int64_t>(fr) * kHistBins);
             }
         }
     };

@@ -245,7 +245,7 @@ int fd_points_detect(fd_ctx *c, int kind, const uint8_t *frames, int frames_on_d
     if ((rc = detect_workspace(c, kind, batch, rows, cols, pi.total, cap, sb))) return rc;
 
     fdk::PointsArgs a = points_args(dframes, batch, rows, cols, g, px, thr);
-    list_outputs(c, a, cap, sb);
+    list_outputs(c, a.list, cap, sb);
     a.mask = pi.mask;
     a.mask_wpr = pi.wpr;
     if (use_seg_lists(g, rows, cols)) {
@@ -257,7 +257,7 @@ int fd_points_detect(fd_ctx *c, int kind, const uint8_t *frames, int frames_on_d
     if (kind == FD_FAST && !g.empty) {
         if ((rc = build_offsets(c, n_off, thr))) return rc;
     }
-    key_map(kind, thr, kind == FD_FAST && !g.empty ? &c->off : nullptr, n_off, a.key_base, a.key_lz);
+    key_map(kind, thr, kind == FD_FAST && !g.empty ? &c->off : nullptr, n_off, a.list.key_base, a.list.key_lz);
     // FAST's emission cut (PointsArgs::emit_cut): only in the raster tie order (the
     // reference order's emulation needs every candidate in push order).
     const bool fast_cut = kind == FD_FAST && !g.empty && c->tie_order == FD_TIES_RASTER;
@@ -280,7 +280,7 @@ int fd_points_detect(fd_ctx *c, int kind, const uint8_t *frames, int frames_on_d
         }
     }
 
-    SelectCall sc(batch, rows, cols, opts->min_feature_distance, need, cap, a.key_base, a.key_lz);
+    SelectCall sc(batch, rows, cols, opts->min_feature_distance, need, cap, a.list.key_base, a.list.key_lz);
     sc.segdesc = a.segdesc;
     sc.seghead = a.seghead;
     sc.nseg = g.blocks_per_frame;
@@ -356,16 +356,16 @@ int fd_points_select(fd_ctx *c, int batch, int rows, int cols, const fd_point_op
     a.batch = batch;
     a.rows = rows;
     a.cols = cols;
-    list_outputs(c, a, cap, sb);
+    list_outputs(c, a.list, cap, sb);
     // any float: keys from float_key(-inf) - 1 (never 0) to float_key(+inf), the whole 32-bit range
-    a.key_base = host_float_key(-std::numeric_limits<float>::infinity()) - 1u;
-    a.key_lz = 0;
+    a.list.key_base = host_float_key(-std::numeric_limits<float>::infinity()) - 1u;
+    a.list.key_lz = 0;
     a.bad = sb.pre_count;
     a.border = -1;  // list position = push position
     c->sel_dirty = true;  // until k_select is enqueued: it resets the control block
     FD_HIP_TRY(c, fdk::launch_cand_lists(a, max_n, c->stream));
     if (!cands_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller's host arrays were the sources
-    SelectCall sc(batch, rows, cols, opts->min_feature_distance, need, cap, a.key_base, a.key_lz);
+    SelectCall sc(batch, rows, cols, opts->min_feature_distance, need, cap, a.list.key_base, a.list.key_lz);
     sc.value_flag = true;
     sc.push_order = true;
     sc.dup_keys = true;
@@ -388,10 +388,7 @@ static int points_response(fd_ctx *c, int kind, const uint8_t *frames, int batch
     if (reset_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(uint32_t) * batch, c->stream));
     if (g.empty) return FD_OK;
     fdk::PointsArgs a = points_args(frames, batch, rows, cols, g, px, opts->min_valid_response);
-    a.list_resp = out_resp;
-    a.list_idx = out_idx;
-    a.list_cap = cand_cap;
-    a.list_count = out_counts;
+    list_outputs(a.list, out_resp, out_idx, cand_cap, out_counts, nullptr);  // (no selection: no histogram, no key map)
     if (kind == FD_FAST) {
         rc = build_offsets(c, static_cast<int64_t>(rows - 6) * (cols - 6), opts->min_valid_response);
         if (rc) return rc;

@@ -257,21 +257,21 @@ int fd_nn_select(fd_ctx *c, const float *heatmap, int heatmap_on_device, int bat
     h.border = opts->invalid_boundary;
     h.mask = pi.mask;
     h.mask_wpr = pi.wpr;
-    list_outputs(c, h, cap, sb);
+    list_outputs(c, h.list, cap, sb);
     // responses in (thr, max_response] (probabilities: max 1) or (thr, +inf]
-    key_map(FD_HARRIS, opts->min_response, nullptr, 0, h.key_base, h.key_lz);
+    key_map(FD_HARRIS, opts->min_response, nullptr, 0, h.list.key_base, h.list.key_lz);
     h.vmax = std::numeric_limits<float>::infinity();
     const bool bounded = std::isfinite(opts->max_response) && opts->max_response > opts->min_response;
     if (bounded) {
         h.vmax = opts->max_response;
         const uint32_t kmax = host_float_key(opts->max_response) + 1u;
-        h.key_lz = kmax > h.key_base ? __builtin_clz(kmax - h.key_base) : 0;
+        h.list.key_lz = kmax > h.list.key_base ? __builtin_clz(kmax - h.list.key_base) : 0;
     }
     h.value_flag = sb.pre_count;
     c->sel_dirty = true;  // until k_select is enqueued: it resets the control block
     FD_HIP_TRY(c, fdk::launch_heat_candidates(h, c->stream));
     SelectCall sc(batch, rows, cols, opts->min_feature_distance, static_cast<uint32_t>(opts->max_features), cap,
-                  h.key_base, h.key_lz);
+                  h.list.key_base, h.list.key_lz);
     sc.tie_idx_desc = 1;
     sc.value_flag = true;
     return run_select(c, sc, pi, sb, out_xy, out_stride, out_counts, outputs_on_device, heatmap_on_device);
@@ -332,14 +332,14 @@ int fd_nn_select_list(fd_ctx *c, const int64_t *keypoints, const float *scores, 
     a.rows = rows;
     a.cols = cols;
     a.border = opts->invalid_boundary;
-    list_outputs(c, a, lcap, sb);
-    a.key_base = host_float_key(-std::numeric_limits<float>::infinity()) - 1u;
-    a.key_lz = 0;
+    list_outputs(c, a.list, lcap, sb);
+    a.list.key_base = host_float_key(-std::numeric_limits<float>::infinity()) - 1u;
+    a.list.key_lz = 0;
     a.bad = sb.pre_count;
     c->sel_dirty = true;  // until k_select is enqueued: it resets the control block
     FD_HIP_TRY(c, fdk::launch_cand_lists(a, cap, c->stream));
     SelectCall sc(batch, rows, cols, opts->min_feature_distance, static_cast<uint32_t>(opts->max_features), lcap,
-                  a.key_base, a.key_lz);
+                  a.list.key_base, a.list.key_lz);
     sc.tie_idx_desc = 1;  // equal scores: raster index descending (ArgSort walked from the back; unpinned)
     sc.dup_keys = true;
     sc.grid_at_d0 = true;

@@ -1230,7 +1230,7 @@ __device__ __forceinline__ void select_frame(const SelectArgs &a, const int f, S
             const uint32_t target = max(kCutMul * vis, vis + kCutAdd);
             const int x0 = first_le(suf0, 0, kHistBins, 0u, target - 1u);  // (all threads: barriers)
             if (x0 > 0) {
-                const uint32_t fk = a.key_base + ((static_cast<uint32_t>(x0 - 1) << 20) >> a.key_lz);
+                const uint32_t fk = level0_floor_key(static_cast<uint32_t>(x0 - 1), a.key_base, a.key_lz);
                 prop = (fk & 0x80000000u) ? (fk & 0x7FFFFFFFu) : 0u;  // the bin's lowest response (a positive float)
             } else {
                 const float cur = __uint_as_float(*a.cut_cur);

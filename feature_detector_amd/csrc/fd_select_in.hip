@@ -9,27 +9,25 @@
 // HBM-bound: 12 B read + 8 B written per candidate. The keypoint-list models' post-processing
 // (fd_nn_select_list) uses the same kernel on (u, v) int64 keypoints plus k_nn_pick for the
 // descriptor rows.
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_emit.h"
 
 namespace fdk {
 namespace {
 
 constexpr int kInBlock = 256;
+static_assert(kInBlock == kPixWg, "hist_clear / hist_flush");
 
 __global__ __launch_bounds__(kInBlock) void k_cand_lists(CandInArgs a) {
-    __shared__ uint32_t hist[kHistBins];
+    __shared__ alignas(16) uint32_t hist[kHistBins];
     const int f = blockIdx.y, tid = threadIdx.x;
-    for (int b = tid; b < kHistBins; b += kInBlock) hist[b] = 0;
-    __syncthreads();
+    hist_clear(hist);
     const int64_t want = a.counts[f];
-    const bool count_ok = want >= 0 && want <= a.stride && want <= a.list_cap;
+    const bool count_ok = want >= 0 && want <= a.stride && want <= a.list.cap;
     const int64_t n = count_ok ? want : 0;
     const float *r = a.resp + static_cast<int64_t>(f) * a.stride;
     const int32_t *xs = a.x + static_cast<int64_t>(f) * a.stride;
     const int32_t *ys = a.y + static_cast<int64_t>(f) * a.stride;
-    float *dr = a.list_resp + static_cast<int64_t>(f) * a.list_cap;
-    uint32_t *di = a.list_idx + static_cast<int64_t>(f) * a.list_cap;
+    const ListFrame d = list_frame(a.list, f);
     bool bad = false;
     const int64_t step = static_cast<int64_t>(gridDim.x) * kInBlock;
     const bool keep_order = a.border < 0;
@@ -54,29 +52,25 @@ __global__ __launch_bounds__(kInBlock) void k_cand_lists(CandInArgs a) {
         if (!ok) v = 0.0f;
         const uint32_t idx = ok ? static_cast<uint32_t>(y) * static_cast<uint32_t>(a.cols) + static_cast<uint32_t>(x) : 0u;
         if (keep_order) {
-            dr[i] = v;
-            di[i] = idx;
+            d.resp[i] = v;
+            d.idx[i] = idx;
         } else {
             // CreateMask (nn_feature_point_detector.cpp:61-67): a candidate in the border is never
             // selected and never draws a box, so it is left out of the list
             if (!ok || y < a.border || y >= a.rows - a.border || x < a.border || x >= a.cols - a.border) continue;
-            const uint32_t pos = atomicAdd(&a.list_count[f], 1u);
-            if (pos >= a.list_cap) continue;  // (cannot happen: list_cap >= count)
-            dr[pos] = v;
-            di[pos] = idx;
+            const uint32_t pos = atomicAdd(&a.list.count[f], 1u);
+            if (pos >= d.cap) continue;  // (cannot happen: cap >= count)
+            d.resp[pos] = v;
+            d.idx[pos] = idx;
         }
-        atomicAdd(&hist[((float_key(v) - a.key_base) << a.key_lz) >> 20], 1u);
+        atomicAdd(&hist[level0_bin(v, a.list.key_base, a.list.key_lz)], 1u);
     }
     if (__syncthreads_or(bad) && tid == 0) atomicOr(&a.bad[f], 0x80000000u);
     if (blockIdx.x == 0 && tid == 0) {
-        if (keep_order) a.list_count[f] = static_cast<uint32_t>(n);
+        if (keep_order) a.list.count[f] = static_cast<uint32_t>(n);
         if (!count_ok) atomicOr(&a.bad[f], 0x80000000u);
     }
-    uint32_t *gh = a.hist0 + static_cast<int64_t>(f) * kHistBins;
-    for (int b = tid; b < kHistBins; b += kInBlock) {
-        const uint32_t c = hist[b];
-        if (c) atomicAdd(&gh[b], c);
-    }
+    hist_flush(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
 }
 
 // One wave per (frame, selected feature): the candidate at the feature's pixel that the selection

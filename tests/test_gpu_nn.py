@@ -116,6 +116,29 @@ def test_nn_select_key_range(sp, oracle):
     assert np.array_equal(cd, ca) and np.array_equal(d, a)
 
 
+def test_nn_select_histogram_edge_bins(sp, oracle):
+    """k_heat_candidates' level-0 histogram at its edges: a candidate count that is no multiple of the
+    workgroup's 256 threads, candidates in bin 0 (the first float above the threshold) and in bin 4095 (the
+    declared maximum: threshold bits 0x3F000000 and maximum bits 0x3F7FFFFE make the key map shift the range
+    (thr, max] onto all 32 key bits), every candidate wanted, so the selection walks all bins down to bin 0."""
+    rng = np.random.default_rng(5)
+    thr, vmax = np.float32(0.5), np.array([0x3F7FFFFE], np.uint32).view(np.float32)[0]
+    heat = rng.random((2, 50, 70)).astype(np.float32)
+    heat[heat > vmax] = vmax
+    heat[0, 10:14, 10:40:3] = vmax                        # bin 4095, ties
+    heat[0, 20:24, 11:41:3] = np.nextafter(thr, np.float32(1))  # bin 0, ties
+    heat[1, 5:45:7, 5:65:5] = vmax
+    heat[1, 6:46:7, 6:66:5] = np.nextafter(thr, np.float32(1))
+    n_cand = [int((heat[b, 3:-3, 3:-3] > thr).sum()) for b in range(2)]
+    assert all(n % 256 for n in n_cand) and min(n_cand) > 256, n_cand
+    o = sp.Options(kInvalidBoundary=3, kMinFeatureDistance=0, kMaxNumberOfDetectedFeatures=5000, kMinResponse=float(thr))
+    xy, cnt = sp.nn_select(heat, o, max_response=float(vmax))
+    for b in range(2):
+        exp = oracle.nn_select(heat[b], 3, 0, 5000, float(thr))
+        assert len(exp) == n_cand[b]
+        assert np.array_equal(features(xy, cnt, b), exp), b
+
+
 def test_nn_descriptors_channels_last_in_place(sp, oracle):
     """A channels-last device map (the network's layout) is read in place (FD_MAP_NHWC) and gives the
     same values as the reference's per-channel planes."""

@@ -145,6 +145,26 @@ def test_full_float_range(fd, oracle):
         assert np.array_equal(res.features(0), oracle.select(vals, x, y, 480, 640, 3, 400, sort_mode=sm))
 
 
+def test_histogram_edge_bins(fd, oracle):
+    """k_cand_lists' level-0 histogram at its edges: a candidate count that is no multiple of the workgroup's
+    256 threads, candidates in the lowest and the highest bin its key map reaches (-inf: bin 0; +inf: bin 4080
+    -- the map covers every float, and bins 4081..4095 would be NaN patterns, which the call refuses), every
+    candidate wanted (distinct pixels, distance 0), so the selection walks all bins down to bin 0."""
+    rng = np.random.default_rng(9)
+    n = 5003
+    vals = (rng.standard_normal(n) * 1e3).astype(np.float32)
+    vals[rng.choice(n, 40, replace=False)] = np.inf
+    vals[rng.choice(n, 40, replace=False)] = -np.inf
+    assert n % 256 and (vals == np.inf).any() and (vals == -np.inf).any()
+    px = rng.choice(480 * 640, n, replace=False)
+    x, y = (px % 640).astype(np.int32), (px // 640).astype(np.int32)
+    for ties, sm in (("reference", 0), ("raster", 1)):
+        res = fd.select_points([(vals, x, y)], 480, 640, n, 0, ties=ties)
+        exp = oracle.select(vals, x, y, 480, 640, 0, n, sort_mode=sm)
+        assert len(exp) == n
+        assert np.array_equal(res.features(0), exp)
+
+
 def test_invalid_candidates_refused(fd):
     import feature_detector_amd._lib as L
 
