@@ -264,7 +264,8 @@ def conv1_bias_relu(x, weight, bias, out=None, ctx: Context | None = None):
     """fd_nn_conv3x3_c1: the encoder's first layer (1 input channel, 3x3, stride 1, padding 1) with its bias
     and ReLU in one pass: x [N, 1, H, W] fp16 on the device -> [N, C, H, W] fp16 channels-last. The 9
     products are summed in float and rounded to half, then the bias is added in float and rounded (as the
-    bias-free convolution followed by bias_relu); within fp16 rounding of PyTorch's convolution + ReLU."""
+    bias-free convolution followed by bias_relu); within fp16 rounding of PyTorch's convolution + ReLU.
+    W <= 4096 (the kernel's row staging); a wider frame is refused."""
     import torch
 
     if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.shape[1] == 1
@@ -444,8 +445,9 @@ def build_net(seed: int = 0, head_gain: float = 100.0, nms: bool = False, top_k:
             three or four elementwise passes over the activation); other inputs take the torch modules."""
             if x.dtype == torch.float16 and x.is_cuda and conv.in_channels == 1 and conv.kernel_size == (3, 3) \
                     and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.out_channels in (8, 16, 32, 64, 128, 256) \
-                    and x.dim() == 4 and x.shape[1] == 1 and not pool:
+                    and x.dim() == 4 and x.shape[1] == 1 and x.shape[3] <= 4096 and not pool:
                 # first layer: write-bound (9 MACs per output), one pass instead of convolution + bias pass
+                # (fd_nn_conv3x3_c1 stages rows of up to 4096 pixels; wider frames take the branches below)
                 return conv1_bias_relu(x.contiguous(), conv.weight, conv.bias)
             if x.dtype == torch.float16 and x.is_cuda and conv.in_channels == 64 and conv.out_channels % 64 == 0 \
                     and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) \
