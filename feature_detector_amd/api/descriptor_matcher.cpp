@@ -1,6 +1,6 @@
 // BriefMatcher over libfdhip.so (fd_brief_match): an MI355X extension, the reference has no matcher.
 // One call matches every query descriptor against every train descriptor in one kernel launch (two with
-// the cross-check).
+// the cross-check). NNDescriptorMatcher: the same over fd_nn_match for float descriptors (squared L2).
 #include "feature_detector/descriptor_matcher.h"
 
 #include <cstdio>
@@ -84,6 +84,65 @@ bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<
     }
     if (distance)
         for (size_t i = 0; i < query.size(); ++i) (*distance)[i] = dist[2 * i];
+    return true;
+}
+
+NNDescriptorMatcher::~NNDescriptorMatcher() {
+    if (ctx_) fd_ctx_destroy(ctx_);
+}
+
+void NNDescriptorMatcher::set_device(int device) {
+    if (ctx_ && device != device_) {
+        fd_ctx_destroy(ctx_);
+        ctx_ = nullptr;
+    }
+    device_ = device;
+}
+
+fd_ctx *NNDescriptorMatcher::Context() {
+    if (!ctx_) {
+        int dev = device_;
+        if (dev < 0) {
+            const char *e = std::getenv("FD_DEVICE");
+            dev = e ? std::atoi(e) : 0;
+        }
+        if (fd_ctx_create(dev, &ctx_) != FD_OK) {
+            ctx_ = nullptr;
+            Fail("fd_ctx_create failed (no MI355X visible?)");
+        }
+    }
+    return ctx_;
+}
+
+bool NNDescriptorMatcher::Fail(const std::string &what) {
+    error_ = what;
+    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
+    return false;
+}
+
+bool NNDescriptorMatcher::Match(const float *query, int32_t n_query, const float *train, int32_t n_train, int32_t dim,
+                                std::vector<int32_t> &train_index, std::vector<float> *distance,
+                                const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    const size_t nq = n_query > 0 ? static_cast<size_t>(n_query) : 0;
+    train_index.assign(nq, -1);
+    if (distance) distance->assign(nq, -1.0f);
+    if (!query || !train || n_query < 1 || n_train < 1) return Fail("Match: empty input");
+    if (dim < 4 || dim > 256 || (dim & 3)) return Fail("Match: dim must be a multiple of 4 in 4..256");
+    if ((query_valid && query_valid->size() != nq) || (train_valid && train_valid->size() != static_cast<size_t>(n_train)))
+        return Fail("Match: one valid flag per descriptor is needed");
+    fd_ctx *ctx = Context();
+    if (!ctx) return false;
+    fd_nn_match_opts o{dim, options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
+    std::vector<float> dist(2 * nq, -1.0f);
+    const int rc = fd_nn_match(ctx, 1, &o, query, query_valid ? query_valid->data() : nullptr, nullptr, n_query, train,
+                               train_valid ? train_valid->data() : nullptr, nullptr, n_train, train_index.data(),
+                               dist.data(), nullptr, 0);
+    if (rc != FD_OK) {
+        train_index.assign(nq, -1);
+        return Fail(std::string("fd_nn_match: ") + fd_last_error(ctx));
+    }
+    if (distance)
+        for (size_t i = 0; i < nq; ++i) (*distance)[i] = dist[2 * i];
     return true;
 }
 

@@ -67,6 +67,9 @@ struct fd_ctx {
     // fd_brief_match: the cross-check's reverse table ([batch][t_stride] best query of every train
     // descriptor), and the staging of host-pointer calls (query / train inputs, outputs)
     fdrt::DevBuf m_rev, m_qbits, m_qvalid, m_qcounts, m_tbits, m_tvalid, m_tcounts, m_idx, m_dist, m_counts;
+    // fd_nn_match shares them (descriptors staged in m_qbits / m_tbits) and adds the norms of both sets
+    // ([batch][q_stride], then [batch][t_stride])
+    fdrt::DevBuf m_norm;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

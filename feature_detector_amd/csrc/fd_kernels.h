@@ -307,6 +307,38 @@ struct MatchArgs {
     float max_ratio;      // <= 0: off
 };
 
+// Squared-L2 matcher for float descriptors (fd_nn_match.hip). k_nn_norms first writes n(x) of every
+// descriptor of both sets (+inf for one flagged invalid, which is how validity reaches k_nn_match);
+// k_nn_match then runs as the Hamming matcher does: forward a = query, b = train; the cross-check's
+// reverse pass a = train, b = query, out_idx = the reverse table, no other output and no test.
+struct NnNormArgs {
+    const float *desc[2];     // [batch][stride[i]][dim]
+    const uint8_t *valid[2];  // [batch][stride[i]] or null (= all valid)
+    const int32_t *counts[2];  // [batch] or null (= stride[i]); bits 25..31 ignored
+    float *out[2];            // [batch][stride[i]]; slots >= counts are not written
+    int stride[2];
+    int batch, dim;
+    int vec[2];  // desc[i] is 16-byte aligned (set by the launcher)
+};
+struct NnMatchArgs {
+    const float *a_desc;      // [batch][a_stride][dim]
+    const float *a_norm;      // [batch][a_stride] (k_nn_norms)
+    const int32_t *a_counts;  // [batch] or null (= a_stride); bits 25..31 ignored
+    int a_stride;
+    const float *b_desc;  // the same three arrays of the searched set
+    const float *b_norm;
+    const int32_t *b_counts;
+    int b_stride;
+    int batch, dim;       // dim: a multiple of 4, 4..256
+    int32_t *out_idx;     // [batch][a_stride]: best b index that passes the tests, else -1
+    float *out_dist;      // [batch][a_stride][2] raw best / second distance (-1: absent), or null
+    int32_t *out_counts;  // [batch] += accepted entries (zeroed by the caller), or null
+    const int32_t *rev;   // [batch][b_stride] best a index of every b entry (cross-check), or null
+    float max_distance;   // < 0: off
+    float max_ratio;      // <= 0: off
+    int b_vec;            // b_desc is 16-byte aligned (set by the launcher)
+};
+
 // SuperPoint heatmap -> candidate lists (the K1 list format + level-0 histogram), for K4.
 struct HeatArgs {
     const float *heat;  // [batch][rows][cols]
@@ -361,6 +393,8 @@ hipError_t launch_lsd_count(const LsdArgs &a, hipStream_t s);    // compact mode
 hipError_t launch_lsd_scatter(const LsdArgs &a, hipStream_t s);  // compact mode: the lists
 hipError_t launch_brief(const BriefArgs &a, hipStream_t s);
 hipError_t launch_brief_match(const MatchArgs &a, hipStream_t s);
+hipError_t launch_nn_norms(NnNormArgs a, hipStream_t s);
+hipError_t launch_nn_match(NnMatchArgs a, hipStream_t s);
 hipError_t launch_heat_candidates(const HeatArgs &a, hipStream_t s);
 int heat_blocks_per_frame(int64_t npx);
 hipError_t launch_nn_desc(const NnDescArgs &a, hipStream_t s);

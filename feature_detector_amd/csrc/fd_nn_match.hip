@@ -1,0 +1,237 @@
+// Nearest-neighbour squared-L2 matcher for NN float descriptors (fd_nn_match, an MI355X extension: the
+// reference has no matcher) for gfx950, on the f32-input MFMA.
+//
+// The distance is a definite float sequence (include/fd_hip.h): dot(q, t) and the norms are fmaf chains
+// with k ascending, d = fmaxf(0, (n(q) + n(t)) - 2 * dot). v_mfma_f32_16x16x4_f32 computes, per output
+// element, D = fma(a_k3, b_k3, fma(a_k2, b_k2, fma(a_k1, b_k1, fma(a_k0, b_k0, C)))) with one rounding
+// per product, so one accumulator per output pair, fed K steps 0, 1, 2, ... in order, is that chain. K
+// is never split across accumulators; the dependent-accumulator latency (40 cycles against a 32-cycle
+// issue) is covered by the independent 16-column sub-tiles of an LDS tile.
+//
+// Two kernels. k_nn_norms: one lane per descriptor, the plain fmaf chain n(x), +inf for a descriptor
+// that is flagged invalid. The +inf carries validity through k_nn_match at no cost per pair: an invalid
+// "b" entry has distance +inf and loses every `<`, an invalid "a" entry has only +inf distances, and
+// +inf is written as "absent" (-1). (A descriptor whose squared norm is not finite is therefore treated
+// as invalid; non-finite inputs are unspecified.)
+//
+// k_nn_match serves both directions like k_brief_match: the "a" side gets answers, the "b" side is
+// searched; the cross-check's reverse pass has a = train, b = query and writes only the raw best index.
+// A workgroup of 4 waves covers 64 "a" descriptors of one frame, wave w rows 16w .. 16w + 15, whose A
+// fragments stay in VGPRs for the whole K (lane l: row l & 15, k = 4s + (l >> 4) of step s: K / 4
+// registers). The frame's "b" descriptors go through LDS in tiles of TB rows, filled with 16-byte loads
+// and stores; the row pitch K + 4 floats puts the 64 lanes of a B-fragment read (row l & 15, k = 4s +
+// (l >> 4)) on the 64 banks 4 (l & 15) + (l >> 4). Every wave scans the whole tile for its own rows, so
+// no merge between waves is needed. C/D: lane l holds column l & 15 of rows 4 (l >> 4) + 0..3, so a lane
+// keeps (best, index, second) for four rows over the columns congruent to l & 15; columns ascend within
+// a lane, and the final merge over the 16 lanes that share the rows is the lexicographic minimum of
+// (distance, index), which is the serial scan's rule for any partition of the indices (fd_match.hip).
+#include "fd_device.h"
+#include "fd_kernels.h"
+
+namespace fdk {
+namespace {
+
+constexpr int kNnWaves = 4;
+constexpr int kNnThreads = kNnWaves * kWave;
+constexpr int kNnRows = 16 * kNnWaves;  // "a" descriptors per workgroup
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int nn_frame_count(const int32_t *counts, int f, int stride) {
+    if (!counts) return stride;
+    return min(static_cast<int>(static_cast<uint32_t>(counts[f]) & 0x01FFFFFFu), stride);
+}
+
+__device__ __forceinline__ f4 load4(const float *p, bool vec) {
+    if (vec) return *reinterpret_cast<const f4 *>(p);
+    return f4{p[0], p[1], p[2], p[3]};
+}
+
+// n(x) of every descriptor in slots < counts[f] of both sets (side 0, then side 1); +inf when flagged invalid.
+__global__ __launch_bounds__(256) void k_nn_norms(NnNormArgs a) {
+    const int64_t n0 = static_cast<int64_t>(a.batch) * a.stride[0], n1 = static_cast<int64_t>(a.batch) * a.stride[1];
+    int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n0 + n1) return;
+    const int side = i >= n0;
+    if (side) i -= n0;
+    const int stride = a.stride[side];
+    const int f = static_cast<int>(i / stride);
+    if (static_cast<int>(i - static_cast<int64_t>(f) * stride) >= nn_frame_count(a.counts[side], f, stride)) return;
+    const float *p = a.desc[side] + i * a.dim;
+    const bool vec = a.vec[side];
+    float acc = 0.0f;
+    for (int k = 0; k < a.dim; k += 4) {
+        const f4 v = load4(p + k, vec);
+        acc = __builtin_fmaf(v.x, v.x, acc);
+        acc = __builtin_fmaf(v.y, v.y, acc);
+        acc = __builtin_fmaf(v.z, v.z, acc);
+        acc = __builtin_fmaf(v.w, v.w, acc);
+    }
+    const bool valid = !a.valid[side] || a.valid[side][i];
+    a.out[side][i] = valid ? acc : __builtin_inff();
+}
+
+// K: the instance's descriptor length (dim zero-padded up to it: fmaf(0, 0, acc) leaves acc unchanged);
+// TB: "b" rows per LDS tile (TB / 16 independent accumulators per wave).
+template <int K, int TB>
+__global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
+    constexpr int P = K + 4, NS = K / 4, NJ = TB / 16, C4 = K / 4;
+    __shared__ __attribute__((aligned(16))) float tile[TB * P];
+    __shared__ float bnorm[TB];
+    const int tiles = (a.a_stride + kNnRows - 1) / kNnRows;
+    const int f = static_cast<int>(blockIdx.x) / tiles;
+    const int q0 = (static_cast<int>(blockIdx.x) - f * tiles) * kNnRows;
+    const int na = nn_frame_count(a.a_counts, f, a.a_stride);
+    if (q0 >= na) return;  // (the whole workgroup: nothing of this frame is read or written)
+    const int nb = nn_frame_count(a.b_counts, f, a.b_stride);
+    const int lane = lane_id();
+    const int wave = static_cast<int>(threadIdx.x) >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const float inf = __builtin_inff();
+
+    // A fragments of the wave's 16 rows, and the norms of the four rows this lane holds results of
+    float af[NS];
+    {
+        const int row = q0 + 16 * wave + c;
+        const float *ap = a.a_desc + (static_cast<int64_t>(f) * a.a_stride + min(row, na - 1)) * a.dim;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int k = 4 * s + g;
+            af[s] = (row < na && k < a.dim) ? ap[k] : 0.0f;
+        }
+    }
+    float an[4], best[4], second[4];
+    int bidx[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = q0 + 16 * wave + 4 * g + r;
+        an[r] = row < na ? a.a_norm[static_cast<int64_t>(f) * a.a_stride + row] : inf;
+        best[r] = inf;
+        second[r] = inf;
+        bidx[r] = -1;
+    }
+
+    const float *bf = a.b_desc + static_cast<int64_t>(f) * a.b_stride * a.dim;
+    const float *bnf = a.b_norm + static_cast<int64_t>(f) * a.b_stride;
+    for (int t0 = 0; t0 < nb; t0 += TB) {
+        const int n = min(TB, nb - t0);
+        __syncthreads();  // every wave is done with the previous tile
+        for (int i = static_cast<int>(threadIdx.x); i < n * C4; i += kNnThreads) {
+            const int r = i / C4, k = (i % C4) * 4;
+            f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (k < a.dim) v = load4(bf + static_cast<int64_t>(t0 + r) * a.dim + k, a.b_vec);
+            *reinterpret_cast<f4 *>(&tile[r * P + k]) = v;
+        }
+        if (static_cast<int>(threadIdx.x) < TB)
+            bnorm[threadIdx.x] = static_cast<int>(threadIdx.x) < n ? bnf[t0 + threadIdx.x] : inf;
+        __syncthreads();
+        f4 acc[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[j] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        const float *tp = tile + c * P + g;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], tp[16 * j * P + 4 * s], acc[j], 0, 0, 0);
+        }
+        // rows of the tile past its fill hold stale words: their norm is +inf and nothing of them is used
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const float bn = bnorm[16 * j + c];
+            const bool ok = bn < inf;
+            const int col = t0 + 16 * j + c;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float d = fmaxf(0.0f, (an[r] + bn) - 2.0f * acc[j][r]);
+                d = ok ? d : inf;
+                // the serial scan: a new best moves the old best to second, else d may lower second;
+                // a NaN compares false both times
+                const bool lt = d < best[r];
+                const float s2 = lt ? best[r] : d;
+                second[r] = s2 < second[r] ? s2 : second[r];
+                bidx[r] = lt ? col : bidx[r];
+                best[r] = lt ? d : best[r];
+            }
+        }
+    }
+
+    // merge over the 16 lanes (columns) that hold the same four rows: every lane ends with the result
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float ob = __shfl_xor(best[r], m), os = __shfl_xor(second[r], m);
+            const int oi = __shfl_xor(bidx[r], m);
+            const bool take = ob < best[r] || (ob == best[r] && oi < bidx[r]);
+            const float lose = take ? best[r] : ob;
+            float s2 = os < second[r] ? os : second[r];
+            s2 = lose < s2 ? lose : s2;
+            second[r] = s2;
+            best[r] = take ? ob : best[r];
+            bidx[r] = take ? oi : bidx[r];
+        }
+    }
+    // lane c < 4 of each group of 16 writes row 4g + c
+    float b1 = inf, b2 = inf;
+    int bi = -1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (c == r) {
+            b1 = best[r];
+            b2 = second[r];
+            bi = bidx[r];
+        }
+    }
+    const int q = q0 + 16 * wave + 4 * g + c;
+    const bool live = c < 4 && q < na;
+    const int64_t aslot = static_cast<int64_t>(f) * a.a_stride + q;
+    const bool has1 = live && b1 < inf, has2 = live && b2 < inf;
+    const float d1 = has1 ? b1 : -1.0f, d2 = has2 ? b2 : -1.0f;
+    const int raw = has1 ? bi : -1;
+    bool ok = raw >= 0;
+    if (ok && a.max_distance >= 0.0f && d1 > a.max_distance) ok = false;
+    // two float multiplies and one compare (the file is built without contraction); skipped without a second
+    if (ok && a.max_ratio > 0.0f && has2 && !(d1 < (a.max_ratio * a.max_ratio) * d2)) ok = false;
+    if (ok && a.rev && a.rev[static_cast<int64_t>(f) * a.b_stride + raw] != q) ok = false;
+    if (live) {
+        a.out_idx[aslot] = ok ? raw : -1;
+        if (a.out_dist) {
+            a.out_dist[2 * aslot] = d1;
+            a.out_dist[2 * aslot + 1] = d2;
+        }
+    }
+    if (a.out_counts) {
+        const int n_ok = popc64(ballot(ok));
+        if (lane == 0 && n_ok) atomicAdd(a.out_counts + f, n_ok);
+    }
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+hipError_t launch_nn_norms(NnNormArgs a, hipStream_t s) {
+    const int64_t total = static_cast<int64_t>(a.batch) * (static_cast<int64_t>(a.stride[0]) + a.stride[1]);
+    if (total == 0) return hipSuccess;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    for (int i = 0; i < 2; ++i) a.vec[i] = aligned16(a.desc[i]);
+    hipLaunchKernelGGL(k_nn_norms, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_nn_match(NnMatchArgs a, hipStream_t s) {
+    const int64_t blocks = static_cast<int64_t>(a.batch) * ((a.a_stride + kNnRows - 1) / kNnRows);
+    if (blocks == 0) return hipSuccess;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    a.b_vec = aligned16(a.b_desc);
+    const unsigned g = static_cast<unsigned>(blocks);
+    if (a.dim <= 128)
+        hipLaunchKernelGGL((k_nn_match<128, 64>), dim3(g), dim3(kNnThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_nn_match<256, 32>), dim3(g), dim3(kNnThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace fdk

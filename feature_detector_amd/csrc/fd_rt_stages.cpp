@@ -1,5 +1,6 @@
 // Host runtime of libfdhip.so: the remaining stages. PNG ingest (fd_png.cpp decodes, fd_gray.hip
-// converts), BRIEF (fd_brief.hip) and its matcher (fd_match.hip), and the NN stages (selection over
+// converts), BRIEF (fd_brief.hip) and its matcher (fd_match.hip), the float-descriptor matcher
+// (fd_nn_match.hip), and the NN stages (selection over
 // heatmaps and keypoint lists, descriptor sampling, the SuperPoint layers of fd_nn.hip / fd_nn_act.hip).
 #include <algorithm>
 #include <cmath>
@@ -220,6 +221,119 @@ int fd_brief_match(fd_ctx *c, int batch, const fd_match_opts *opts, const uint32
             FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
         return copy_back_written(c, q_counts, batch, q_stride,
                                  {{out_idx, a.out_idx, sizeof(int32_t)}, {out_dist, a.out_dist, 2 * sizeof(int32_t)}});
+    }
+    return FD_OK;
+}
+
+// Squared-L2 matcher (fd_nn_match.hip): the norms of both sets first (validity rides on them), then as
+// fd_brief_match: with cross_check the reverse pass into the reverse table, then the forward pass.
+int fd_nn_match(fd_ctx *c, int batch, const fd_nn_match_opts *opts, const float *q_desc, const uint8_t *q_valid,
+                const int32_t *q_counts, int32_t q_stride, const float *t_desc, const uint8_t *t_valid,
+                const int32_t *t_counts, int32_t t_stride, int32_t *out_idx, float *out_dist, int32_t *out_counts,
+                int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_desc || !t_desc || !out_idx) return fail(c, FD_ERR_INVALID, "bad arguments");
+    if (batch < 1 || q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "need batch >= 1 and strides >= 0");
+    if (opts->dim < 4 || opts->dim > 256 || (opts->dim & 3))
+        return fail(c, FD_ERR_INVALID, "dim must be a multiple of 4 in [4, 256]");
+    if (!std::isfinite(opts->max_ratio) || !std::isfinite(opts->max_distance))
+        return fail(c, FD_ERR_INVALID, "max_ratio and max_distance must be finite");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    if (q_stride == 0) {  // no query slots: every frame has 0 matches
+        if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+        if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
+        return FD_OK;
+    }
+    const size_t dim = static_cast<size_t>(opts->dim);
+    const size_t qslots = static_cast<size_t>(batch) * q_stride, tslots = static_cast<size_t>(batch) * t_stride;
+    fdk::NnNormArgs nn{};
+    fdk::NnMatchArgs a{};
+    a.a_stride = q_stride;
+    a.b_stride = t_stride;
+    a.batch = batch;
+    a.dim = opts->dim;
+    a.max_distance = opts->max_distance;
+    a.max_ratio = opts->max_ratio;
+    if (io_on_device) {
+        a.a_desc = q_desc;
+        nn.valid[0] = q_valid;
+        a.a_counts = q_counts;
+        a.b_desc = t_desc;
+        nn.valid[1] = t_valid;
+        a.b_counts = t_counts;
+        a.out_idx = out_idx;
+        a.out_dist = out_dist;
+        a.out_counts = out_counts;
+    } else {
+        // one side's three arrays into their staging buffers (absent ones stay null: all valid / stride each)
+        auto stage = [&](const float *desc, const uint8_t *valid, const int32_t *counts, size_t slots, DevBuf &ddesc,
+                         DevBuf &dvalid, DevBuf &dcounts, const float *&odesc, const uint8_t *&ovalid,
+                         const int32_t *&ocounts) -> int {
+            FD_HIP_TRY(c, ensure_as(c, ddesc, dim * slots, odesc));
+            if (slots) FD_HIP_TRY(c, hipMemcpyAsync(ddesc.p, desc, sizeof(float) * dim * slots, hipMemcpyHostToDevice, c->stream));
+            if (valid) {
+                FD_HIP_TRY(c, ensure_as(c, dvalid, slots, ovalid));
+                if (slots) FD_HIP_TRY(c, hipMemcpyAsync(dvalid.p, valid, slots, hipMemcpyHostToDevice, c->stream));
+            }
+            if (counts) {
+                FD_HIP_TRY(c, ensure_as(c, dcounts, batch, ocounts));
+                FD_HIP_TRY(c, hipMemcpyAsync(dcounts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
+            }
+            return FD_OK;
+        };
+        if ((rc = stage(q_desc, q_valid, q_counts, qslots, c->m_qbits, c->m_qvalid, c->m_qcounts, a.a_desc, nn.valid[0],
+                        a.a_counts)))
+            return rc;
+        if ((rc = stage(t_desc, t_valid, t_counts, tslots, c->m_tbits, c->m_tvalid, c->m_tcounts, a.b_desc, nn.valid[1],
+                        a.b_counts)))
+            return rc;
+        FD_HIP_TRY(c, ensure_as(c, c->m_idx, qslots, a.out_idx));
+        if (out_dist) FD_HIP_TRY(c, ensure_as(c, c->m_dist, 2 * qslots, a.out_dist));
+        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->m_counts, batch, a.out_counts));
+    }
+    float *norms = nullptr;
+    FD_HIP_TRY(c, ensure_as(c, c->m_norm, qslots + tslots, norms));
+    a.a_norm = norms;
+    a.b_norm = norms + qslots;
+    nn.desc[0] = a.a_desc;
+    nn.desc[1] = a.b_desc;
+    nn.counts[0] = a.a_counts;
+    nn.counts[1] = a.b_counts;
+    nn.out[0] = norms;
+    nn.out[1] = norms + qslots;
+    nn.stride[0] = q_stride;
+    nn.stride[1] = t_stride;
+    nn.batch = batch;
+    nn.dim = opts->dim;
+    FD_HIP_TRY(c, fdk::launch_nn_norms(nn, c->stream));
+    if (opts->cross_check && t_stride > 0) {
+        int32_t *rev = nullptr;
+        FD_HIP_TRY(c, ensure_as(c, c->m_rev, tslots, rev));
+        fdk::NnMatchArgs r{};
+        r.a_desc = a.b_desc;
+        r.a_norm = a.b_norm;
+        r.a_counts = a.b_counts;
+        r.a_stride = t_stride;
+        r.b_desc = a.a_desc;
+        r.b_norm = a.a_norm;
+        r.b_counts = a.a_counts;
+        r.b_stride = q_stride;
+        r.batch = batch;
+        r.dim = opts->dim;
+        r.out_idx = rev;
+        r.max_distance = -1.0f;
+        FD_HIP_TRY(c, fdk::launch_nn_match(r, c->stream));
+        a.rev = rev;
+    }
+    if (a.out_counts) FD_HIP_TRY(c, hipMemsetAsync(a.out_counts, 0, sizeof(int32_t) * batch, c->stream));
+    FD_HIP_TRY(c, fdk::launch_nn_match(a, c->stream));
+    if (!io_on_device) {
+        if (out_counts)
+            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
+        return copy_back_written(c, q_counts, batch, q_stride,
+                                 {{out_idx, a.out_idx, sizeof(int32_t)}, {out_dist, a.out_dist, 2 * sizeof(float)}});
     }
     return FD_OK;
 }

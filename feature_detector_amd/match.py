@@ -1,8 +1,9 @@
-"""Nearest-neighbour Hamming matching of BRIEF descriptors over the C ABI (fd_brief_match).
+"""Nearest-neighbour matching over the C ABI: Hamming distance of BRIEF descriptors (fd_brief_match) and
+squared L2 distance of NN float descriptors (fd_nn_match).
 
 An MI355X extension (the reference has no matcher): the stage after detect_points -> brief_compute, on
-the same [batch][stride] layouts, so a detect -> describe -> match chain stays on the GPU. The
-semantics (validity, ties, the three acceptance tests) are in include/fd_hip.h.
+the same [batch][stride] layouts, so a detect -> describe -> match chain stays on the GPU; nn_match is
+the same stage after nn_descriptors / nn_select_list. The semantics (validity, ties, the three acceptance tests) are in include/fd_hip.h.
 """
 from __future__ import annotations
 
@@ -12,14 +13,14 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_match_opts
+from ._lib import fd_match_opts, fd_nn_match_opts
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
 
 @dataclass
 class MatchResult:
     idx: object     # int32 [B, Sq]: accepted train index per query slot, else -1
-    dist: object    # int32 [B, Sq, 2]: raw best / second-best distance (-1: absent)
+    dist: object    # [B, Sq, 2]: raw best / second-best distance (-1: absent); int32 (brief_match) or float32 (nn_match)
     counts: object  # int32 [B]: accepted matches per frame
 
 
@@ -107,5 +108,80 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     _bind_stream(ctx, on_dev)
     rc = _lib.load().fd_brief_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qw), _ptr(qv), _ptr(qc), sq, _ptr(tw), _ptr(tv),
                                     _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return MatchResult(idx, dist, counts)
+
+
+def _float_side(desc, valid, counts, on_dev, name):
+    if on_dev:
+        import torch
+
+        if desc.dtype != torch.float32:
+            raise TypeError(f"{name}_desc must be float32")
+        d = desc.contiguous()
+        if d.dim() == 2:
+            d = d.unsqueeze(0)
+    else:
+        d = np.asarray(desc)
+        if d.dtype != np.float32:
+            raise TypeError(f"{name}_desc must be float32")
+        d = np.ascontiguousarray(d)
+        if d.ndim == 2:
+            d = d[None]
+    if len(d.shape) != 3:
+        raise ValueError(f"{name}_desc must be [batch, S, dim] or [S, dim]")
+    b, s = int(d.shape[0]), int(d.shape[1])
+    if on_dev:
+        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
+        c = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
+    else:
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
+        c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
+    return d, v, c, b, s
+
+
+def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid=None, max_distance: float = -1.0,
+             max_ratio: float = 0.0, cross_check: bool = False, out=None, ctx: Context | None = None) -> MatchResult:
+    """fd_nn_match for a batch: frame b of the query set against frame b of the train set, squared L2.
+
+    q_desc / t_desc: float32 [B, S, dim] or [S, dim] (batch 1), as nn_descriptors / nn_select_list return
+    them; dim is the last axis (a multiple of 4, 4..256). *_counts, *_valid, host / device inputs and
+    out= are as in brief_match, except that dist (and out's dist tensor) is float32 [B, Sq, 2]: squared
+    distances, -1.0 where absent. max_distance bounds the squared distance; max_ratio is Lowe's ratio of
+    distances (applied squared to the squared distances).
+    """
+    ctx = _resolve_ctx(ctx, q_desc, t_desc)
+    on_dev = _is_torch_device_tensor(q_desc)
+    if on_dev != _is_torch_device_tensor(t_desc):
+        raise ValueError("q_desc and t_desc must both be device tensors or both host arrays")
+    qd, qv, qc, b, sq = _float_side(q_desc, q_valid, q_counts, on_dev, "q")
+    td, tv, tc, tb, st = _float_side(t_desc, t_valid, t_counts, on_dev, "t")
+    if tb != b:
+        raise ValueError("q_desc and t_desc must have the same batch")
+    dim = int(qd.shape[2])
+    if int(td.shape[2]) != dim:
+        raise ValueError("q_desc and t_desc must have the same dim")
+    opts = fd_nn_match_opts(dim, float(max_distance), float(max_ratio), 1 if cross_check else 0)
+    if on_dev:
+        import torch
+
+        if out is not None:
+            idx, dist, counts = out
+            for t, shape, dt in ((idx, (b, sq), torch.int32), (dist, (b, sq, 2), torch.float32), (counts, (b,), torch.int32)):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                    raise ValueError(f"out must be contiguous tensors: int32 {(b, sq)}, float32 {(b, sq, 2)}, int32 {(b,)}")
+        else:
+            idx = torch.full((b, sq), -1, dtype=torch.int32, device=qd.device)
+            dist = torch.full((b, sq, 2), -1.0, dtype=torch.float32, device=qd.device)
+            counts = torch.zeros((b,), dtype=torch.int32, device=qd.device)
+    else:
+        if out is not None:
+            raise ValueError("out= is for device tensors")
+        idx = np.full((b, sq), -1, np.int32)
+        dist = np.full((b, sq, 2), -1.0, np.float32)
+        counts = np.zeros((b,), np.int32)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_nn_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qd), _ptr(qv), _ptr(qc), sq, _ptr(td), _ptr(tv),
+                                 _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return MatchResult(idx, dist, counts)

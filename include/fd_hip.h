@@ -344,6 +344,58 @@ int fd_brief_match(fd_ctx *ctx, int batch, const fd_match_opts *opts,
                    const uint32_t *t_bits, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
                    int32_t *out_idx, int32_t *out_dist, int32_t *out_counts, int io_on_device);
 
+/* ---- Squared-L2 matcher for NN float descriptors (MI355X extension: the reference has no matcher) --- */
+typedef struct fd_nn_match_opts {
+    int32_t dim;          /* floats per descriptor: a multiple of 4, 4..256 */
+    float   max_distance; /* reject a best match with squared distance > max_distance; < 0: no bound */
+    float   max_ratio;    /* accept only if d1 < (max_ratio * max_ratio) * d2 (squared distances); <= 0: off */
+    int32_t cross_check;  /* 1: accept q -> t only if t's best query is q */
+} fd_nn_match_opts;
+
+/*
+ * fd_nn_match -- nearest neighbour in squared L2 distance of every query descriptor among the train
+ * descriptors, frame b of the query set against frame b of the train set: fd_brief_match's sibling for
+ * the float descriptors of the SuperPoint / DISK path. *_desc is [batch][stride][dim] float, exactly as
+ * fd_nn_descriptors and fd_nn_select_list write them (256 channels for SuperPoint, 128 for DISK);
+ * *_valid [batch][stride] (NULL = all valid) and *_counts int32 [batch] (NULL = stride each; bits 25..31
+ * are ignored) are as in fd_brief_match, and so is matching frame i of one batch against its frame
+ * i + 1: the train pointers advanced by one frame, batch - 1.
+ * Distance: squared L2 as this float sequence, bit for bit (no contraction, one rounding per step):
+ *   dot(q, t): acc = 0; for k = 0 .. dim-1: acc = fmaf(q[k], t[k], acc)
+ *   n(x) = dot(x, x), the same chain
+ *   d = fmaxf(0.0f, (n(q) + n(t)) - 2.0f * dot(q, t))
+ * d(q, t) has the same bits from either side (products and sums commute), so the cross-check below is
+ * symmetric: "t's best query is q" is decided on the very distances of the forward search.
+ * An invalid train descriptor is never a candidate; an invalid query gets out_idx -1 and both distances
+ * -1. An all-zero descriptor is valid unless flagged (fd_nn_descriptors writes zeros for keypoints
+ * outside the map: flag those). Equal distances go to the lowest train index (what a serial scan in
+ * ascending index order with `<` gives); a NaN distance never wins a `<`. Inputs that are not finite, or
+ * whose squared norm is not finite in float, are otherwise unspecified (such a descriptor may be
+ * treated as invalid).
+ * out_dist [batch][q_stride][2] float (NULL to skip): [0] the smallest distance to a valid train
+ * descriptor, [1] the smallest distance to a valid train descriptor with another index than the best one
+ * (equal to [0] on a tie); -1.0f when absent. Both are raw values, written whether or not the match is
+ * accepted.
+ * out_idx [batch][q_stride]: the best train index if it passes every enabled test, else -1. Tests:
+ * max_distance (rejects d1 > max_distance); the ratio test, two float multiplies and one compare
+ * (d1 < (max_ratio * max_ratio) * d2, skipped when d2 is absent); cross_check (the train descriptor's
+ * best query -- over the frame's valid queries, the same distance sequence, lowest query index on ties,
+ * independent of the other two tests -- must be this query).
+ * out_counts [batch] (NULL to skip): accepted matches among slots < q_counts[b]. Slots >= q_counts[b]
+ * of out_idx and out_dist are not written. q_stride 0: nothing but out_counts = 0; t_stride 0: as all
+ * train counts 0.
+ * All pointers are device pointers when io_on_device: the call is then asynchronous on the context's
+ * stream, and graph-capturable once a first call of the shape has sized the workspace (the norms and
+ * the cross-check's reverse table; growing them under capture fails). Host pointers otherwise: staged
+ * through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx / opts / q_desc / t_desc / out_idx NULL, dim outside 4..256 or not a multiple of
+ * 4, a negative stride, batch < 1, a non-finite max_ratio or max_distance.
+ */
+int fd_nn_match(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts,
+                const float *q_desc, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                const float *t_desc, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

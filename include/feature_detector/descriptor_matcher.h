@@ -62,6 +62,55 @@ private:
     std::string error_;
 };
 
+/* Class NNDescriptorMatcher Declaration. */
+// Nearest-neighbour squared-L2 matching of NN float descriptors (SuperPoint 256, DISK 128 channels) over
+// fd_nn_match. Descriptors are contiguous rows of `dim` floats: a std::vector of the reference's
+// Eigen::Matrix<float, N, 1> descriptors is such an array (data() of its first element, dim = N), so no
+// Eigen type appears here. The semantics, the float sequence of the distance included, are fd_nn_match's
+// (include/fd_hip.h).
+class NNDescriptorMatcher {
+public:
+    struct Options {
+        float kMaxDistance = -1.0f;  // reject a best match with squared distance above this; < 0: no bound
+        float kMaxRatio = 0.0f;      // accept only if best < kMaxRatio^2 * second best (squared distances); <= 0: off
+        bool kCrossCheck = false;    // accept q -> t only if t's best query is q
+    };
+
+public:
+    NNDescriptorMatcher() = default;
+    virtual ~NNDescriptorMatcher();
+    NNDescriptorMatcher(const NNDescriptorMatcher &) = delete;
+    NNDescriptorMatcher &operator=(const NNDescriptorMatcher &) = delete;
+
+    // query: n_query rows, train: n_train rows of dim floats (dim a multiple of 4, 4..256).
+    // train_index[i]: the train row matched to query row i, or -1. distance (optional): [i] the raw
+    // smallest squared distance of query i to a valid train row, accepted or not (-1: none).
+    // query_valid / train_valid (optional, one flag per row): flag 0 the all-zero descriptors of keypoints
+    // outside the descriptor map to keep them out of the matching.
+    // False for empty inputs, a bad dim, flag vectors of the wrong size, or a libfdhip failure (last_error()).
+    bool Match(const float *query, int32_t n_query, const float *train, int32_t n_train, int32_t dim,
+               std::vector<int32_t> &train_index, std::vector<float> *distance = nullptr,
+               const std::vector<uint8_t> *query_valid = nullptr, const std::vector<uint8_t> *train_valid = nullptr);
+
+    // Reference for member variables.
+    Options &options() { return options_; }
+    const Options &options() const { return options_; }
+
+    void set_device(int device);
+    int device() const { return device_; }
+    const std::string &last_error() const { return error_; }
+
+private:
+    fd_ctx *Context();
+    bool Fail(const std::string &what);
+
+private:
+    Options options_;
+    fd_ctx *ctx_ = nullptr;
+    int device_ = -1;
+    std::string error_;
+};
+
 }  // namespace feature_detector
 
 #endif  // FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_

@@ -9,6 +9,10 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
   --shape fastmatch  FAST (need 500, dist 15) + BRIEF-256 + fd_brief_match of frame i against frame i + 1 of
                      the batch (63 frame pairs, detect's device counts and BRIEF's valid flags in place), 10
                      calls (--cross-check: with the cross-check, two k_brief_match launches per call)
+  --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
+                     128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
+                     baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
+                     events (the whole call: k_nn_norms + k_nn_match launches + the counts memset)
   --shape lsd        fd_lsd_map (dense) and fd_lsd_lines (compact map + host stage), 1920x1080 batch 256,
                      64-px checker + noise (BASELINE configs[3]), 3 calls each (--kind dense / compact: one;
                      dense_unpitched: dense maps with unpadded rows)
@@ -27,11 +31,12 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
 p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
+p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
 g = torch.Generator(device="cuda")
@@ -122,6 +127,33 @@ elif a.shape == "fastmatch":  # configs[2]'s shape with need 500, then the match
         fd.brief_match(bits[:-1], bits[1:], res.counts[:-1], res.counts[1:], valid[:-1], valid[1:], max_distance=64,
                        max_ratio=0.9, cross_check=a.cross_check, out=out)
     print("matches per frame pair (mean):", float(out[2].float().mean()), "keypoints:", float((res.counts & 0x1FFFFFF).float().mean()))
+elif a.shape == "nnmatch":
+    kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
+    B, S = 64, 240
+    q = torch.nn.functional.normalize(torch.randn((B, S, a.dim), generator=g, device="cuda"), dim=2)
+    t = torch.nn.functional.normalize(q.roll(17, 1) + 0.3 * torch.randn((B, S, a.dim), generator=g, device="cuda"), dim=2)
+    out = (torch.empty((B, S), dtype=torch.int32, device="cuda"), torch.empty((B, S, 2), dtype=torch.float32, device="cuda"),
+           torch.empty((B,), dtype=torch.int32, device="cuda"))
+
+    def ours():
+        fd.nn_match(q, t, max_ratio=0.9, cross_check=a.cross_check, out=out)
+
+    def baseline():  # what a caller outside the C ABI writes (no validity, counts or tie rule)
+        d = (q * q).sum(2)[:, :, None] + (t * t).sum(2)[:, None, :] - 2.0 * torch.bmm(q, t.transpose(1, 2))
+        return torch.topk(d, 2, dim=2, largest=False)
+
+    for name, fn in (("fd.nn_match", ours), ("torch bmm + norms + topk(2)", baseline)):
+        for _ in range(3):
+            fn()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range((a.calls or 20) + 1)]
+        ev[0].record()
+        for e in ev[1:]:
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        us = sorted(1e3 * x.elapsed_time(y) for x, y in zip(ev, ev[1:]))
+        print(f"{name}, {kind}: median {us[len(us) // 2]:.1f} us per call (min {us[0]:.1f}, max {us[-1]:.1f}), {len(us)} calls")
+    print("matches per frame (mean):", float(out[2].float().mean()))
 else:
     kind = a.kind or "fast"
     frames = noise(64, 720, 1280)
