@@ -1,8 +1,10 @@
 // BriefMatcher over libfdhip.so (fd_brief_match): an MI355X extension, the reference has no matcher.
 // One call matches every query descriptor against every train descriptor in one kernel launch (two with
 // the cross-check). NNDescriptorMatcher: the same over fd_nn_match for float descriptors (squared L2).
+// MatchGuided of both: the same call through the guided entry points, with the keypoint positions.
 #include "feature_detector/descriptor_matcher.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -57,11 +59,38 @@ bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<
     return true;
 }
 
+// Vec2 positions -> [n][2] floats (x, y)
+std::vector<float> Flatten(const std::vector<Vec2> &uv) {
+    std::vector<float> xy(2 * uv.size());
+    for (size_t i = 0; i < uv.size(); ++i) {
+        xy[2 * i] = uv[i].x();
+        xy[2 * i + 1] = uv[i].y();
+    }
+    return xy;
+}
+
+bool BadRadius(float r) { return !std::isfinite(r) || r < 0.0f; }
+
 }  // namespace
 
 bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
                          std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
                          const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    return Run(query, train, nullptr, nullptr, 0.0f, 0.0f, train_index, distance, query_valid, train_valid);
+}
+
+bool BriefMatcher::MatchGuided(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                               const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, float radius_x,
+                               float radius_y, std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
+                               const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    return Run(query, train, &query_uv, &train_uv, radius_x, radius_y, train_index, distance, query_valid, train_valid);
+}
+
+// query_uv / train_uv null: Match; else MatchGuided
+bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                       const std::vector<Vec2> *query_uv, const std::vector<Vec2> *train_uv, float radius_x, float radius_y,
+                       std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
+                       const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
     train_index.assign(query.size(), -1);
     if (distance) distance->assign(query.size(), -1);
     if (query.empty() || train.empty()) return Fail("Match: empty input");
@@ -71,13 +100,25 @@ bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<
     if (!Pack(query, length, q) || !Pack(train, length, t)) return Fail("Match: descriptors of unequal length");
     if ((query_valid && query_valid->size() != query.size()) || (train_valid && train_valid->size() != train.size()))
         return Fail("Match: one valid flag per descriptor is needed");
+    if (query_uv && (query_uv->size() != query.size() || train_uv->size() != train.size()))
+        return Fail("MatchGuided: one position per descriptor is needed");
+    if (query_uv && (BadRadius(radius_x) || BadRadius(radius_y))) return Fail("MatchGuided: a radius must be finite and >= 0");
     fd_ctx *ctx = Context();
     if (!ctx) return false;
     fd_match_opts o{static_cast<int32_t>(length), options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
     std::vector<int32_t> dist(2 * query.size(), -1);
-    const int rc = fd_brief_match(ctx, 1, &o, q.data(), query_valid ? query_valid->data() : nullptr, nullptr,
-                                  static_cast<int32_t>(query.size()), t.data(), train_valid ? train_valid->data() : nullptr,
-                                  nullptr, static_cast<int32_t>(train.size()), train_index.data(), dist.data(), nullptr, 0);
+    const uint8_t *qv = query_valid ? query_valid->data() : nullptr, *tv = train_valid ? train_valid->data() : nullptr;
+    const int32_t nq = static_cast<int32_t>(query.size()), nt = static_cast<int32_t>(train.size());
+    int rc;
+    if (query_uv) {
+        const std::vector<float> qxy = Flatten(*query_uv), txy = Flatten(*train_uv);
+        const fd_match_gate gate{radius_x, radius_y};
+        rc = fd_brief_match_guided(ctx, 1, &o, &gate, q.data(), qv, nullptr, nq, qxy.data(), t.data(), tv, nullptr, nt,
+                                   txy.data(), train_index.data(), dist.data(), nullptr, 0);
+    } else {
+        rc = fd_brief_match(ctx, 1, &o, q.data(), qv, nullptr, nq, t.data(), tv, nullptr, nt, train_index.data(),
+                            dist.data(), nullptr, 0);
+    }
     if (rc != FD_OK) {
         train_index.assign(query.size(), -1);
         return Fail(std::string("fd_brief_match: ") + fd_last_error(ctx));
@@ -123,6 +164,22 @@ bool NNDescriptorMatcher::Fail(const std::string &what) {
 bool NNDescriptorMatcher::Match(const float *query, int32_t n_query, const float *train, int32_t n_train, int32_t dim,
                                 std::vector<int32_t> &train_index, std::vector<float> *distance,
                                 const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    return Run(query, n_query, nullptr, train, n_train, nullptr, dim, false, 0.0f, 0.0f, train_index, distance, query_valid,
+               train_valid);
+}
+
+bool NNDescriptorMatcher::MatchGuided(const float *query, int32_t n_query, const float *query_xy, const float *train,
+                                      int32_t n_train, const float *train_xy, int32_t dim, float radius_x, float radius_y,
+                                      std::vector<int32_t> &train_index, std::vector<float> *distance,
+                                      const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+    return Run(query, n_query, query_xy, train, n_train, train_xy, dim, true, radius_x, radius_y, train_index, distance,
+               query_valid, train_valid);
+}
+
+bool NNDescriptorMatcher::Run(const float *query, int32_t n_query, const float *query_xy, const float *train,
+                              int32_t n_train, const float *train_xy, int32_t dim, bool guided, float radius_x,
+                              float radius_y, std::vector<int32_t> &train_index, std::vector<float> *distance,
+                              const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
     const size_t nq = n_query > 0 ? static_cast<size_t>(n_query) : 0;
     train_index.assign(nq, -1);
     if (distance) distance->assign(nq, -1.0f);
@@ -130,13 +187,22 @@ bool NNDescriptorMatcher::Match(const float *query, int32_t n_query, const float
     if (dim < 4 || dim > 256 || (dim & 3)) return Fail("Match: dim must be a multiple of 4 in 4..256");
     if ((query_valid && query_valid->size() != nq) || (train_valid && train_valid->size() != static_cast<size_t>(n_train)))
         return Fail("Match: one valid flag per descriptor is needed");
+    if (guided && (!query_xy || !train_xy)) return Fail("MatchGuided: positions are needed");
+    if (guided && (BadRadius(radius_x) || BadRadius(radius_y))) return Fail("MatchGuided: a radius must be finite and >= 0");
     fd_ctx *ctx = Context();
     if (!ctx) return false;
     fd_nn_match_opts o{dim, options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
     std::vector<float> dist(2 * nq, -1.0f);
-    const int rc = fd_nn_match(ctx, 1, &o, query, query_valid ? query_valid->data() : nullptr, nullptr, n_query, train,
-                               train_valid ? train_valid->data() : nullptr, nullptr, n_train, train_index.data(),
-                               dist.data(), nullptr, 0);
+    const uint8_t *qv = query_valid ? query_valid->data() : nullptr, *tv = train_valid ? train_valid->data() : nullptr;
+    int rc;
+    if (guided) {
+        const fd_match_gate gate{radius_x, radius_y};
+        rc = fd_nn_match_guided(ctx, 1, &o, &gate, query, qv, nullptr, n_query, query_xy, train, tv, nullptr, n_train,
+                                train_xy, train_index.data(), dist.data(), nullptr, 0);
+    } else {
+        rc = fd_nn_match(ctx, 1, &o, query, qv, nullptr, n_query, train, tv, nullptr, n_train, train_index.data(),
+                         dist.data(), nullptr, 0);
+    }
     if (rc != FD_OK) {
         train_index.assign(nq, -1);
         return Fail(std::string("fd_nn_match: ") + fd_last_error(ctx));

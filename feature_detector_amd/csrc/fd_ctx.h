@@ -70,6 +70,8 @@ struct fd_ctx {
     // fd_nn_match shares them (descriptors staged in m_qbits / m_tbits) and adds the norms of both sets
     // ([batch][q_stride], then [batch][t_stride])
     fdrt::DevBuf m_norm;
+    // the guided matchers' host-pointer calls stage both sets' positions ([batch][stride][2]) here
+    fdrt::DevBuf m_qxy, m_txy;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

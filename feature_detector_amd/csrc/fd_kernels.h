@@ -288,7 +288,9 @@ struct BriefArgs {
 
 // Hamming matcher (fd_match.hip): every entry of the "a" set against the "b" set of the same frame.
 // Forward pass: a = query, b = train. Cross-check's reverse pass: a = train, b = query, out_idx = the
-// reverse table, no other output and no test.
+// reverse table, no other output and no test. Guided matching (fd_brief_match_guided): with a_xy / b_xy
+// set, a "b" entry is a candidate of an "a" entry only inside the window |dx| <= radius_x, |dy| <= radius_y
+// (the reverse pass swaps the two position arrays with the sets; the gate is symmetric).
 struct MatchArgs {
     const uint32_t *a_bits;   // [batch][a_stride][ceil(length / 32)]
     const uint8_t *a_valid;   // [batch][a_stride] or null (= all valid)
@@ -305,6 +307,9 @@ struct MatchArgs {
     const int32_t *rev;   // [batch][b_stride] best a index of every b entry (cross-check), or null
     int max_distance;     // < 0: off
     float max_ratio;      // <= 0: off
+    const float *a_xy;    // [batch][a_stride][2] (x, y), or null (both null: no gate)
+    const float *b_xy;    // [batch][b_stride][2]
+    float radius_x, radius_y;  // the window's half-width / half-height (unused without a gate)
 };
 
 // Squared-L2 matcher for float descriptors (fd_nn_match.hip). k_nn_norms first writes n(x) of every
@@ -337,6 +342,9 @@ struct NnMatchArgs {
     float max_distance;   // < 0: off
     float max_ratio;      // <= 0: off
     int b_vec;            // b_desc is 16-byte aligned (set by the launcher)
+    const float *a_xy;    // [batch][a_stride][2] (x, y), or null (both null: no gate), as in MatchArgs
+    const float *b_xy;    // [batch][b_stride][2]
+    float radius_x, radius_y;
 };
 
 // SuperPoint heatmap -> candidate lists (the K1 list format + level-0 histogram), for K4.

@@ -23,6 +23,12 @@
 // instead of 0 (a word per entry in LDS), so it loses against every valid entry (distance <= 256), and
 // a result >= kInvalidPenalty means "absent". Bits above `length` are masked on both sides, once: the
 // lane's own words when they are loaded, the "b" words when a tile is filled.
+//
+// The GATED instances (fd_brief_match_guided) add the search window: a lane keeps its own entry's (x, y)
+// in two registers, a tile's 256 "b" positions go to LDS beside the words (2 KiB, read as the same
+// broadcast), and a pair outside the window takes the invalid entry's route: its popcount sum starts at
+// kInvalidPenalty. Per pair that is two subtractions, two compares and a select; the update and the merge
+// do not know of it. |b - a| has the same bits as |a - b|, so the reverse pass decides on the same pairs.
 #include "fd_device.h"
 #include "fd_kernels.h"
 
@@ -42,10 +48,12 @@ __device__ __forceinline__ int frame_count(const int32_t *counts, int f, int str
 }
 
 // NW: descriptor words held per lane and per LDS row (words above ceil(length / 32) are zero).
-template <int NW>
+// GATED: only "b" entries inside the lane's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y).
+template <int NW, bool GATED>
 __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t tile[kMatchTile * NW];
     __shared__ uint32_t pen[kMatchTile];
+    __shared__ float bxy[GATED ? 2 * kMatchTile : 1];
     __shared__ int32_t part[3][kMatchWaves - 1][kWave];
     const int tiles = (a.a_stride + kWave - 1) / kWave;
     const int f = static_cast<int>(blockIdx.x) / tiles;
@@ -66,6 +74,15 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
         qw[w] = (live && w < nw) ? a.a_bits[aslot * nw + w] : 0u;
         if (w == nw - 1) qw[w] &= tail;
     }
+    float ax = 0.0f, ay = 0.0f;
+    const float *bp = nullptr;
+    if constexpr (GATED) {
+        if (live) {
+            ax = a.a_xy[2 * aslot];
+            ay = a.a_xy[2 * aslot + 1];
+        }
+        bp = a.b_xy + static_cast<int64_t>(f) * a.b_stride * 2;
+    }
     const uint32_t *bb = a.b_bits + static_cast<int64_t>(f) * a.b_stride * nw;
     const uint8_t *bv = a.b_valid ? a.b_valid + static_cast<int64_t>(f) * a.b_stride : nullptr;
     int best = kAbsent, second = kAbsent, bidx = -1;
@@ -80,10 +97,19 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
         }
         if (static_cast<int>(threadIdx.x) < n)
             pen[threadIdx.x] = (bv && !bv[t0 + threadIdx.x]) ? static_cast<uint32_t>(kInvalidPenalty) : 0u;
+        if constexpr (GATED) {
+            for (int i = static_cast<int>(threadIdx.x); i < 2 * n; i += kMatchThreads)
+                bxy[i] = bp[static_cast<int64_t>(t0) * 2 + i];
+        }
         __syncthreads();
 #pragma unroll 2
         for (int j = wave; j < n; j += kMatchWaves) {
             uint32_t d = pen[j];
+            if constexpr (GATED) {
+                // one subtraction and one inclusive compare per axis; a NaN fails both
+                const bool in = fabsf(bxy[2 * j] - ax) <= a.radius_x && fabsf(bxy[2 * j + 1] - ay) <= a.radius_y;
+                d = in ? d : static_cast<uint32_t>(kInvalidPenalty);
+            }
 #pragma unroll
             for (int w = 0; w < NW; ++w) d += static_cast<uint32_t>(__popc(qw[w] ^ tile[j * NW + w]));
             const int di = static_cast<int>(d);
@@ -133,7 +159,10 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
 
 template <int NW>
 void launch_nw(const MatchArgs &a, unsigned blocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_brief_match<NW>, dim3(blocks), dim3(kMatchThreads), 0, s, a);
+    if (a.a_xy)
+        hipLaunchKernelGGL((k_brief_match<NW, true>), dim3(blocks), dim3(kMatchThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_brief_match<NW, false>), dim3(blocks), dim3(kMatchThreads), 0, s, a);
 }
 
 }  // namespace

@@ -25,6 +25,11 @@
 // keeps (best, index, second) for four rows over the columns congruent to l & 15; columns ascend within
 // a lane, and the final merge over the 16 lanes that share the rows is the lexicographic minimum of
 // (distance, index), which is the serial scan's rule for any partition of the indices (fd_match.hip).
+//
+// The GATED instances (fd_nn_match_guided) add the search window of fd_match.hip: a lane keeps the
+// positions of its four rows (8 registers), a tile's TB "b" positions go to LDS beside bnorm, and a pair
+// outside the window gets d = +inf where an invalid column already does, after the MFMA chain, which the
+// gate does not touch.
 #include "fd_device.h"
 #include "fd_kernels.h"
 
@@ -72,12 +77,16 @@ __global__ __launch_bounds__(256) void k_nn_norms(NnNormArgs a) {
 }
 
 // K: the instance's descriptor length (dim zero-padded up to it: fmaf(0, 0, acc) leaves acc unchanged);
-// TB: "b" rows per LDS tile (TB / 16 independent accumulators per wave).
-template <int K, int TB>
-__global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
+// TB: "b" rows per LDS tile (TB / 16 independent accumulators per wave); GATED: only "b" rows inside a
+// row's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y).
+// The gated instances ask for the ungated ones' 4 waves per SIMD (the LDS tile's limit): unasked, the
+// K = 256 one takes 132 registers and drops to 3.
+template <int K, int TB, bool GATED>
+__global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATED ? 4 : 1))) void k_nn_match(NnMatchArgs a) {
     constexpr int P = K + 4, NS = K / 4, NJ = TB / 16, C4 = K / 4;
     __shared__ __attribute__((aligned(16))) float tile[TB * P];
     __shared__ float bnorm[TB];
+    __shared__ __attribute__((aligned(8))) float bxy[GATED ? 2 * TB : 2];
     const int tiles = (a.a_stride + kNnRows - 1) / kNnRows;
     const int f = static_cast<int>(blockIdx.x) / tiles;
     const int q0 = (static_cast<int>(blockIdx.x) - f * tiles) * kNnRows;
@@ -102,10 +111,16 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
     }
     float an[4], best[4], second[4];
     int bidx[4];
+    float ax[4], ay[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = q0 + 16 * wave + 4 * g + r;
         an[r] = row < na ? a.a_norm[static_cast<int64_t>(f) * a.a_stride + row] : inf;
+        if constexpr (GATED) {
+            const float *ap = a.a_xy + (static_cast<int64_t>(f) * a.a_stride + min(row, na - 1)) * 2;
+            ax[r] = ap[0];
+            ay[r] = ap[1];
+        }
         best[r] = inf;
         second[r] = inf;
         bidx[r] = -1;
@@ -113,6 +128,7 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
 
     const float *bf = a.b_desc + static_cast<int64_t>(f) * a.b_stride * a.dim;
     const float *bnf = a.b_norm + static_cast<int64_t>(f) * a.b_stride;
+    const float *bpf = GATED ? a.b_xy + static_cast<int64_t>(f) * a.b_stride * 2 : nullptr;
     for (int t0 = 0; t0 < nb; t0 += TB) {
         const int n = min(TB, nb - t0);
         __syncthreads();  // every wave is done with the previous tile
@@ -124,6 +140,9 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
         }
         if (static_cast<int>(threadIdx.x) < TB)
             bnorm[threadIdx.x] = static_cast<int>(threadIdx.x) < n ? bnf[t0 + threadIdx.x] : inf;
+        if constexpr (GATED) {  // (positions past the fill stay stale: their norm is +inf)
+            if (static_cast<int>(threadIdx.x) < 2 * n) bxy[threadIdx.x] = bpf[static_cast<int64_t>(t0) * 2 + threadIdx.x];
+        }
         __syncthreads();
         f4 acc[NJ];
 #pragma unroll
@@ -141,10 +160,20 @@ __global__ __launch_bounds__(kNnThreads) void k_nn_match(NnMatchArgs a) {
             const float bn = bnorm[16 * j + c];
             const bool ok = bn < inf;
             const int col = t0 + 16 * j + c;
+            float bx = 0.0f, by = 0.0f;
+            if constexpr (GATED) {
+                bx = bxy[2 * (16 * j + c)];
+                by = bxy[2 * (16 * j + c) + 1];
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float d = fmaxf(0.0f, (an[r] + bn) - 2.0f * acc[j][r]);
                 d = ok ? d : inf;
+                if constexpr (GATED) {
+                    // one subtraction and one inclusive compare per axis; a NaN fails both
+                    const bool in = fabsf(bx - ax[r]) <= a.radius_x && fabsf(by - ay[r]) <= a.radius_y;
+                    d = in ? d : inf;
+                }
                 // the serial scan: a new best moves the old best to second, else d may lower second;
                 // a NaN compares false both times
                 const bool lt = d < best[r];
@@ -227,10 +256,17 @@ hipError_t launch_nn_match(NnMatchArgs a, hipStream_t s) {
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     a.b_vec = aligned16(a.b_desc);
     const unsigned g = static_cast<unsigned>(blocks);
-    if (a.dim <= 128)
-        hipLaunchKernelGGL((k_nn_match<128, 64>), dim3(g), dim3(kNnThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_nn_match<256, 32>), dim3(g), dim3(kNnThreads), 0, s, a);
+    if (a.dim <= 128) {
+        if (a.a_xy)
+            hipLaunchKernelGGL((k_nn_match<128, 64, true>), dim3(g), dim3(kNnThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_nn_match<128, 64, false>), dim3(g), dim3(kNnThreads), 0, s, a);
+    } else {
+        if (a.a_xy)
+            hipLaunchKernelGGL((k_nn_match<256, 32, true>), dim3(g), dim3(kNnThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_nn_match<256, 32, false>), dim3(g), dim3(kNnThreads), 0, s, a);
+    }
     return hipGetLastError();
 }
 

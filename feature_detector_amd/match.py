@@ -4,6 +4,9 @@ squared L2 distance of NN float descriptors (fd_nn_match).
 An MI355X extension (the reference has no matcher): the stage after detect_points -> brief_compute, on
 the same [batch][stride] layouts, so a detect -> describe -> match chain stays on the GPU; nn_match is
 the same stage after nn_descriptors / nn_select_list. The semantics (validity, ties, the three acceptance tests) are in include/fd_hip.h.
+
+Both take an optional search window (q_xy, t_xy, radius): guided matching over fd_brief_match_guided /
+fd_nn_match_guided, where a train keypoint is a candidate of a query only within radius pixels of it.
 """
 from __future__ import annotations
 
@@ -13,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_match_opts, fd_nn_match_opts
+from ._lib import fd_match_gate, fd_match_opts, fd_nn_match_opts
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
 
@@ -28,6 +31,44 @@ def _ptr(x):
     if x is None:
         return None
     return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def _guided(q_xy, t_xy, radius) -> bool:
+    """Whether the call is the guided one: all three given; none given is the unguided call."""
+    given = [x is not None for x in (q_xy, t_xy, radius)]
+    if any(given) and not all(given):
+        raise ValueError("guided matching needs q_xy, t_xy and radius together")
+    return all(given)
+
+
+def _gate(q_xy, t_xy, radius, on_dev, b, sq, st):
+    """The guided call's (gate, q_xy, t_xy), or None for the unguided call."""
+    if not _guided(q_xy, t_xy, radius):
+        return None
+    try:
+        rx, ry = (float(r) for r in radius)
+    except TypeError:
+        rx = ry = float(radius)
+    sides = []
+    for xy, s, name in ((q_xy, sq, "q"), (t_xy, st, "t")):
+        if _is_torch_device_tensor(xy) != on_dev:
+            raise ValueError(f"{name}_xy must be on the side (host / device) of the descriptors")
+        if on_dev:
+            import torch
+
+            if xy.dtype != torch.float32:
+                raise TypeError(f"{name}_xy must be float32")
+            p = xy.contiguous()
+        else:
+            p = np.asarray(xy)
+            if p.dtype != np.float32:
+                raise TypeError(f"{name}_xy must be float32")
+            p = np.ascontiguousarray(p)
+        shape = tuple(int(d) for d in p.shape)
+        if shape != (b, s, 2) and not (b == 1 and shape == (s, 2)):
+            raise ValueError(f"{name}_xy must be [{b}, {s}, 2]" + (f" or [{s}, 2]" if b == 1 else ""))
+        sides.append(p)
+    return fd_match_gate(rx, ry), sides[0], sides[1]
 
 
 def _host_side(bits, valid, counts, nw, name):
@@ -63,7 +104,7 @@ def _device_side(bits, valid, counts, nw, name):
 
 def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_valid=None, length: int = 256,
                 max_distance: int = -1, max_ratio: float = 0.0, cross_check: bool = False, out=None,
-                ctx: Context | None = None) -> MatchResult:
+                ctx: Context | None = None, q_xy=None, t_xy=None, radius=None) -> MatchResult:
     """fd_brief_match for a batch: frame b of the query set against frame b of the train set.
 
     q_bits / t_bits: int32 or uint32 words [B, S, ceil(length/32)] or [S, words] (batch 1), as
@@ -73,7 +114,13 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     idx and dist are -1. Device path only: out = preallocated contiguous int32 tensors (idx [B, Sq],
     dist [B, Sq, 2], counts [B]); slots >= q_counts[b] then keep their contents and the call is kernels
     only (graph-capturable once a first call of the shape has run).
+
+    Guided matching (fd_brief_match_guided): q_xy / t_xy float32 positions [B, S, 2] (or [S, 2] for batch
+    1) on the descriptors' side, as detect_points leaves them, and radius, a float or an (rx, ry) pair:
+    train entry j is a candidate of query i only if |t_xy[j] - q_xy[i]| <= radius on both axes. Give all
+    three or none.
     """
+    _guided(q_xy, t_xy, radius)
     ctx = _resolve_ctx(ctx, q_bits, t_bits)
     nw = (int(length) + 31) // 32 if 1 <= int(length) <= 256 else 0
     opts = fd_match_opts(int(length), int(max_distance), float(max_ratio), 1 if cross_check else 0)
@@ -87,6 +134,7 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     tw, tv, tc, tb, st = side(t_bits, t_valid, t_counts, nw, "t")
     if tb != b:
         raise ValueError("q_bits and t_bits must have the same batch")
+    gate = _gate(q_xy, t_xy, radius, on_dev, b, sq, st)
     if on_dev:
         import torch
 
@@ -106,8 +154,13 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
         dist = np.full((b, sq, 2), -1, np.int32)
         counts = np.zeros((b,), np.int32)
     _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_brief_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qw), _ptr(qv), _ptr(qc), sq, _ptr(tw), _ptr(tv),
-                                    _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    if gate is None:
+        rc = _lib.load().fd_brief_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qw), _ptr(qv), _ptr(qc), sq, _ptr(tw),
+                                        _ptr(tv), _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    else:
+        rc = _lib.load().fd_brief_match_guided(ctx.ptr, b, ctypes.byref(opts), ctypes.byref(gate[0]), _ptr(qw), _ptr(qv),
+                                               _ptr(qc), sq, _ptr(gate[1]), _ptr(tw), _ptr(tv), _ptr(tc), st,
+                                               _ptr(gate[2]), _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return MatchResult(idx, dist, counts)
 
@@ -141,15 +194,18 @@ def _float_side(desc, valid, counts, on_dev, name):
 
 
 def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid=None, max_distance: float = -1.0,
-             max_ratio: float = 0.0, cross_check: bool = False, out=None, ctx: Context | None = None) -> MatchResult:
+             max_ratio: float = 0.0, cross_check: bool = False, out=None, ctx: Context | None = None, q_xy=None,
+             t_xy=None, radius=None) -> MatchResult:
     """fd_nn_match for a batch: frame b of the query set against frame b of the train set, squared L2.
 
     q_desc / t_desc: float32 [B, S, dim] or [S, dim] (batch 1), as nn_descriptors / nn_select_list return
     them; dim is the last axis (a multiple of 4, 4..256). *_counts, *_valid, host / device inputs and
     out= are as in brief_match, except that dist (and out's dist tensor) is float32 [B, Sq, 2]: squared
     distances, -1.0 where absent. max_distance bounds the squared distance; max_ratio is Lowe's ratio of
-    distances (applied squared to the squared distances).
+    distances (applied squared to the squared distances). q_xy, t_xy and radius give the guided call
+    (fd_nn_match_guided), as in brief_match.
     """
+    _guided(q_xy, t_xy, radius)
     ctx = _resolve_ctx(ctx, q_desc, t_desc)
     on_dev = _is_torch_device_tensor(q_desc)
     if on_dev != _is_torch_device_tensor(t_desc):
@@ -162,6 +218,7 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
     if int(td.shape[2]) != dim:
         raise ValueError("q_desc and t_desc must have the same dim")
     opts = fd_nn_match_opts(dim, float(max_distance), float(max_ratio), 1 if cross_check else 0)
+    gate = _gate(q_xy, t_xy, radius, on_dev, b, sq, st)
     if on_dev:
         import torch
 
@@ -181,7 +238,12 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
         dist = np.full((b, sq, 2), -1.0, np.float32)
         counts = np.zeros((b,), np.int32)
     _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_nn_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qd), _ptr(qv), _ptr(qc), sq, _ptr(td), _ptr(tv),
-                                 _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    if gate is None:
+        rc = _lib.load().fd_nn_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qd), _ptr(qv), _ptr(qc), sq, _ptr(td), _ptr(tv),
+                                     _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
+    else:
+        rc = _lib.load().fd_nn_match_guided(ctx.ptr, b, ctypes.byref(opts), ctypes.byref(gate[0]), _ptr(qd), _ptr(qv),
+                                            _ptr(qc), sq, _ptr(gate[1]), _ptr(td), _ptr(tv), _ptr(tc), st, _ptr(gate[2]),
+                                            _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return MatchResult(idx, dist, counts)

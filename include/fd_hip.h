@@ -396,6 +396,52 @@ int fd_nn_match(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts,
                 const float *t_desc, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
                 int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
 
+/* ---- Guided (position-gated) matching: a search window for both matchers (MI355X extension) --------- */
+typedef struct fd_match_gate {
+    float radius_x; /* half-width of the window in pixels: finite, >= 0 */
+    float radius_y; /* half-height */
+} fd_match_gate;
+
+/*
+ * fd_brief_match_guided / fd_nn_match_guided -- fd_brief_match / fd_nn_match with a search window, the
+ * frame-to-frame tracker's form: a train keypoint is a candidate of a query only if it lies within a few
+ * pixels of where the query is expected.
+ * q_xy / t_xy: positions float [batch][stride][2], stored (x, y): what fd_points_detect / fd_nn_select
+ * write, with the stride and slot order of that side's descriptor arrays. Query positions may be
+ * predictions (the last position plus a motion model); they need not lie inside the frame or be integers.
+ * The gate: train entry j is a candidate of query i iff both
+ *   fabsf(t_xy[j].x - q_xy[i].x) <= gate->radius_x
+ *   fabsf(t_xy[j].y - q_xy[i].y) <= gate->radius_y
+ * hold, each one float subtraction (one rounding) and one inclusive compare. A NaN on either side makes a
+ * compare false, so that pair is never a candidate (inf - inf is NaN and fails the same way).
+ * fabsf(a - b) has the bits of fabsf(b - a): the gate is symmetric, so the cross-check stays decided on
+ * the pairs of the forward search.
+ * Everything the unguided entry defines over "valid train descriptors" is defined here over "valid train
+ * descriptors inside this query's window", and nothing else changes: the best distance with the lowest
+ * train index on ties; the second distance (the smallest distance to another candidate in the window; -1
+ * when the window holds fewer than two, and the ratio test is then skipped); an empty window gives
+ * out_idx -1 and both distances -1; the cross-check's reverse search takes a train entry's best query
+ * over the valid queries whose window contains it, lowest query index on ties. The distance definition,
+ * max_distance, the ratio formulas, out_counts, the unwritten slots >= q_counts[b], the ignored bits
+ * 25..31 of counts, the zero-stride cases, host staging against device pointers and graph capture (once
+ * a first call of the shape has sized the workspace) are those of the unguided entries. With finite
+ * positions and both radii 3.0e38f every output equals the unguided call's.
+ * FD_ERR_INVALID: whatever the unguided entry rejects; gate, q_xy or t_xy NULL; a radius that is
+ * negative, NaN or infinite.
+ */
+int fd_brief_match_guided(fd_ctx *ctx, int batch, const fd_match_opts *opts, const fd_match_gate *gate,
+                          const uint32_t *q_bits, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                          const float *q_xy,
+                          const uint32_t *t_bits, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                          const float *t_xy,
+                          int32_t *out_idx, int32_t *out_dist, int32_t *out_counts, int io_on_device);
+int fd_nn_match_guided(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts, const fd_match_gate *gate,
+                       const float *q_desc, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                       const float *q_xy,
+                       const float *t_desc, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                       const float *t_xy,
+                       int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

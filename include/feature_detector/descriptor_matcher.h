@@ -4,7 +4,9 @@
 // MI355X extension: the reference has no matcher (its demos stop at the descriptors). The semantics are
 // those of fd_brief_match (include/fd_hip.h): equal distances go to the lowest train index, an invalid
 // descriptor is neither matched nor a candidate, and a best match is reported only if it passes the
-// enabled tests of Options.
+// enabled tests of Options. MatchGuided adds the tracker's search window (fd_brief_match_guided): a train
+// descriptor is a candidate of a query only if its keypoint lies within (radius_x, radius_y) pixels of the
+// query's.
 #ifndef FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
 #define FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
 
@@ -43,6 +45,16 @@ public:
                std::vector<int32_t> *distance = nullptr, const std::vector<uint8_t> *query_valid = nullptr,
                const std::vector<uint8_t> *train_valid = nullptr);
 
+    // Match within a search window: train[j] is a candidate of query[i] only if
+    // |train_uv[j].x - query_uv[i].x| <= radius_x and |train_uv[j].y - query_uv[i].y| <= radius_y (float,
+    // inclusive; a NaN position never matches). query_uv / train_uv: one position per descriptor, as
+    // the detector returned them or as a motion model predicts them. Outputs and the return value are
+    // Match's; also false for position vectors of the wrong size or a radius that is negative or not finite.
+    bool MatchGuided(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                     const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, float radius_x, float radius_y,
+                     std::vector<int32_t> &train_index, std::vector<int32_t> *distance = nullptr,
+                     const std::vector<uint8_t> *query_valid = nullptr, const std::vector<uint8_t> *train_valid = nullptr);
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -54,6 +66,9 @@ public:
 private:
     fd_ctx *Context();
     bool Fail(const std::string &what);
+    bool Run(const std::vector<BriefType> &query, const std::vector<BriefType> &train, const std::vector<Vec2> *query_uv,
+             const std::vector<Vec2> *train_uv, float radius_x, float radius_y, std::vector<int32_t> &train_index,
+             std::vector<int32_t> *distance, const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid);
 
 private:
     Options options_;
@@ -92,6 +107,13 @@ public:
                std::vector<int32_t> &train_index, std::vector<float> *distance = nullptr,
                const std::vector<uint8_t> *query_valid = nullptr, const std::vector<uint8_t> *train_valid = nullptr);
 
+    // Match within a search window (fd_nn_match_guided), as BriefMatcher::MatchGuided: query_xy / train_xy
+    // are n_query / n_train rows of (x, y) floats, row i the keypoint of descriptor row i.
+    bool MatchGuided(const float *query, int32_t n_query, const float *query_xy, const float *train, int32_t n_train,
+                     const float *train_xy, int32_t dim, float radius_x, float radius_y, std::vector<int32_t> &train_index,
+                     std::vector<float> *distance = nullptr, const std::vector<uint8_t> *query_valid = nullptr,
+                     const std::vector<uint8_t> *train_valid = nullptr);
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -103,6 +125,10 @@ public:
 private:
     fd_ctx *Context();
     bool Fail(const std::string &what);
+    bool Run(const float *query, int32_t n_query, const float *query_xy, const float *train, int32_t n_train,
+             const float *train_xy, int32_t dim, bool guided, float radius_x, float radius_y,
+             std::vector<int32_t> &train_index, std::vector<float> *distance, const std::vector<uint8_t> *query_valid,
+             const std::vector<uint8_t> *train_valid);
 
 private:
     Options options_;
