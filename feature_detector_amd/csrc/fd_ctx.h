@@ -72,6 +72,9 @@ struct fd_ctx {
     fdrt::DevBuf m_norm;
     // the guided matchers' host-pointer calls stage both sets' positions ([batch][stride][2]) here
     fdrt::DevBuf m_qxy, m_txy;
+    // fd_pyr_build's host-output pyramid; fd_flow_lk: the backward pass's results ([batch][stride] positions
+    // and status) and the staging of host-pointer calls (inputs, outputs)
+    fdrt::DevBuf f_pyr, f_bxy, f_bst, f_xy, f_valid, f_counts, f_guess, f_oxy, f_ost, f_oerr, f_ocnt;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

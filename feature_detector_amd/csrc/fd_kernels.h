@@ -374,7 +374,44 @@ struct NnDescArgs {
     float *out;  // [batch][stride][channels]
 };
 
+// Pyramidal Lucas-Kanade tracker (fd_flow.hip): the template comes from pyramid `tmpl`, the search runs in
+// `srch` (the backward pass swaps them).
+constexpr int kPyrMaxLevels = 6;  // FD_PYR_MAX_LEVELS
+struct FlowArgs {
+    const uint8_t *tmpl, *srch;  // packed pyramids (fd_pyr_layout)
+    int64_t off[kPyrMaxLevels];  // byte offset of every level (fd_pyr_layout without its last entry)
+    int batch, rows, cols, levels, stride;
+    int r, max_iters;            // half window 1..10
+    float eps2;                  // epsilon * epsilon (float)
+    float max_error;             // < 0: off
+    double tau;                  // (double)min_eigen * 1024.0 * n
+    const float *xy;             // [batch][stride][2] (x, y)
+    const uint8_t *valid;        // [batch][stride] or null (= all valid)
+    int valid_is_status;         // valid holds a status array: only slots equal to 1 are tracked
+    const int32_t *counts;       // [batch] or null (= stride); bits 25..31 ignored
+    const float *guess;          // as xy, or null (= xy)
+    float *out_xy;               // [batch][stride][2]
+    uint8_t *out_status;         // [batch][stride]
+    float *out_err;              // [batch][stride] or null
+};
+
+// k_flow_finish: the forward-backward test (back_status non-null) and the per-frame counts.
+struct FlowFinishArgs {
+    const float *xy;             // the forward pass's input positions
+    uint8_t *status;             // forward status, updated in place (5: failed the round trip)
+    const float *back_xy;        // backward result, or null with back_status
+    const uint8_t *back_status;
+    float fb2;                   // fb_max_dist * fb_max_dist (float)
+    const int32_t *counts;
+    int batch, stride;
+    int32_t *out_counts;         // [batch] += tracked slots (zeroed by the caller), or null
+};
+
 // Launchers (stream-ordered, no allocation, no synchronisation: graph-capturable).
+// one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
+hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
+hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);
+hipError_t launch_flow_finish(const FlowFinishArgs &a, hipStream_t s);
 hipError_t launch_mask_boxes(const float *prior_xy, const int32_t *prior_frame, int n_prior, int dist, int rows,
                              int cols, uint32_t *mask, int mask_wpr, hipStream_t s);
 hipError_t launch_fast_mask_scan(const uint32_t *mask, int mask_wpr, int batch, int rows, int cols, int32_t *row_base,

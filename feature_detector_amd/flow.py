@@ -1,0 +1,186 @@
+"""Image pyramids and pyramidal Lucas-Kanade feature tracking over the C ABI (fd_pyr_build, fd_flow_lk).
+
+An MI355X extension (the reference has no tracker): the step before detect_points in a VIO / SLAM front
+end, on the [batch][stride] layouts detect_points writes, so detect -> track -> (mask survivors) -> detect
+stays on the GPU. The arithmetic (exact integer window sums, one 2 x 2 solve in double) is in
+include/fd_hip.h.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import fd_flow_opts
+from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+
+
+def pyramid_layout(batch: int, rows: int, cols: int, levels: int) -> list[int]:
+    """fd_pyr_layout: byte offsets of the levels in the packed pyramid; the last entry is the total size."""
+    off = (ctypes.c_int64 * (max(int(levels), 0) + 1))()
+    rc = _lib.load().fd_pyr_layout(int(batch), int(rows), int(cols), int(levels), off)
+    if rc != _lib.FD_OK:
+        raise _lib.FdError(rc, "fd_pyr_layout: need batch, rows, cols >= 1, levels in [1, 6] and a top level that keeps a pixel")
+    return list(off)
+
+
+@dataclass
+class Pyramid:
+    data: object   # packed uint8 buffer (fd_pyr_layout): a torch device tensor, or a numpy array (host frames)
+    batch: int
+    rows: int
+    cols: int
+    levels: int
+    offsets: list  # byte offset per level, then the total size
+
+    def level(self, l: int):
+        """Level l as a [batch, rows >> l, cols >> l] view of the packed buffer."""
+        r, c = self.rows >> l, self.cols >> l
+        return self.data[self.offsets[l]:self.offsets[l] + self.batch * r * c].reshape(self.batch, r, c)
+
+
+def _ptr(x):
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_out: bool | None = None) -> Pyramid:
+    """fd_pyr_build for a batch of uint8 frames [B, rows, cols] (or [rows, cols]): level 0 is the frames,
+    every further level the rounded 2 x 2 box mean of the one below it.
+
+    Torch device frames give a device pyramid, asynchronous on torch's current stream (kernels and one
+    copy: graph-capturable). Host (numpy) frames give a numpy pyramid, or with device_out=True a device
+    pyramid (what track_lk builds from host frames).
+    """
+    ptr, on_dev, b, r, c, keep = _frames(frames)
+    ctx = _resolve_ctx(ctx, frames)
+    off = pyramid_layout(b, r, c, levels)
+    dev_out = bool(on_dev) if device_out is None else bool(device_out)
+    if on_dev and not dev_out:
+        raise ValueError("device frames give a device pyramid")
+    if dev_out:
+        import torch
+
+        data = torch.empty((off[-1],), dtype=torch.uint8, device=keep.device if on_dev else f"cuda:{ctx.device}")
+    else:
+        data = np.zeros((off[-1],), np.uint8)
+    _bind_stream(ctx, bool(on_dev))
+    rc = _lib.load().fd_pyr_build(ctx.ptr, ctypes.c_void_p(ptr), on_dev, b, r, c, int(levels), _ptr(data), 1 if dev_out else 0)
+    _lib.check(ctx.ptr, rc)
+    return Pyramid(data, b, r, c, int(levels), off)
+
+
+@dataclass
+class FlowResult:
+    xy: object      # float32 [B, S, 2]: tracked positions (x, y) in the next frame
+    status: object  # uint8 [B, S]: 1 = tracked, everything else lost (fd_flow_status)
+    err: object     # float32 [B, S]: mean absolute residual of the window, in intensity units
+    counts: object  # int32 [B]: tracked slots per frame
+
+
+def _device_pyramid(p, levels, ctx, name):
+    """A device Pyramid from a Pyramid (host ones are uploaded) or a frame batch."""
+    if isinstance(p, Pyramid):
+        if p.levels != int(levels):
+            raise ValueError(f"{name}: the pyramid has {p.levels} levels, the call asks for {levels}")
+        if _is_torch_device_tensor(p.data):
+            return p
+        import torch
+
+        return Pyramid(torch.from_numpy(p.data).to(f"cuda:{ctx.device}"), p.batch, p.rows, p.cols, p.levels, p.offsets)
+    return build_pyramid(p, levels, ctx=ctx, device_out=True)
+
+
+def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 3, half_window: int = 7,
+             max_iters: int = 30, epsilon: float = 0.01, min_eigen: float = 1e-3, fb_max_dist: float = -1,
+             max_error: float = -1, out=None, ctx: Context | None = None) -> FlowResult:
+    """fd_flow_lk: track the features xy of every frame of `prev` into the frame of `next` with the same index.
+
+    prev / next: uint8 frame batches [B, rows, cols] (or [rows, cols]) or Pyramids (build_pyramid with the
+    same `levels`), so a tracking loop builds each frame's pyramid once. xy: float32 [B, S, 2] (or [S, 2]
+    for batch 1), (x, y) as detect_points writes them; counts int32 [B] (None = S each; detect_points'
+    device counts pass as they are); valid uint8 [B, S] (None = all valid); guess as xy: the expected
+    positions in `next` (None = xy).
+
+    Host (numpy) xy gives numpy outputs; torch device xy gives torch outputs, asynchronous on torch's
+    current stream. Slots the call does not write (>= counts[b]) are 0. Device path only: out =
+    preallocated contiguous tensors (xy float32 [B, S, 2], status uint8 [B, S], err float32 [B, S], counts
+    int32 [B]); unwritten slots then keep their contents, and with Pyramid inputs the call is kernels only
+    (graph-capturable once a first call of the shape has run).
+
+    The defaults (3 levels, a 15 x 15 window, 30 iterations, epsilon 0.01, min_eigen 1e-3) are the usual
+    conventions of pyramidal LK front ends, not values tuned for this library. fb_max_dist >= 0 turns the
+    forward-backward check on (a second pass), max_error >= 0 the residual test.
+    """
+    on_dev = _is_torch_device_tensor(xy)
+    ctx = _resolve_ctx(ctx, xy, prev.data if isinstance(prev, Pyramid) else prev,
+                       next.data if isinstance(next, Pyramid) else next)
+    if on_dev:
+        import torch
+
+        if xy.dtype != torch.float32:
+            raise TypeError("xy must be float32")
+        pxy = xy.contiguous()
+        if pxy.dim() == 2:
+            pxy = pxy.unsqueeze(0)
+    else:
+        pxy = np.asarray(xy)
+        if pxy.dtype != np.float32:
+            raise TypeError("xy must be float32")
+        pxy = np.ascontiguousarray(pxy)
+        if pxy.ndim == 2:
+            pxy = pxy[None]
+    if len(pxy.shape) != 3 or pxy.shape[2] != 2:
+        raise ValueError("xy must be [batch, S, 2] or [S, 2]")
+    b, s = int(pxy.shape[0]), int(pxy.shape[1])
+    pp, pn = _device_pyramid(prev, levels, ctx, "prev"), _device_pyramid(next, levels, ctx, "next")
+    if (pp.batch, pp.rows, pp.cols) != (pn.batch, pn.rows, pn.cols):
+        raise ValueError("prev and next must have the same batch, rows and cols")
+    if pp.batch != b:
+        raise ValueError("xy and the frames must have the same batch")
+    if guess is not None and _is_torch_device_tensor(guess) != on_dev:
+        raise ValueError("guess must be on the side (host / device) of xy")
+    if on_dev:
+        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
+        cn = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
+        g = None
+        if guess is not None:
+            if guess.dtype != torch.float32:
+                raise TypeError("guess must be float32")
+            g = guess.contiguous().reshape(b, s, 2)
+        if out is not None:
+            oxy, ost, oerr, ocnt = out
+            for t, shape, dt in ((oxy, (b, s, 2), torch.float32), (ost, (b, s), torch.uint8), (oerr, (b, s), torch.float32),
+                                 (ocnt, (b,), torch.int32)):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                    raise ValueError(f"out must be contiguous tensors: float32 {(b, s, 2)}, uint8 {(b, s)}, "
+                                     f"float32 {(b, s)}, int32 {(b,)}")
+        else:
+            oxy = torch.zeros((b, s, 2), dtype=torch.float32, device=pxy.device)
+            ost = torch.zeros((b, s), dtype=torch.uint8, device=pxy.device)
+            oerr = torch.zeros((b, s), dtype=torch.float32, device=pxy.device)
+            ocnt = torch.zeros((b,), dtype=torch.int32, device=pxy.device)
+    else:
+        if out is not None:
+            raise ValueError("out= is for device tensors")
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
+        cn = None if counts is None else np.ascontiguousarray(np.asarray(counts).astype(np.int32).reshape(b))
+        g = None
+        if guess is not None:
+            g = np.asarray(guess)
+            if g.dtype != np.float32:
+                raise TypeError("guess must be float32")
+            g = np.ascontiguousarray(g).reshape(b, s, 2)
+        oxy, ost = np.zeros((b, s, 2), np.float32), np.zeros((b, s), np.uint8)
+        oerr, ocnt = np.zeros((b, s), np.float32), np.zeros((b,), np.int32)
+    opts = fd_flow_opts(int(half_window), int(max_iters), float(epsilon), float(min_eigen), float(fb_max_dist),
+                        float(max_error))
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_flow_lk(ctx.ptr, b, pp.rows, pp.cols, int(levels), ctypes.byref(opts), _ptr(pp.data), _ptr(pn.data),
+                                _ptr(pxy), _ptr(v), _ptr(cn), s, _ptr(g), _ptr(oxy), _ptr(ost), _ptr(oerr), _ptr(ocnt),
+                                1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return FlowResult(oxy, ost, oerr, ocnt)

@@ -442,6 +442,117 @@ int fd_nn_match_guided(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts, con
                        const float *t_xy,
                        int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
 
+/* ---- Image pyramid and pyramidal Lucas-Kanade tracking (MI355X extension) --------------------------- */
+#define FD_PYR_MAX_LEVELS 6
+
+/*
+ * fd_pyr_layout -- the packed pyramid of a batch: [level][batch][rows_l][cols_l] uint8 with
+ * rows_l = rows >> l, cols_l = cols >> l, every level starting at a multiple of 256 bytes. offsets[l] is
+ * the byte offset of level l (offsets[0] = 0) and offsets[levels] the size of the whole (the next multiple
+ * of 256 after the last level). A host computation: no context, no GPU.
+ * FD_ERR_INVALID: offsets NULL, batch < 1, levels outside 1..6, or a top level with a zero dimension.
+ */
+int fd_pyr_layout(int batch, int rows, int cols, int levels, int64_t *offsets /* [levels + 1] */);
+
+/*
+ * fd_pyr_build -- the box pyramid of a batch of frames [batch][rows][cols] into pyr (fd_pyr_layout).
+ * Level 0 is a copy of the frames; pixel (y, x) of level l + 1 is
+ *   (I(2y, 2x) + I(2y, 2x + 1) + I(2y + 1, 2x) + I(2y + 1, 2x + 1) + 2) >> 2
+ * of level l (an odd last row or column is dropped). Padding bytes between levels are not written.
+ * frames / pyr are device pointers when frames_on_device / pyr_on_device (pyr then 256-byte aligned, as
+ * device allocations are); with both the call is copies and kernels on the context's stream only
+ * (graph-capturable). A host pyr is built in the context's workspace and copied back, complete on return.
+ * FD_ERR_INVALID: what fd_pyr_layout rejects; ctx, frames or pyr NULL; a misaligned device pyr.
+ */
+int fd_pyr_build(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols, int levels,
+                 uint8_t *pyr, int pyr_on_device);
+
+typedef struct fd_flow_opts {
+    int32_t half_window; /* r in 1..10: the window is (2r + 1)^2 = n pixels */
+    int32_t max_iters;   /* 1..100 iterations per level */
+    float epsilon;       /* > 0: a level stops after a step of length <= epsilon (level pixels) */
+    float min_eigen;     /* >= 0: smallest accepted minimum eigenvalue of the window's mean gradient matrix,
+                            central-difference gradients in intensity units per pixel (Gx, Gy are 32 times
+                            those, hence the 1024 of the level test) */
+    float fb_max_dist;   /* forward-backward check: largest round-trip distance in pixels; < 0: off */
+    float max_error;     /* largest mean absolute residual (intensity units) of a track; < 0: off */
+} fd_flow_opts;
+
+/* out_status values of fd_flow_lk: 1 is the only "tracked" */
+enum fd_flow_status {
+    FD_FLOW_INVALID = 0,  /* valid flag 0 */
+    FD_FLOW_TRACKED = 1,
+    FD_FLOW_OUTSIDE = 2,  /* xy not finite or outside the frame, or the track left the frame */
+    FD_FLOW_FLAT = 3,     /* the level-0 gradient matrix fails the level test */
+    FD_FLOW_STEP = 4,     /* a non-finite step */
+    FD_FLOW_FB = 5,       /* failed the forward-backward check */
+    FD_FLOW_ERROR = 6     /* out_err above max_error */
+};
+
+/*
+ * fd_flow_lk -- pyramidal Lucas-Kanade (inverse-compositional: the gradients come from the template
+ * frame) for the features xy of every frame of a batch, from the pyramids of the previous and the next
+ * frames (fd_pyr_build with the same batch, rows, cols, levels; device pointers always). The reference
+ * has no tracker: the contract is this text, a definite arithmetic sequence in which every window sum is
+ * an exact integer (any summation order gives it) and only the 2 x 2 solve is floating point.
+ *
+ * xy: float [batch][stride][2], stored (x, y): what fd_points_detect / fd_nn_select write. counts int32
+ * [batch] (NULL: stride each; bits 25..31 ignored), valid uint8 [batch][stride] (NULL: all valid),
+ * guess_xy as xy: the expected positions in the next frame (NULL: xy itself).
+ *
+ * Raw bilinear sum. For a float position (x, y) on a level image I (rows_l x cols_l) and integer offsets
+ * (u, v): ix = (int)floorf(x), ax = x - floorf(x) (exact), qx = (int)(ax * 1024.0f) (truncated), y
+ * likewise, and
+ *   S(u, v) = (1024 - qx)(1024 - qy) I(cy(iy + v), cx(ix + u))     + qx (1024 - qy) I(cy(iy + v), cx(ix + u + 1))
+ *           + (1024 - qx) qy         I(cy(iy + v + 1), cx(ix + u)) + qx qy          I(cy(iy + v + 1), cx(ix + u + 1))
+ * with cx / cy clamping to [0, cols_l - 1] / [0, rows_l - 1]: no read is undefined. S < 2^28.
+ *
+ * Per feature slot below counts[b]:
+ *   valid 0: status 0, out_xy = xy, out_err not written.
+ *   xy not finite or outside [0, cols - 1] x [0, rows - 1]: status 2.
+ *   L = levels - 1; in float d = (guess - xy) * 2^-L per axis (0 without a guess). For l = L .. 0:
+ *   1. p = xy * 2^-l (exact; the quarter-pixel offset of the box pyramid is ignored, as OpenCV ignores its own).
+ *   2. Template from the previous pyramid's level l at p, for u, v in [-r, r] (arithmetic shifts):
+ *        Iq = (S(u, v) + 2^14) >> 15   (intensity * 32)
+ *        Gx = (S(u + 1, v) - S(u - 1, v) + 2^15) >> 16,  Gy = (S(u, v + 1) - S(u, v - 1) + 2^15) >> 16
+ *   3. A11 = sum Gx^2, A12 = sum Gx Gy, A22 = sum Gy^2: exact integers.
+ *   4. Level test, in double, every operation rounded once, no contraction:
+ *        tau = (double)min_eigen * 1024.0 * n; e11 = a11 - tau; e22 = a22 - tau; det = a11 * a22 - a12 * a12
+ *        usable iff det > 0 && e11 > 0 && e22 > 0 && e11 * e22 - a12 * a12 >= 0
+ *      (the minimum-eigenvalue test without a square root). An unusable level above 0 is skipped with d
+ *      carried down; an unusable level 0 gives status 3.
+ *   5. At most max_iters iterations: q = p + d (one float add per axis). In-frame test in level-0 units:
+ *      0 <= q.x * 2^l <= (float)(cols - 1) and the same for y (false on NaN); failing it gives status 2 at
+ *      any level. Jq = (S_next(u, v at q) + 2^14) >> 15 from the next pyramid's level l; D = Iq - Jq;
+ *      b1 = sum D Gx, b2 = sum D Gy, E = sum |D| (exact integers). In double
+ *        sx = (a22 * b1 - a12 * b2) / det,  sy = (a11 * b2 - a12 * b1) / det
+ *      then in float fx = (float)sx, fy = (float)sy; a non-finite fx or fy gives status 4; d = d + (fx, fy);
+ *      the level stops after the update when fx * fx + fy * fy <= epsilon * epsilon (float, every product
+ *      rounded).
+ *   6. If l > 0: d = d * 2.0f.
+ *   out_xy = xy + d; out_err = (float)((double)E / (32.0 * n)) with the E of the last iteration at level 0.
+ *   Running out of iterations is not a loss. max_error >= 0 && out_err > max_error: status 6.
+ * Forward-backward check (fb_max_dist >= 0), for the slots still at status 1: a second pass tracks out_xy
+ * from the next pyramid back into the previous one with the same options (max_error apart: it is not
+ * applied to the way back) and xy as the guess. A lost backward track gives status 5, and so does
+ * bx * bx + by * by > fb_max_dist * fb_max_dist with bx = back.x - xy.x, by = back.y - xy.y (float).
+ *
+ * Outputs: out_status uint8 (enum fd_flow_status; 1 = tracked, everything else lost), out_xy, out_err
+ * (NULL to skip), out_counts [batch] (NULL to skip): the status-1 slots below counts[b]. A slot lost
+ * inside the tracker (status 2, 3, 4) has out_xy = xy and out_err = -1; status 5 and 6 keep the forward
+ * track's values. Slots >= counts[b] are not written. stride 0: nothing but out_counts = 0.
+ * The feature arrays (xy, valid, counts, guess_xy and the outputs) are device pointers when io_on_device:
+ * the call is then asynchronous on the context's stream, and graph-capturable once a first call of the
+ * shape has sized the workspace (the backward pass's results; growing them under capture fails). Host
+ * pointers otherwise: staged through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, a pyramid, xy, out_xy or out_status NULL; batch < 1; a negative stride; rows,
+ * cols, levels that fd_pyr_layout rejects; an option outside its range above or not finite.
+ */
+int fd_flow_lk(fd_ctx *ctx, int batch, int rows, int cols, int levels, const fd_flow_opts *opts,
+               const uint8_t *prev_pyr, const uint8_t *next_pyr,
+               const float *xy, const uint8_t *valid, const int32_t *counts, int32_t stride, const float *guess_xy,
+               float *out_xy, uint8_t *out_status, float *out_err, int32_t *out_counts, int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

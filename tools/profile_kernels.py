@@ -9,6 +9,10 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
   --shape fastmatch  FAST (need 500, dist 15) + BRIEF-256 + fd_brief_match of frame i against frame i + 1 of
                      the batch (63 frame pairs, detect's device counts and BRIEF's valid flags in place), 10
                      calls (--cross-check: with the cross-check, two k_brief_match launches per call)
+  --shape fastflow   FAST (need 500, dist 15) on 64 frames of one blurred-noise scene, each moved by (-2, -1) px
+                     against the one before, fd_pyr_build (3 levels) of frames 0..62 and 1..63, and fd_flow_lk
+                     (r 7, the defaults) of frame i's keypoints into frame i + 1, 10 calls (--fb: with the
+                     forward-backward check, two k_flow_lk launches per call)
   --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
                      128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
                      baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
@@ -31,11 +35,12 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
 p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
+p.add_argument("--fb", action="store_true", help="fastflow: track with the forward-backward check")
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
@@ -127,6 +132,25 @@ elif a.shape == "fastmatch":  # configs[2]'s shape with need 500, then the match
         fd.brief_match(bits[:-1], bits[1:], res.counts[:-1], res.counts[1:], valid[:-1], valid[1:], max_distance=64,
                        max_ratio=0.9, cross_check=a.cross_check, out=out)
     print("matches per frame pair (mean):", float(out[2].float().mean()), "keypoints:", float((res.counts & 0x1FFFFFF).float().mean()))
+elif a.shape == "fastflow":  # detect -> pyramids -> track on consecutive frames of one moving scene
+    kind = "fast" + (" fb" if a.fb else "")
+    base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
+    base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)  # (the blur's contrast restored)
+    frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
+    out = None
+    for _ in range(a.calls or 10):
+        res = fd.detect_points("fast", frames, 500, 15, THR["fast"])
+        if out is None:
+            s = res.xy.shape[1]
+            out = (torch.empty((63, s, 2), dtype=torch.float32, device="cuda"), torch.empty((63, s), dtype=torch.uint8, device="cuda"),
+                   torch.empty((63, s), dtype=torch.float32, device="cuda"), torch.empty((63,), dtype=torch.int32, device="cuda"))
+        p0, p1 = fd.build_pyramid(frames[:-1], 3), fd.build_pyramid(frames[1:], 3)
+        fd.track_lk(p0, p1, res.xy[:-1], counts=res.counts[:-1], levels=3, half_window=7, fb_max_dist=1.0 if a.fb else -1.0,
+                    out=out)
+    n = (res.counts[:-1] & 0x1FFFFFF).float()
+    moved = (out[0] - res.xy[:-1])[out[1] == 1]
+    print("keypoints per frame (mean):", float(n.mean()), "tracked (mean):", float(out[3].float().mean()),
+          "median displacement of the tracked:", moved.median(0).values.tolist())
 elif a.shape == "nnmatch":
     kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
     B, S = 64, 240
