@@ -111,6 +111,27 @@ def test_oracle_matches_numpy_restatement(orc, sampler, length, half):
             assert np.array_equal(mom[k].view(np.uint32), np.array(em, np.float32).view(np.uint32)), k
 
 
+@pytest.mark.parametrize("sampler", [0, 1])
+@pytest.mark.parametrize("length,half", [(256, 19), (256, 20), (64, 30), (64, 31), (33, 32)])
+def test_oracle_matches_numpy_restatement_at_large_patches(orc, sampler, length, half):
+    """The patch sizes where k_brief changes its staging and its moment path (tests/test_gpu_brief_edges.py), on
+    a frame just large enough for the border 2 * half: both corners of the admissible square, a fractional
+    keypoint and one outside the border."""
+    mb = 2 * half
+    size = 2 * mb + 4
+    img = orc.make_frame("noise", 90 + half, size, size + 2)
+    uv = np.array([(mb, mb), (size + 2 - mb, size - mb), (mb + 1.25, mb + 2.5), (mb - 0.5, mb + 1)], np.float32)
+    bits, valid, mom = orc.brief(img, uv, length, half, sampler)
+    assert valid.tolist() == [1, 1, 1, 0]
+    pat = orc.brief_pattern()
+    for k, (x, y) in enumerate(uv):
+        eb, ev, em = numpy_brief(img, x, y, length, half, sampler, pat)
+        assert valid[k] == ev, k
+        assert np.array_equal(bits[k], eb), k
+        if em is not None:
+            assert np.array_equal(mom[k].view(np.uint32), np.array(em, np.float32).view(np.uint32)), k
+
+
 def test_border_flat_and_sampler_independent_moments(orc):
     img = orc.make_frame("checker", 5, 120, 160)
     uv = np.array([(18.9, 60), (19, 60), (141, 60), (141.5, 60), (80, 18), (80, 101), (80, 101.5), (80, 60)],

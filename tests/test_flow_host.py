@@ -4,6 +4,7 @@ import ctypes
 
 import numpy as np
 
+import flow_cases as C
 import flow_ref as R
 
 
@@ -62,6 +63,53 @@ def test_pyr_layout_offsets():
     for bad in ((0, 8, 8, 1), (1, 8, 8, 0), (1, 8, 8, 7), (1, 8, 40, 5), (1, 40, 8, 5), (1, 0, 8, 1)):
         assert L.fd_pyr_layout(*bad, off) == fd._lib.FD_ERR_INVALID
     assert L.fd_pyr_layout(1, 8, 8, 1, None) == fd._lib.FD_ERR_INVALID
+
+
+def test_half_windows_reach_every_round_count():
+    """k_flow_lk is instantiated per ROUNDS = ceil((2r + 1)^2 / 64): half_window 1..10 reach all seven, and 8
+    and 9 are the only ones that reach 5 and 6 (tests/test_gpu_flow_edges.py launches all ten)."""
+    got = {r: C.rounds(r) for r in range(1, 11)}
+    assert got == {1: 1, 2: 1, 3: 1, 4: 2, 5: 2, 6: 3, 7: 4, 8: 5, 9: 6, 10: 7}
+    assert set(got.values()) == set(range(1, 8))
+
+
+def test_saturated_frames_pass_the_32_bit_sums():
+    """The inputs of test_gpu_flow_edges.py::test_saturated_contrast have what they were built for: level-0
+    window sums that a 32-bit total would get wrong. sum gx*gx reaches 2^31 at half_window 8, 9 and 10 and
+    2^32 at 10; with the content moving by (-1, -1) the first iteration's b1 or b2 is below -2^31 (the
+    arithmetic shift of negative lane values and the signed recombination in wave_sum_i32)."""
+    prev, nxt = C.sat_frames()
+    assert set(np.unique(prev)) == {0, 255} and np.array_equal(nxt[0, :-1, :-1], prev[0, 1:, 1:])
+    xy = C.sat_features()[0]
+    assert xy.shape == (24, 2) and (xy == np.rint(xy)).all(1).sum() == 8
+    for r in (8, 9, 10):
+        sums = [C.level0_sums(prev[0], nxt[0], p, r) for p in xy]
+        a11, b = max(s[0] for s in sums), min(min(s[1], s[2]) for s in sums)
+        print(f"half_window {r}: largest sum gx*gx {a11:.4g}, most negative b {b:.4g}")
+        assert a11 >= 2 ** 31
+        assert b < 0 and -b >= 2 ** 31
+        if r == 10:
+            assert a11 >= 2 ** 32
+    # the sums are the tracker's own: at an integral feature d = 0 gives the first iteration of track_one
+    p = xy[0]
+    st = R.track_one([prev[0].astype(np.int64)], [nxt[0].astype(np.int64)], p, None, C.ROWS, C.COLS, 10, 1, 0.01, 1e-4, -1.0)
+    assert st[1] == 1 and not np.array_equal(st[0], p)
+
+
+def test_odd_frame_features_pass_the_coarse_levels_last_column():
+    """97 x 131 loses a column at every level (65, 32, 16 columns): a feature on the last column of level 0
+    lies beyond the last column of a coarser level, where the template patch is all clamped reads, and
+    level 0 of frame 1 starts at an odd byte offset."""
+    xy = C.odd_features()
+    assert xy.shape == (3, 20, 2)
+    rows, cols = C.ODD_ROWS, C.ODD_COLS
+    for p in ((cols - 1, rows - 1), (cols - 1, 40), (50, rows - 1), (cols - 1.25, rows - 1.5), (0, 0), (cols - 1, 0), (0, rows - 1)):
+        assert (xy[0] == np.array(p, np.float32)).all(1).any(), p
+    beyond = C.beyond_last_column(xy[0], cols, 4)
+    assert beyond and {l for _, l in beyond} >= {1, 2, 3} and all(l > 0 for _, l in beyond)
+    assert any(np.float32(p[1]) * np.float32(0.5) > (rows >> 1) - 1 for p in xy[0])
+    assert (rows * cols) % 2 == 1  # frame 1's level 0 starts at an odd byte
+    assert (rows >> 3, cols >> 3) == (12, 16)
 
 
 def test_null_context_is_rejected():
