@@ -12,40 +12,37 @@
 
 namespace feature_detector {
 
-BriefMatcher::~BriefMatcher() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
+namespace {
 
-void BriefMatcher::set_device(int device) {
-    if (ctx_ && device != device_) {
-        fd_ctx_destroy(ctx_);
-        ctx_ = nullptr;
-    }
-    device_ = device;
-}
-
-fd_ctx *BriefMatcher::Context() {
-    if (!ctx_) {
-        int dev = device_;
-        if (dev < 0) {
-            const char *e = std::getenv("FD_DEVICE");
-            dev = e ? std::atoi(e) : 0;
-        }
-        if (fd_ctx_create(dev, &ctx_) != FD_OK) {
-            ctx_ = nullptr;
-            Fail("fd_ctx_create failed (no MI355X visible?)");
-        }
-    }
-    return ctx_;
-}
-
-bool BriefMatcher::Fail(const std::string &what) {
-    error_ = what;
-    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
+// What both matchers do alike with their members (ctx_, device_, error_).
+bool FailWith(std::string &error, const std::string &what) {
+    error = what;
+    std::fprintf(stderr, "[feature_detector] %s\n", error.c_str());
     return false;
 }
 
-namespace {
+void SetDevice(fd_ctx *&ctx, int &device_member, int device) {
+    if (ctx && device != device_member) {
+        fd_ctx_destroy(ctx);
+        ctx = nullptr;
+    }
+    device_member = device;
+}
+
+// The context, created on first use (device < 0: FD_DEVICE, else device 0).
+fd_ctx *Acquire(fd_ctx *&ctx, int device, std::string &error) {
+    if (!ctx) {
+        if (device < 0) {
+            const char *e = std::getenv("FD_DEVICE");
+            device = e ? std::atoi(e) : 0;
+        }
+        if (fd_ctx_create(device, &ctx) != FD_OK) {
+            ctx = nullptr;
+            FailWith(error, "fd_ctx_create failed (no MI355X visible?)");
+        }
+    }
+    return ctx;
+}
 
 // std::vector<bool> descriptors -> [n][words] uint32, bit i = bit i % 32 of word i / 32 (fd_brief_compute's layout)
 bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<uint32_t> &words) {
@@ -72,6 +69,13 @@ std::vector<float> Flatten(const std::vector<Vec2> &uv) {
 bool BadRadius(float r) { return !std::isfinite(r) || r < 0.0f; }
 
 }  // namespace
+
+BriefMatcher::~BriefMatcher() {
+    if (ctx_) fd_ctx_destroy(ctx_);
+}
+void BriefMatcher::set_device(int device) { SetDevice(ctx_, device_, device); }
+fd_ctx *BriefMatcher::Context() { return Acquire(ctx_, device_, error_); }
+bool BriefMatcher::Fail(const std::string &what) { return FailWith(error_, what); }
 
 bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
                          std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
@@ -131,35 +135,9 @@ bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<Br
 NNDescriptorMatcher::~NNDescriptorMatcher() {
     if (ctx_) fd_ctx_destroy(ctx_);
 }
-
-void NNDescriptorMatcher::set_device(int device) {
-    if (ctx_ && device != device_) {
-        fd_ctx_destroy(ctx_);
-        ctx_ = nullptr;
-    }
-    device_ = device;
-}
-
-fd_ctx *NNDescriptorMatcher::Context() {
-    if (!ctx_) {
-        int dev = device_;
-        if (dev < 0) {
-            const char *e = std::getenv("FD_DEVICE");
-            dev = e ? std::atoi(e) : 0;
-        }
-        if (fd_ctx_create(dev, &ctx_) != FD_OK) {
-            ctx_ = nullptr;
-            Fail("fd_ctx_create failed (no MI355X visible?)");
-        }
-    }
-    return ctx_;
-}
-
-bool NNDescriptorMatcher::Fail(const std::string &what) {
-    error_ = what;
-    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-    return false;
-}
+void NNDescriptorMatcher::set_device(int device) { SetDevice(ctx_, device_, device); }
+fd_ctx *NNDescriptorMatcher::Context() { return Acquire(ctx_, device_, error_); }
+bool NNDescriptorMatcher::Fail(const std::string &what) { return FailWith(error_, what); }
 
 bool NNDescriptorMatcher::Match(const float *query, int32_t n_query, const float *train, int32_t n_train, int32_t dim,
                                 std::vector<int32_t> &train_index, std::vector<float> *distance,

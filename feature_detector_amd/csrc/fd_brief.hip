@@ -22,8 +22,7 @@
 // for h <= 31 every partial sum stays below 2^24, so the reference's sequential float sums are exact
 // and equal an integer wave reduction. Otherwise (fractional keypoint, bilinear, or h > 31) lane 0
 // accumulates in the reference's loop order from samples staged 64 at a time in LDS.
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_match_common.h"
 #include "../../include/fd_hip.h"
 
 namespace fdk {
@@ -215,7 +214,7 @@ __global__ __launch_bounds__(256) void k_brief(BriefArgs a) {
     const int f = static_cast<int>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot / a.stride)));
     const int k = static_cast<int>(__builtin_amdgcn_readfirstlane(static_cast<int>(slot - static_cast<int64_t>(f) * a.stride)));
     if (a.counts) {
-        const int n = static_cast<int>(static_cast<uint32_t>(a.counts[f]) & 0x01FFFFFFu);  // detect's guard flags off
+        const int n = count_word(a.counts[f]);  // detect's guard flags off
         if (k >= n) return;  // Compute sizes the descriptor list to the keypoints (descriptor.h:30-32)
     }
     const float u = a.uv[2 * slot];

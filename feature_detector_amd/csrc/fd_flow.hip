@@ -23,8 +23,7 @@
 // from the forward result with the original position as the guess; it reads the forward status as its
 // valid flag (valid_is_status). k_flow_finish applies the round-trip test and counts the tracked slots per
 // frame, one global atomic per workgroup.
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_match_common.h"
 
 namespace fdk {
 namespace {
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(kFlowThreads) void k_flow_lk(FlowArgs a) {
     if (lin >= static_cast<int64_t>(a.batch) * a.stride) return;
     const int f = static_cast<int>(lin / a.stride);
     const int slot_in = static_cast<int>(lin - static_cast<int64_t>(f) * a.stride);
-    const int nf = a.counts ? min(static_cast<int>(static_cast<uint32_t>(a.counts[f]) & 0x01FFFFFFu), a.stride) : a.stride;
+    const int nf = frame_count(a.counts, f, a.stride);
     if (slot_in >= nf) return;
     uint8_t *patch = patches[wave];
     const float x = a.xy[2 * lin], y = a.xy[2 * lin + 1];
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(kFinishThreads) void k_flow_finish(FlowFinishArgs a
     const int tiles = (a.stride + kFinishThreads - 1) / kFinishThreads;
     const int f = static_cast<int>(blockIdx.x) / tiles;
     const int i = (static_cast<int>(blockIdx.x) - f * tiles) * kFinishThreads + static_cast<int>(threadIdx.x);
-    const int nf = a.counts ? min(static_cast<int>(static_cast<uint32_t>(a.counts[f]) & 0x01FFFFFFu), a.stride) : a.stride;
+    const int nf = frame_count(a.counts, f, a.stride);
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
     bool ok = false;

@@ -286,36 +286,42 @@ struct BriefArgs {
     uint8_t *out_valid;  // [batch][stride] or null
 };
 
-// Hamming matcher (fd_match.hip): every entry of the "a" set against the "b" set of the same frame.
-// Forward pass: a = query, b = train. Cross-check's reverse pass: a = train, b = query, out_idx = the
-// reverse table, no other output and no test. Guided matching (fd_brief_match_guided): with a_xy / b_xy
+// A frame's count word (detect_points' device counts pass as they are): the count in bits 0..24, the
+// guard flags of fd_points_detect above them.
+constexpr uint32_t kCountMask = 0x01FFFFFFu;
+
+// What both matchers' kernels take alike: every entry of the "a" set against the "b" set of the same
+// frame. Forward pass: a = query, b = train. Cross-check's reverse pass: a = train, b = query, out_idx =
+// the reverse table, no other output and no test. Guided matching (fd_*_match_guided): with a_xy / b_xy
 // set, a "b" entry is a candidate of an "a" entry only inside the window |dx| <= radius_x, |dy| <= radius_y
 // (the reverse pass swaps the two position arrays with the sets; the gate is symmetric).
-struct MatchArgs {
-    const uint32_t *a_bits;   // [batch][a_stride][ceil(length / 32)]
-    const uint8_t *a_valid;   // [batch][a_stride] or null (= all valid)
+struct MatchCommon {
     const int32_t *a_counts;  // [batch] or null (= a_stride); bits 25..31 ignored
-    int a_stride;
-    const uint32_t *b_bits;  // the same three arrays of the searched set
-    const uint8_t *b_valid;
-    const int32_t *b_counts;
-    int b_stride;
-    int batch, length;
+    const int32_t *b_counts;  // the same of the searched set
+    int a_stride, b_stride, batch;
     int32_t *out_idx;     // [batch][a_stride]: best b index that passes the tests, else -1
-    int32_t *out_dist;    // [batch][a_stride][2] raw best / second distance (-1: absent), or null
     int32_t *out_counts;  // [batch] += accepted entries (zeroed by the caller), or null
     const int32_t *rev;   // [batch][b_stride] best a index of every b entry (cross-check), or null
-    int max_distance;     // < 0: off
     float max_ratio;      // <= 0: off
     const float *a_xy;    // [batch][a_stride][2] (x, y), or null (both null: no gate)
     const float *b_xy;    // [batch][b_stride][2]
     float radius_x, radius_y;  // the window's half-width / half-height (unused without a gate)
 };
 
+// Hamming matcher (fd_match.hip).
+struct MatchArgs : MatchCommon {
+    const uint32_t *a_bits;  // [batch][a_stride][ceil(length / 32)]
+    const uint8_t *a_valid;  // [batch][a_stride] or null (= all valid)
+    const uint32_t *b_bits;  // the same two arrays of the searched set
+    const uint8_t *b_valid;
+    int length;
+    int32_t *out_dist;  // [batch][a_stride][2] raw best / second distance (-1: absent), or null
+    int max_distance;   // < 0: off
+};
+
 // Squared-L2 matcher for float descriptors (fd_nn_match.hip). k_nn_norms first writes n(x) of every
 // descriptor of both sets (+inf for one flagged invalid, which is how validity reaches k_nn_match);
-// k_nn_match then runs as the Hamming matcher does: forward a = query, b = train; the cross-check's
-// reverse pass a = train, b = query, out_idx = the reverse table, no other output and no test.
+// k_nn_match then runs as the Hamming matcher does.
 struct NnNormArgs {
     const float *desc[2];     // [batch][stride[i]][dim]
     const uint8_t *valid[2];  // [batch][stride[i]] or null (= all valid)
@@ -325,26 +331,15 @@ struct NnNormArgs {
     int batch, dim;
     int vec[2];  // desc[i] is 16-byte aligned (set by the launcher)
 };
-struct NnMatchArgs {
-    const float *a_desc;      // [batch][a_stride][dim]
-    const float *a_norm;      // [batch][a_stride] (k_nn_norms)
-    const int32_t *a_counts;  // [batch] or null (= a_stride); bits 25..31 ignored
-    int a_stride;
-    const float *b_desc;  // the same three arrays of the searched set
+struct NnMatchArgs : MatchCommon {
+    const float *a_desc;  // [batch][a_stride][dim]
+    const float *a_norm;  // [batch][a_stride] (k_nn_norms)
+    const float *b_desc;  // the same two arrays of the searched set
     const float *b_norm;
-    const int32_t *b_counts;
-    int b_stride;
-    int batch, dim;       // dim: a multiple of 4, 4..256
-    int32_t *out_idx;     // [batch][a_stride]: best b index that passes the tests, else -1
-    float *out_dist;      // [batch][a_stride][2] raw best / second distance (-1: absent), or null
-    int32_t *out_counts;  // [batch] += accepted entries (zeroed by the caller), or null
-    const int32_t *rev;   // [batch][b_stride] best a index of every b entry (cross-check), or null
-    float max_distance;   // < 0: off
-    float max_ratio;      // <= 0: off
-    int b_vec;            // b_desc is 16-byte aligned (set by the launcher)
-    const float *a_xy;    // [batch][a_stride][2] (x, y), or null (both null: no gate), as in MatchArgs
-    const float *b_xy;    // [batch][b_stride][2]
-    float radius_x, radius_y;
+    int dim;             // a multiple of 4, 4..256
+    float *out_dist;     // [batch][a_stride][2] raw best / second distance (-1: absent), or null
+    float max_distance;  // < 0: off
+    int b_vec;           // b_desc is 16-byte aligned (set by the launcher)
 };
 
 // SuperPoint heatmap -> candidate lists (the K1 list format + level-0 histogram), for K4.

@@ -29,8 +29,7 @@
 // broadcast), and a pair outside the window takes the invalid entry's route: its popcount sum starts at
 // kInvalidPenalty. Per pair that is two subtractions, two compares and a select; the update and the merge
 // do not know of it. |b - a| has the same bits as |a - b|, so the reverse pass decides on the same pairs.
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_match_common.h"
 
 namespace fdk {
 namespace {
@@ -40,12 +39,6 @@ constexpr int kMatchThreads = kMatchWaves * kWave;
 constexpr int kMatchTile = kMatchThreads;  // "b" entries per LDS tile (one valid flag per thread)
 constexpr int kInvalidPenalty = 1 << 20;
 constexpr int kAbsent = 0x7FFFFFFF;
-
-// Entries of frame f: the count word without fd_points_detect's guard flags (bits 25..31), at most stride.
-__device__ __forceinline__ int frame_count(const int32_t *counts, int f, int stride) {
-    if (!counts) return stride;
-    return min(static_cast<int>(static_cast<uint32_t>(counts[f]) & 0x01FFFFFFu), stride);
-}
 
 // NW: descriptor words held per lane and per LDS row (words above ceil(length / 32) are zero).
 // GATED: only "b" entries inside the lane's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y).
@@ -137,24 +130,9 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
     const bool avalid = live && (!a.a_valid || a.a_valid[aslot]);
     const int d1 = (avalid && best < kInvalidPenalty) ? best : -1;
     const int d2 = (avalid && second < kInvalidPenalty) ? second : -1;
-    const int raw = d1 >= 0 ? bidx : -1;
-    bool ok = raw >= 0;
-    if (ok && a.max_distance >= 0 && d1 > a.max_distance) ok = false;
-    // one float multiply and one compare (the file is built without contraction); skipped without a second
-    if (ok && a.max_ratio > 0.0f && d2 >= 0 && !(static_cast<float>(d1) < a.max_ratio * static_cast<float>(d2)))
-        ok = false;
-    if (ok && a.rev && a.rev[static_cast<int64_t>(f) * a.b_stride + raw] != q) ok = false;
-    if (live) {
-        a.out_idx[aslot] = ok ? raw : -1;
-        if (a.out_dist) {
-            a.out_dist[2 * aslot] = d1;
-            a.out_dist[2 * aslot + 1] = d2;
-        }
-    }
-    if (a.out_counts) {
-        const int n_ok = popc64(ballot(ok));
-        if (lane == 0 && n_ok) atomicAdd(a.out_counts + f, n_ok);
-    }
+    // the ratio rule: one float multiply and one compare (the file is built without contraction)
+    match_emit(a, f, q, aslot, live, d1 >= 0, d2 >= 0, d1, d2, d1 >= 0 ? bidx : -1,
+               static_cast<float>(d1) < a.max_ratio * static_cast<float>(d2));
 }
 
 template <int NW>

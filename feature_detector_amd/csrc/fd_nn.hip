@@ -11,6 +11,7 @@
 //   ExtractDescriptorsForSelectedFeatures (:163-193) -> k_nn_desc: bilinear sampling of the
 //       1/8-resolution descriptor map, the reference's float sequence (-ffp-contract=off)
 #include "fd_emit.h"
+#include "fd_match_common.h"
 
 namespace fdk {
 namespace {
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256) void k_nn_desc(NnDescArgs a) {
     if (slot >= static_cast<int64_t>(a.batch) * a.stride) return;
     const int f = static_cast<int>(slot / a.stride);
     const int k = static_cast<int>(slot - static_cast<int64_t>(f) * a.stride);
-    if (a.counts && k >= static_cast<int>(static_cast<uint32_t>(a.counts[f]) & 0x01FFFFFFu)) return;
+    if (a.counts && k >= count_word(a.counts[f])) return;
     const float x = a.xy[2 * slot], y = a.xy[2 * slot + 1];
     // :170-178
     const float row = y / 8.0f;

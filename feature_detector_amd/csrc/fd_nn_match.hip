@@ -30,8 +30,7 @@
 // positions of its four rows (8 registers), a tile's TB "b" positions go to LDS beside bnorm, and a pair
 // outside the window gets d = +inf where an invalid column already does, after the MFMA chain, which the
 // gate does not touch.
-#include "fd_device.h"
-#include "fd_kernels.h"
+#include "fd_match_common.h"
 
 namespace fdk {
 namespace {
@@ -41,11 +40,6 @@ constexpr int kNnThreads = kNnWaves * kWave;
 constexpr int kNnRows = 16 * kNnWaves;  // "a" descriptors per workgroup
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int nn_frame_count(const int32_t *counts, int f, int stride) {
-    if (!counts) return stride;
-    return min(static_cast<int>(static_cast<uint32_t>(counts[f]) & 0x01FFFFFFu), stride);
-}
 
 __device__ __forceinline__ f4 load4(const float *p, bool vec) {
     if (vec) return *reinterpret_cast<const f4 *>(p);
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(256) void k_nn_norms(NnNormArgs a) {
     if (side) i -= n0;
     const int stride = a.stride[side];
     const int f = static_cast<int>(i / stride);
-    if (static_cast<int>(i - static_cast<int64_t>(f) * stride) >= nn_frame_count(a.counts[side], f, stride)) return;
+    if (static_cast<int>(i - static_cast<int64_t>(f) * stride) >= frame_count(a.counts[side], f, stride)) return;
     const float *p = a.desc[side] + i * a.dim;
     const bool vec = a.vec[side];
     float acc = 0.0f;
@@ -90,9 +84,9 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
     const int tiles = (a.a_stride + kNnRows - 1) / kNnRows;
     const int f = static_cast<int>(blockIdx.x) / tiles;
     const int q0 = (static_cast<int>(blockIdx.x) - f * tiles) * kNnRows;
-    const int na = nn_frame_count(a.a_counts, f, a.a_stride);
+    const int na = frame_count(a.a_counts, f, a.a_stride);
     if (q0 >= na) return;  // (the whole workgroup: nothing of this frame is read or written)
-    const int nb = nn_frame_count(a.b_counts, f, a.b_stride);
+    const int nb = frame_count(a.b_counts, f, a.b_stride);
     const int lane = lane_id();
     const int wave = static_cast<int>(threadIdx.x) >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -217,23 +211,8 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
     const int64_t aslot = static_cast<int64_t>(f) * a.a_stride + q;
     const bool has1 = live && b1 < inf, has2 = live && b2 < inf;
     const float d1 = has1 ? b1 : -1.0f, d2 = has2 ? b2 : -1.0f;
-    const int raw = has1 ? bi : -1;
-    bool ok = raw >= 0;
-    if (ok && a.max_distance >= 0.0f && d1 > a.max_distance) ok = false;
-    // two float multiplies and one compare (the file is built without contraction); skipped without a second
-    if (ok && a.max_ratio > 0.0f && has2 && !(d1 < (a.max_ratio * a.max_ratio) * d2)) ok = false;
-    if (ok && a.rev && a.rev[static_cast<int64_t>(f) * a.b_stride + raw] != q) ok = false;
-    if (live) {
-        a.out_idx[aslot] = ok ? raw : -1;
-        if (a.out_dist) {
-            a.out_dist[2 * aslot] = d1;
-            a.out_dist[2 * aslot + 1] = d2;
-        }
-    }
-    if (a.out_counts) {
-        const int n_ok = popc64(ballot(ok));
-        if (lane == 0 && n_ok) atomicAdd(a.out_counts + f, n_ok);
-    }
+    // the ratio rule: two float multiplies and one compare (the file is built without contraction)
+    match_emit(a, f, q, aslot, live, has1, has2, d1, d2, has1 ? bi : -1, d1 < (a.max_ratio * a.max_ratio) * d2);
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -1,7 +1,8 @@
 // Host runtime of libfdhip.so, the C ABI declared in include/fd_hip.h: the context (its stream, its
 // grow-only device workspace, the status words) and the staging of host frames and prior features.
 // The stages are in fd_rt_points.cpp (point detectors), fd_rt_select.cpp (selection driver),
-// fd_rt_lsd.cpp (LSD map and lines) and fd_rt_stages.cpp (BRIEF, PNG, NN); fd_ctx.h is their shared header.
+// fd_rt_lsd.cpp (LSD map and lines), fd_rt_stages.cpp (PNG, BRIEF compute, NN), fd_rt_match.cpp (the two
+// descriptor matchers) and fd_rt_flow.cpp (pyramid, tracker); fd_ctx.h is their shared header.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -143,7 +144,7 @@ int refuse_sync_under_capture(fd_ctx *c, int outputs_on_device) {
 int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t stride,
                       std::initializer_list<SlotArray> arrays) {
     for (int b = 0; b < batch; ++b) {
-        const int n = counts ? std::min<int64_t>(static_cast<uint32_t>(counts[b]) & 0x01FFFFFFu, stride) : stride;
+        const int n = counts ? std::min<int64_t>(static_cast<uint32_t>(counts[b]) & fdk::kCountMask, stride) : stride;
         if (n <= 0) continue;
         const size_t s0 = static_cast<size_t>(b) * stride;
         for (const SlotArray &a : arrays)

@@ -71,35 +71,59 @@ def _gate(q_xy, t_xy, radius, on_dev, b, sq, st):
     return fd_match_gate(rx, ry), sides[0], sides[1]
 
 
-def _host_side(bits, valid, counts, nw, name):
-    w = np.asarray(bits)
-    if w.dtype not in (np.uint32, np.int32):
-        raise TypeError(f"{name}_bits must be int32 or uint32 words")
-    w = np.ascontiguousarray(w).view(np.uint32)
-    if w.ndim == 2:
-        w = w[None]
-    if w.ndim != 3 or w.shape[2] != nw:
-        raise ValueError(f"{name}_bits must be [batch, S, {nw}] or [S, {nw}]")
-    b, s = int(w.shape[0]), int(w.shape[1])
-    v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
-    c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
-    return w, v, c, b, s
+def _side(x, valid, counts, on_dev, name, check):
+    """One set as the library takes it: (x [B, S, n], valid uint8 [B, S] or None, counts int32 [B] or None, B, S).
+    check(x, xp, name), xp = torch or numpy, is the matcher's rule: TypeError for x's dtype, ValueError for its axes."""
+    if on_dev:
+        import torch as xp
+    else:
+        xp, x = np, np.asarray(x)
+    if x.ndim == 2:
+        x = x[None]
+    check(x, xp, name)
+    b, s = int(x.shape[0]), int(x.shape[1])
+    if on_dev:
+        x = x.contiguous()
+        v = None if valid is None else valid.to(xp.uint8).contiguous().reshape(b, s)
+        c = None if counts is None else counts.to(xp.int32).contiguous().reshape(b)
+    else:
+        x = np.ascontiguousarray(x)
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
+        c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
+    return x, v, c, b, s
 
 
-def _device_side(bits, valid, counts, nw, name):
-    import torch
+def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg):
+    """What both matchers end with: the outputs (dist: the distances' dtype name; out: the caller's tensors,
+    checked against out_msg's shapes), then the entry point `entry`, or with a gate `entry`_guided."""
+    (qx, qv, qc, b, sq), (tx, tv, tc, _, st) = q, t
+    shapes = ((b, sq), (b, sq, 2), (b,))
+    if on_dev:
+        import torch
 
-    if bits.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
-        raise TypeError(f"{name}_bits must be int32 or uint32 words")
-    w = bits.contiguous()
-    if w.dim() == 2:
-        w = w.unsqueeze(0)
-    if w.dim() != 3 or w.shape[2] != nw:
-        raise ValueError(f"{name}_bits must be [batch, S, {nw}] or [S, {nw}]")
-    b, s = int(w.shape[0]), int(w.shape[1])
-    v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
-    c = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
-    return w, v, c, b, s
+        if out is not None:
+            idx, dst, counts = out
+            for ten, shape, dt in zip(out, shapes, (torch.int32, getattr(torch, dist), torch.int32)):
+                if tuple(ten.shape) != shape or ten.dtype != dt or not ten.is_contiguous():
+                    raise ValueError(out_msg.format(*shapes))
+        else:
+            idx = torch.full(shapes[0], -1, dtype=torch.int32, device=qx.device)
+            dst = torch.full(shapes[1], -1, dtype=getattr(torch, dist), device=qx.device)
+            counts = torch.zeros(shapes[2], dtype=torch.int32, device=qx.device)
+    else:
+        if out is not None:
+            raise ValueError("out= is for device tensors")
+        idx, dst, counts = np.full(shapes[0], -1, np.int32), np.full(shapes[1], -1, dist), np.zeros(shapes[2], np.int32)
+    _bind_stream(ctx, on_dev)
+    head, outs = (ctx.ptr, b, ctypes.byref(opts)), (_ptr(idx), _ptr(dst), _ptr(counts), 1 if on_dev else 0)
+    qa, ta = (_ptr(qx), _ptr(qv), _ptr(qc), sq), (_ptr(tx), _ptr(tv), _ptr(tc), st)
+    if gate is None:
+        rc = getattr(_lib.load(), entry)(*head, *qa, *ta, *outs)
+    else:
+        rc = getattr(_lib.load(), entry + "_guided")(*head, ctypes.byref(gate[0]), *qa, _ptr(gate[1]), *ta, _ptr(gate[2]),
+                                                     *outs)
+    _lib.check(ctx.ptr, rc)
+    return MatchResult(idx, dst, counts)
 
 
 def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_valid=None, length: int = 256,
@@ -129,68 +153,20 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
         raise ValueError("q_bits and t_bits must both be device tensors or both host arrays")
     if nw == 0:  # (the library reports the bad length: any word count is taken)
         nw = int(q_bits.shape[-1])
-    side = _device_side if on_dev else _host_side
-    qw, qv, qc, b, sq = side(q_bits, q_valid, q_counts, nw, "q")
-    tw, tv, tc, tb, st = side(t_bits, t_valid, t_counts, nw, "t")
-    if tb != b:
+
+    def check(w, xp, name):
+        if w.dtype not in (xp.int32, getattr(xp, "uint32", xp.int32)):
+            raise TypeError(f"{name}_bits must be int32 or uint32 words")
+        if w.ndim != 3 or w.shape[2] != nw:
+            raise ValueError(f"{name}_bits must be [batch, S, {nw}] or [S, {nw}]")
+
+    q = _side(q_bits, q_valid, q_counts, on_dev, "q", check)
+    t = _side(t_bits, t_valid, t_counts, on_dev, "t", check)
+    if t[3] != q[3]:
         raise ValueError("q_bits and t_bits must have the same batch")
-    gate = _gate(q_xy, t_xy, radius, on_dev, b, sq, st)
-    if on_dev:
-        import torch
-
-        if out is not None:
-            idx, dist, counts = out
-            for t, shape in ((idx, (b, sq)), (dist, (b, sq, 2)), (counts, (b,))):
-                if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
-                    raise ValueError(f"out must be contiguous int32 tensors of shapes {(b, sq)}, {(b, sq, 2)}, {(b,)}")
-        else:
-            idx = torch.full((b, sq), -1, dtype=torch.int32, device=qw.device)
-            dist = torch.full((b, sq, 2), -1, dtype=torch.int32, device=qw.device)
-            counts = torch.zeros((b,), dtype=torch.int32, device=qw.device)
-    else:
-        if out is not None:
-            raise ValueError("out= is for device tensors")
-        idx = np.full((b, sq), -1, np.int32)
-        dist = np.full((b, sq, 2), -1, np.int32)
-        counts = np.zeros((b,), np.int32)
-    _bind_stream(ctx, on_dev)
-    if gate is None:
-        rc = _lib.load().fd_brief_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qw), _ptr(qv), _ptr(qc), sq, _ptr(tw),
-                                        _ptr(tv), _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
-    else:
-        rc = _lib.load().fd_brief_match_guided(ctx.ptr, b, ctypes.byref(opts), ctypes.byref(gate[0]), _ptr(qw), _ptr(qv),
-                                               _ptr(qc), sq, _ptr(gate[1]), _ptr(tw), _ptr(tv), _ptr(tc), st,
-                                               _ptr(gate[2]), _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return MatchResult(idx, dist, counts)
-
-
-def _float_side(desc, valid, counts, on_dev, name):
-    if on_dev:
-        import torch
-
-        if desc.dtype != torch.float32:
-            raise TypeError(f"{name}_desc must be float32")
-        d = desc.contiguous()
-        if d.dim() == 2:
-            d = d.unsqueeze(0)
-    else:
-        d = np.asarray(desc)
-        if d.dtype != np.float32:
-            raise TypeError(f"{name}_desc must be float32")
-        d = np.ascontiguousarray(d)
-        if d.ndim == 2:
-            d = d[None]
-    if len(d.shape) != 3:
-        raise ValueError(f"{name}_desc must be [batch, S, dim] or [S, dim]")
-    b, s = int(d.shape[0]), int(d.shape[1])
-    if on_dev:
-        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
-        c = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
-    else:
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
-        c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
-    return d, v, c, b, s
+    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4])
+    return _run(ctx, "fd_brief_match", opts, q, t, gate, on_dev, "int32", out,
+                "out must be contiguous int32 tensors of shapes {}, {}, {}")
 
 
 def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid=None, max_distance: float = -1.0,
@@ -210,40 +186,21 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
     on_dev = _is_torch_device_tensor(q_desc)
     if on_dev != _is_torch_device_tensor(t_desc):
         raise ValueError("q_desc and t_desc must both be device tensors or both host arrays")
-    qd, qv, qc, b, sq = _float_side(q_desc, q_valid, q_counts, on_dev, "q")
-    td, tv, tc, tb, st = _float_side(t_desc, t_valid, t_counts, on_dev, "t")
-    if tb != b:
+
+    def check(d, xp, name):
+        if d.dtype != xp.float32:
+            raise TypeError(f"{name}_desc must be float32")
+        if d.ndim != 3:
+            raise ValueError(f"{name}_desc must be [batch, S, dim] or [S, dim]")
+
+    q = _side(q_desc, q_valid, q_counts, on_dev, "q", check)
+    t = _side(t_desc, t_valid, t_counts, on_dev, "t", check)
+    if t[3] != q[3]:
         raise ValueError("q_desc and t_desc must have the same batch")
-    dim = int(qd.shape[2])
-    if int(td.shape[2]) != dim:
+    dim = int(q[0].shape[2])
+    if int(t[0].shape[2]) != dim:
         raise ValueError("q_desc and t_desc must have the same dim")
     opts = fd_nn_match_opts(dim, float(max_distance), float(max_ratio), 1 if cross_check else 0)
-    gate = _gate(q_xy, t_xy, radius, on_dev, b, sq, st)
-    if on_dev:
-        import torch
-
-        if out is not None:
-            idx, dist, counts = out
-            for t, shape, dt in ((idx, (b, sq), torch.int32), (dist, (b, sq, 2), torch.float32), (counts, (b,), torch.int32)):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-                    raise ValueError(f"out must be contiguous tensors: int32 {(b, sq)}, float32 {(b, sq, 2)}, int32 {(b,)}")
-        else:
-            idx = torch.full((b, sq), -1, dtype=torch.int32, device=qd.device)
-            dist = torch.full((b, sq, 2), -1.0, dtype=torch.float32, device=qd.device)
-            counts = torch.zeros((b,), dtype=torch.int32, device=qd.device)
-    else:
-        if out is not None:
-            raise ValueError("out= is for device tensors")
-        idx = np.full((b, sq), -1, np.int32)
-        dist = np.full((b, sq, 2), -1.0, np.float32)
-        counts = np.zeros((b,), np.int32)
-    _bind_stream(ctx, on_dev)
-    if gate is None:
-        rc = _lib.load().fd_nn_match(ctx.ptr, b, ctypes.byref(opts), _ptr(qd), _ptr(qv), _ptr(qc), sq, _ptr(td), _ptr(tv),
-                                     _ptr(tc), st, _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
-    else:
-        rc = _lib.load().fd_nn_match_guided(ctx.ptr, b, ctypes.byref(opts), ctypes.byref(gate[0]), _ptr(qd), _ptr(qv),
-                                            _ptr(qc), sq, _ptr(gate[1]), _ptr(td), _ptr(tv), _ptr(tc), st, _ptr(gate[2]),
-                                            _ptr(idx), _ptr(dist), _ptr(counts), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return MatchResult(idx, dist, counts)
+    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4])
+    return _run(ctx, "fd_nn_match", opts, q, t, gate, on_dev, "float32", out,
+                "out must be contiguous tensors: int32 {}, float32 {}, int32 {}")
