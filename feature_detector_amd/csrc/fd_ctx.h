@@ -75,6 +75,11 @@ struct fd_ctx {
     // fd_pyr_build's host-output pyramid; fd_flow_lk: the backward pass's results ([batch][stride] positions
     // and status) and the staging of host-pointer calls (inputs, outputs)
     fdrt::DevBuf f_pyr, f_bxy, f_bst, f_xy, f_valid, f_counts, f_guess, f_oxy, f_ost, f_oerr, f_ocnt;
+    // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
+    // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
+    // per-frame best-hypothesis words; then the staging of host-pointer calls (inputs, outputs)
+    fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best;
+    fdrt::DevBuf g_qxy, g_txy, g_counts, g_idx, g_valid, g_omodel, g_oinl, g_ocnt, g_obest;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

@@ -402,7 +402,31 @@ struct FlowFinishArgs {
     int32_t *out_counts;         // [batch] += tracked slots (zeroed by the caller), or null
 };
 
+// RANSAC verification (fd_ransac.hip): one block for the three kernels. k_ransac_compact fills corr, cidx,
+// n and zeroes best; k_ransac_hyp fills models and raises best; k_ransac_finish writes the outputs.
+struct RansacArgs {
+    const float *q_xy, *t_xy;    // [batch][q_stride][2], [batch][t_stride][2] (x, y)
+    const int32_t *q_counts;     // [batch] or null (= q_stride); bits 25..31 ignored
+    const int32_t *match_idx;    // [batch][q_stride] or null (slot i pairs with slot i)
+    const uint8_t *pair_valid;   // [batch][q_stride] or null; only a byte equal to 1 takes part
+    int batch, q_stride, t_stride;
+    int model, hypotheses;       // FD_RANSAC_*; 1..4096
+    uint32_t seed;
+    double cx, cy, scale;        // the conditioning transform, as doubles of the option floats
+    double tt;                   // ((double)threshold * scale)^2
+    double *corr;                // [batch][q_stride][4] conditioned (x, y, u, v) of the correspondences, in slot order
+    int32_t *cidx;               // [batch][q_stride] a slot's index in corr, or -1
+    int32_t *n;                  // [batch] correspondences
+    double *models;              // [batch][hypotheses][9] conditioned models
+    unsigned long long *best;    // [batch] ((count + 1) << 32) | (0xFFFFFFFF - h) of the best valid hypothesis; 0: none
+    double *out_model;           // [batch][9]
+    uint8_t *out_inlier;         // [batch][q_stride] or null
+    int32_t *out_counts, *out_best;  // [batch] or null
+};
+
 // Launchers (stream-ordered, no allocation, no synchronisation: graph-capturable).
+// the three kernels of fd_ransac, in order
+hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);

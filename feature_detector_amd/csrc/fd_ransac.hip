@@ -1,0 +1,350 @@
+// RANSAC verification of matches and tracks (fd_ransac, include/fd_hip.h): the fundamental matrix from 8
+// correspondences or the homography from 4, a fixed number of hypotheses, all evaluated. Every floating
+// point operation is a double one, rounded once (the build passes -ffp-contract=off), in the contract's
+// order, so the result is a definite one that tests/ransac_ref.py restates bit for bit.
+//
+// k_ransac_compact, one workgroup per frame: the ordered list of the frame's correspondences (conditioned
+// coordinates, 32 bytes each) by a workgroup prefix over the take flags, and every slot's index in it.
+// k_ransac_hyp, one wave per workgroup, a lane per hypothesis: the lane samples, builds its 8 x 9 system
+// and eliminates it with complete pivoting. The pivot search indexes rows and columns by data, so the
+// system lives in LDS as [element][lane] (36 KiB): the bank of an access depends on the lane alone,
+// whatever element each lane picks, and nothing is indexed dynamically in registers. The correspondences
+// then pass through an LDS tile that every lane reads at the same address (a broadcast), each lane
+// counting its own model's inliers. The wave's best (count, lowest index) goes to the frame's 64-bit slot
+// in one atomicMax. k_ransac_finish, one workgroup per frame: classifies every slot with the winner by the
+// same device function and writes the outputs.
+#include "fd_match_common.h"
+
+namespace fdk {
+namespace {
+
+constexpr int kRansacThreads = 256;  // k_ransac_compact, k_ransac_finish
+constexpr int kTile = 256;           // correspondences per LDS tile of the scoring loop (8 KiB)
+constexpr int kFundamental = 0;      // FD_RANSAC_FUNDAMENTAL
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// The M distinct picks of hypothesis h of frame f among n correspondences; false when there are fewer
+// than M or a pick found no new index in 32 tries.
+template <int M>
+__device__ __forceinline__ bool sample(uint32_t seed, int f, int h, int n, int (&pick)[M]) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) pick[k] = 0;
+    if (n < M) return false;
+    const uint32_t base = mix(mix(seed + 0x9E3779B9u * static_cast<uint32_t>(f)) + static_cast<uint32_t>(h));
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        bool found = false;
+        for (int a = 0; a < 32 && !found && ok; ++a) {
+            const int idx = static_cast<int>(__umulhi(mix(base + 32u * k + a), static_cast<uint32_t>(n)));
+            bool dup = false;
+#pragma unroll
+            for (int j = 0; j < k; ++j) dup |= pick[j] == idx;
+            if (!dup) {
+                pick[k] = idx;
+                found = true;
+            }
+        }
+        ok = ok && found;
+    }
+    return ok;
+}
+
+// Element (r, c) of a lane's 8 x 9 system: A points at the lane's column of the [element][lane] array.
+__device__ __forceinline__ double &el(double *A, int r, int c) { return A[(9 * r + c) * kWave]; }
+
+// Null vector of the lane's system by Gaussian elimination with complete pivoting, into x; false for a
+// pivot that fails the relative test or a non-finite result. Destroys the system.
+__device__ __forceinline__ bool null_vector(double *A, double (&x)[9]) {
+    uint64_t perm = 0x876543210ull;  // nibble c: the original column now at position c
+    bool ok = true;
+    double p0 = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        double best = -1.0;
+        int pr = k, pc = k;
+        for (int r = k; r < 8; ++r)
+            for (int c = k; c < 9; ++c) {
+                const double m = fabs(el(A, r, c));
+                if (m > best) {  // false for a NaN
+                    best = m;
+                    pr = r;
+                    pc = c;
+                }
+            }
+        if (k == 0) p0 = best;
+        ok = ok && best > 1e-12 * p0;
+        for (int c = k; c < 9; ++c) {  // the columns left of k are never read again
+            const double t = el(A, k, c);
+            el(A, k, c) = el(A, pr, c);
+            el(A, pr, c) = t;
+        }
+        for (int r = 0; r < 8; ++r) {
+            const double t = el(A, r, k);
+            el(A, r, k) = el(A, r, pc);
+            el(A, r, pc) = t;
+        }
+        const uint64_t nk = (perm >> (4 * k)) & 15u, nc = (perm >> (4 * pc)) & 15u;
+        perm = (perm & ~(15ull << (4 * k))) | (nc << (4 * k));
+        perm = (perm & ~(15ull << (4 * pc))) | (nk << (4 * pc));
+        const double piv = el(A, k, k);
+        for (int r = k + 1; r < 8; ++r) {
+            const double f = el(A, r, k) / piv;
+            for (int c = k + 1; c < 9; ++c) el(A, r, c) = el(A, r, c) - f * el(A, k, c);
+        }
+    }
+    double y[9];
+    y[8] = 1.0;
+#pragma unroll
+    for (int k = 7; k >= 0; --k) {
+        double s = 0.0;
+#pragma unroll
+        for (int c = k + 1; c < 9; ++c) s = s + el(A, k, c) * y[c];
+        y[k] = (0.0 - s) / el(A, k, k);
+    }
+    // undo the column permutation through the (now free) first elements of the lane's column
+#pragma unroll
+    for (int c = 0; c < 9; ++c) A[static_cast<int>((perm >> (4 * c)) & 15u) * kWave] = y[c];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        x[c] = A[c * kWave];
+        ok = ok && isfinite(x[c]);
+    }
+    return ok;
+}
+
+// The inlier test of a conditioned model h on a conditioned correspondence p = (x, y, u, v): the Sampson
+// distance (F) or the forward transfer error (H) against tt = t * t, without a division. A NaN fails.
+template <int MODEL>
+__device__ __forceinline__ bool inlier(const double (&h)[9], d4 p, double tt) {
+    const double x = p.x, y = p.y, u = p.z, v = p.w;
+    if (MODEL == kFundamental) {
+        const double l0 = h[0] * x + h[1] * y + h[2];
+        const double l1 = h[3] * x + h[4] * y + h[5];
+        const double l2 = h[6] * x + h[7] * y + h[8];
+        const double m0 = h[0] * u + h[3] * v + h[6];
+        const double m1 = h[1] * u + h[4] * v + h[7];
+        const double e = u * l0 + v * l1 + l2;
+        return e * e <= tt * (l0 * l0 + l1 * l1 + m0 * m0 + m1 * m1);
+    }
+    const double w = h[6] * x + h[7] * y + h[8];
+    const double dx = (h[0] * x + h[1] * y + h[2]) - u * w;
+    const double dy = (h[3] * x + h[4] * y + h[5]) - v * w;
+    return dx * dx + dy * dy <= tt * (w * w);
+}
+
+__global__ __launch_bounds__(kRansacThreads) void k_ransac_compact(RansacArgs a) {
+    __shared__ uint32_t wsum[kRansacThreads / kWave];
+    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
+    const int nf = frame_count(a.q_counts, f, a.q_stride);
+    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
+    d4 *corr = reinterpret_cast<d4 *>(a.corr) + s0;
+    uint32_t base = 0;
+    for (int i0 = 0; i0 < nf; i0 += kRansacThreads) {
+        const int i = i0 + tid;
+        bool take = false;
+        d4 p = {0.0, 0.0, 0.0, 0.0};
+        if (i < nf) {
+            take = !a.pair_valid || a.pair_valid[s0 + i] == 1;
+            const int j = a.match_idx ? a.match_idx[s0 + i] : i;
+            take = take && j >= 0 && j < a.t_stride;
+            if (take) {
+                const float2 q = reinterpret_cast<const float2 *>(a.q_xy)[s0 + i];
+                const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[static_cast<int64_t>(f) * a.t_stride + j];
+                take = isfinite(q.x) && isfinite(q.y) && isfinite(t.x) && isfinite(t.y);
+                p.x = (static_cast<double>(q.x) - a.cx) * a.scale;
+                p.y = (static_cast<double>(q.y) - a.cy) * a.scale;
+                p.z = (static_cast<double>(t.x) - a.cx) * a.scale;
+                p.w = (static_cast<double>(t.y) - a.cy) * a.scale;
+            }
+        }
+        uint32_t tot;
+        const uint32_t pos = base + wg_excl_add<kRansacThreads>(take ? 1u : 0u, wsum, tot);
+        if (take) corr[pos] = p;  // pos < nf <= q_stride
+        if (i < nf) a.cidx[s0 + i] = take ? static_cast<int32_t>(pos) : -1;
+        base += tot;
+    }
+    if (tid == 0) {
+        a.n[f] = static_cast<int32_t>(base);
+        a.best[f] = 0ull;
+    }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(kWave) void k_ransac_hyp(RansacArgs a) {
+    constexpr int M = MODEL == kFundamental ? 8 : 4;
+    __shared__ double mat[72 * kWave];
+    __shared__ d4 tile[kTile];
+    const int lane = lane_id();
+    const int groups = (a.hypotheses + kWave - 1) / kWave;
+    const int f = static_cast<int>(blockIdx.x) / groups;
+    const int h = (static_cast<int>(blockIdx.x) - f * groups) * kWave + lane;
+    const int n = a.n[f];
+    const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + static_cast<int64_t>(f) * a.q_stride;
+    int pick[M];
+    bool ok = h < a.hypotheses;
+    ok = sample<M>(a.seed, f, h, n, pick) && ok;
+    double *A = mat + lane;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        d4 p = {0.0, 0.0, 0.0, 0.0};
+        if (ok) p = corr[pick[k]];  // pick < n <= q_stride
+        const double x = p.x, y = p.y, u = p.z, v = p.w;
+        if (MODEL == kFundamental) {
+            el(A, k, 0) = u * x;
+            el(A, k, 1) = u * y;
+            el(A, k, 2) = u;
+            el(A, k, 3) = v * x;
+            el(A, k, 4) = v * y;
+            el(A, k, 5) = v;
+            el(A, k, 6) = x;
+            el(A, k, 7) = y;
+            el(A, k, 8) = 1.0;
+        } else {
+            el(A, 2 * k, 0) = x;
+            el(A, 2 * k, 1) = y;
+            el(A, 2 * k, 2) = 1.0;
+            el(A, 2 * k, 3) = 0.0;
+            el(A, 2 * k, 4) = 0.0;
+            el(A, 2 * k, 5) = 0.0;
+            el(A, 2 * k, 6) = -(u * x);
+            el(A, 2 * k, 7) = -(u * y);
+            el(A, 2 * k, 8) = -u;
+            el(A, 2 * k + 1, 0) = 0.0;
+            el(A, 2 * k + 1, 1) = 0.0;
+            el(A, 2 * k + 1, 2) = 0.0;
+            el(A, 2 * k + 1, 3) = x;
+            el(A, 2 * k + 1, 4) = y;
+            el(A, 2 * k + 1, 5) = 1.0;
+            el(A, 2 * k + 1, 6) = -(v * x);
+            el(A, 2 * k + 1, 7) = -(v * y);
+            el(A, 2 * k + 1, 8) = -v;
+        }
+    }
+    double x[9];
+    ok = null_vector(A, x) && ok;
+
+    int count = 0;
+    for (int base = 0; base < n; base += kTile) {  // n is the frame's: uniform over the workgroup
+        const int m = min(kTile, n - base);
+        __syncthreads();
+        for (int j = lane; j < m; j += kWave) tile[j] = corr[base + j];
+        __syncthreads();
+        for (int j = 0; j < m; ++j) count += inlier<MODEL>(x, tile[j], a.tt) ? 1 : 0;
+    }
+    if (ok) {
+        double *dst = a.models + (static_cast<int64_t>(f) * a.hypotheses + h) * 9;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) dst[c] = x[c];
+    }
+    // valid hypotheses carry count + 1, so that a valid one with no inlier still beats "none" (0)
+    const uint32_t hi = ok ? static_cast<uint32_t>(count) + 1u : 0u;
+    const uint32_t top = wave_max_u32(hi);
+    const uint32_t lo = wave_max_u32(hi == top ? 0xFFFFFFFFu - static_cast<uint32_t>(h) : 0u);
+    if (lane == 0 && top) atomicMax(a.best + f, (static_cast<unsigned long long>(top) << 32) | lo);
+}
+
+// out = a * b, 3 x 3 row-major, every sum from 0.0 with the inner index ascending.
+__device__ __forceinline__ void matmul3(const double (&a)[9], const double (&b)[9], double (&out)[9]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc = acc + a[3 * i + k] * b[3 * k + j];
+            out[3 * i + j] = acc;
+        }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(kRansacThreads) void k_ransac_finish(RansacArgs a) {
+    __shared__ int total;
+    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
+    const int nf = frame_count(a.q_counts, f, a.q_stride);
+    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
+    const unsigned long long key = a.best[f];
+    const bool has = key != 0ull;
+    const int h = has ? static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key)) : -1;
+    double x[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) x[c] = has ? a.models[(static_cast<int64_t>(f) * a.hypotheses + h) * 9 + c] : 0.0;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + s0;
+    uint32_t mine = 0;
+    for (int i = tid; i < nf; i += kRansacThreads) {
+        bool in = false;
+        if (has) {
+            const int ci = a.cidx[s0 + i];
+            if (ci >= 0) in = inlier<MODEL>(x, corr[ci], a.tt);
+        }
+        if (a.out_inlier) a.out_inlier[s0 + i] = in ? 1 : 0;
+        mine += in ? 1u : 0u;
+    }
+    const uint32_t wave_n = wave_total_add(mine);
+    if (lane_id() == 0 && wave_n) atomicAdd(&total, static_cast<int>(wave_n));
+    __syncthreads();
+    if (tid != 0) return;
+    if (a.out_counts) a.out_counts[f] = total;
+    if (a.out_best) a.out_best[f] = h;
+    double *om = a.out_model + static_cast<int64_t>(f) * 9;
+    if (!has) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) om[c] = 0.0;
+        return;
+    }
+    const double s = a.scale;
+    const double T[9] = {s, 0.0, -(s * a.cx), 0.0, s, -(s * a.cy), 0.0, 0.0, 1.0};
+    double L[9], mt[9], p[9];
+    if (MODEL == kFundamental) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) L[3 * i + j] = T[3 * j + i];
+    } else {
+        const double inv = 1.0 / s;
+        const double Ti[9] = {inv, 0.0, a.cx, 0.0, inv, a.cy, 0.0, 0.0, 1.0};
+#pragma unroll
+        for (int c = 0; c < 9; ++c) L[c] = Ti[c];
+    }
+    matmul3(x, T, mt);
+    matmul3(L, mt, p);
+    double best = -1.0, pv = p[0];
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+        if (fabs(p[c]) > best) {
+            best = fabs(p[c]);
+            pv = p[c];
+        }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) om[c] = p[c] / pv;
+}
+
+}  // namespace
+
+hipError_t launch_ransac(const RansacArgs &a, hipStream_t s) {
+    const int64_t blocks = static_cast<int64_t>(a.batch) * ((a.hypotheses + kWave - 1) / kWave);
+    if (a.batch < 1 || blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    const dim3 frames(static_cast<unsigned>(a.batch)), hyps(static_cast<unsigned>(blocks));
+    hipLaunchKernelGGL(k_ransac_compact, frames, dim3(kRansacThreads), 0, s, a);
+    if (a.model == kFundamental) {
+        hipLaunchKernelGGL((k_ransac_hyp<0>), hyps, dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL((k_ransac_finish<0>), frames, dim3(kRansacThreads), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_ransac_hyp<1>), hyps, dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL((k_ransac_finish<1>), frames, dim3(kRansacThreads), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace fdk

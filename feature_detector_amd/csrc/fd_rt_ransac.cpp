@@ -1,0 +1,107 @@
+// Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac) over the kernels of
+// fd_ransac.hip.
+#include <algorithm>
+#include <cmath>
+
+#include "fd_ctx.h"
+
+using namespace fdrt;
+
+extern "C" {
+
+int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_xy, const int32_t *q_counts,
+              int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx, const uint8_t *pair_valid,
+              double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_xy || !t_xy || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
+    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
+    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
+    if (!match_idx && t_stride < q_stride)
+        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
+    if (opts->model != FD_RANSAC_FUNDAMENTAL && opts->model != FD_RANSAC_HOMOGRAPHY)
+        return fail(c, FD_ERR_INVALID, "model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
+    if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
+        return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
+    if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0f))
+        return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    if (!std::isfinite(opts->center_x) || !std::isfinite(opts->center_y))
+        return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
+    if (!std::isfinite(opts->scale) || !(opts->scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    if (q_stride == 0) {  // no slots: no frame has a model
+        if (io_on_device) {
+            FD_HIP_TRY(c, hipMemsetAsync(out_model, 0, sizeof(double) * 9 * batch, c->stream));
+            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+            if (out_best) FD_HIP_TRY(c, hipMemsetAsync(out_best, 0xFF, sizeof(int32_t) * batch, c->stream));
+        } else {
+            std::fill(out_model, out_model + static_cast<size_t>(9) * batch, 0.0);
+            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
+            if (out_best) std::fill(out_best, out_best + batch, -1);
+        }
+        return FD_OK;
+    }
+    const size_t qs = static_cast<size_t>(batch) * q_stride, ts = static_cast<size_t>(batch) * t_stride;
+    fdk::RansacArgs a{};
+    a.batch = batch;
+    a.q_stride = q_stride;
+    a.t_stride = t_stride;
+    a.model = opts->model;
+    a.hypotheses = opts->hypotheses;
+    a.seed = opts->seed;
+    a.cx = static_cast<double>(opts->center_x);
+    a.cy = static_cast<double>(opts->center_y);
+    a.scale = static_cast<double>(opts->scale);
+    const double t = static_cast<double>(opts->threshold) * a.scale;
+    a.tt = t * t;
+    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 4 * qs, a.corr));
+    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
+    FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
+    FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 9, a.models));
+    FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
+    if (io_on_device) {
+        a.q_xy = q_xy;
+        a.t_xy = t_xy;
+        a.q_counts = q_counts;
+        a.match_idx = match_idx;
+        a.pair_valid = pair_valid;
+        a.out_model = out_model;
+        a.out_inlier = out_inlier;
+        a.out_counts = out_counts;
+        a.out_best = out_best;
+    } else {
+        FD_HIP_TRY(c, ensure_as(c, c->g_qxy, 2 * qs, a.q_xy));
+        FD_HIP_TRY(c, hipMemcpyAsync(c->g_qxy.p, q_xy, sizeof(float) * 2 * qs, hipMemcpyHostToDevice, c->stream));
+        FD_HIP_TRY(c, ensure_as(c, c->g_txy, 2 * ts, a.t_xy));
+        if (ts) FD_HIP_TRY(c, hipMemcpyAsync(c->g_txy.p, t_xy, sizeof(float) * 2 * ts, hipMemcpyHostToDevice, c->stream));
+        if (q_counts) {
+            FD_HIP_TRY(c, ensure_as(c, c->g_counts, batch, a.q_counts));
+            FD_HIP_TRY(c, hipMemcpyAsync(c->g_counts.p, q_counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
+        }
+        if (match_idx) {
+            FD_HIP_TRY(c, ensure_as(c, c->g_idx, qs, a.match_idx));
+            FD_HIP_TRY(c, hipMemcpyAsync(c->g_idx.p, match_idx, sizeof(int32_t) * qs, hipMemcpyHostToDevice, c->stream));
+        }
+        if (pair_valid) {
+            FD_HIP_TRY(c, ensure_as(c, c->g_valid, qs, a.pair_valid));
+            FD_HIP_TRY(c, hipMemcpyAsync(c->g_valid.p, pair_valid, qs, hipMemcpyHostToDevice, c->stream));
+        }
+        FD_HIP_TRY(c, ensure_as(c, c->g_omodel, static_cast<size_t>(9) * batch, a.out_model));
+        if (out_inlier) FD_HIP_TRY(c, ensure_as(c, c->g_oinl, qs, a.out_inlier));
+        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->g_ocnt, batch, a.out_counts));
+        if (out_best) FD_HIP_TRY(c, ensure_as(c, c->g_obest, batch, a.out_best));
+    }
+    FD_HIP_TRY(c, fdk::launch_ransac(a, c->stream));
+    if (!io_on_device) {
+        FD_HIP_TRY(c, hipMemcpyAsync(out_model, a.out_model, sizeof(double) * 9 * batch, hipMemcpyDeviceToHost, c->stream));
+        if (out_counts)
+            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
+        if (out_best)
+            FD_HIP_TRY(c, hipMemcpyAsync(out_best, a.out_best, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
+        return copy_back_written(c, q_counts, batch, q_stride, {{out_inlier, a.out_inlier, 1}});  // synchronises
+    }
+    return FD_OK;
+}
+
+}  // extern "C"

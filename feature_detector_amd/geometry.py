@@ -1,0 +1,129 @@
+"""RANSAC verification of matches and tracks over the C ABI (fd_ransac).
+
+An MI355X extension (the reference has no such stage): the step after brief_match / nn_match or track_lk
+in a VIO / SLAM front end, on their [batch][stride] layouts, so detect -> describe -> match -> verify and
+detect -> track -> verify stay on the GPU. The arithmetic (a counter-based sampler, one solve in double per
+hypothesis, every hypothesis evaluated) is in include/fd_hip.h.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import fd_ransac_opts
+from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
+
+MODELS = {"fundamental": _lib.FD_RANSAC_FUNDAMENTAL, "homography": _lib.FD_RANSAC_HOMOGRAPHY}
+
+
+@dataclass
+class GeometryResult:
+    model: object    # float64 [B, 9]: row-major 3 x 3 in pixel coordinates, largest entry 1.0; zeros: no model
+    inliers: object  # uint8 [B, S]: 1 = a correspondence the model classifies as an inlier
+    counts: object   # int32 [B]: inliers per frame
+    best: object     # int32 [B]: the winning hypothesis, -1: no model
+
+
+def _ptr(x):
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
+
+
+def conditioning(image_size=None):
+    """The fixed conditioning transform of verify_geometry: ((center_x, center_y), scale)."""
+    if image_size is None:
+        return (0.0, 0.0), 1.0 / 256
+    rows, cols = image_size
+    return ((cols - 1) / 2, (rows - 1) / 2), 2.0 / (rows + cols)
+
+
+def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: str = "fundamental", hypotheses: int = 256,
+                    seed: int = 0, threshold: float = 1.0, image_size=None, out=None,
+                    ctx: Context | None = None) -> GeometryResult:
+    """fd_ransac: the fundamental matrix ("fundamental", 8-point samples) or homography ("homography",
+    4-point samples) with the most inliers among `hypotheses` minimal samples, and the inlier mask.
+
+    q_xy: float32 [B, S, 2] (or [S, 2] for batch 1), t_xy: float32 [B, T, 2], (x, y) as detect_points and
+    track_lk write them. matches int32 [B, S]: the train index of every query slot as brief_match /
+    nn_match return it (-1: none); None pairs slot i with slot i (tracks: T >= S). valid uint8 [B, S]: a slot
+    takes part only where it is 1, so track_lk's status passes as it is (None: all). counts int32 [B]
+    (None: S each). threshold is in pixels: the Sampson distance (F) or the forward transfer error (H).
+
+    image_size = (rows, cols) conditions the coordinates with center = ((cols - 1) / 2, (rows - 1) / 2) and
+    scale = 2 / (rows + cols); without it the center is (0, 0) and the scale 1 / 256.
+
+    Host (numpy) q_xy gives numpy outputs; torch device q_xy gives torch outputs, asynchronous on torch's
+    current stream. Inlier slots the call does not write (>= counts[b]) are 0. Device path only: out =
+    preallocated contiguous tensors (model float64 [B, 9], inliers uint8 [B, S], counts int32 [B], best
+    int32 [B]); unwritten slots then keep their contents, and the call is kernels only (graph-capturable
+    once a first call of the shape has run). The inlier mask can be passed as the next track_lk's valid.
+    """
+    if model not in MODELS:
+        raise ValueError(f"model must be one of {sorted(MODELS)}")
+    on_dev = _is_torch_device_tensor(q_xy)
+    if _is_torch_device_tensor(t_xy) != on_dev:
+        raise ValueError("t_xy must be on the side (host / device) of q_xy")
+    ctx = _resolve_ctx(ctx, q_xy, t_xy)
+
+    def positions(x, name):
+        if on_dev:
+            import torch
+
+            if x.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32")
+            x = x.contiguous()
+            x = x.unsqueeze(0) if x.dim() == 2 else x
+        else:
+            x = np.asarray(x)
+            if x.dtype != np.float32:
+                raise TypeError(f"{name} must be float32")
+            x = np.ascontiguousarray(x)
+            x = x[None] if x.ndim == 2 else x
+        if len(x.shape) != 3 or x.shape[2] != 2:
+            raise ValueError(f"{name} must be [batch, S, 2] or [S, 2]")
+        return x
+
+    pq, pt = positions(q_xy, "q_xy"), positions(t_xy, "t_xy")
+    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
+    if int(pt.shape[0]) != b:
+        raise ValueError("q_xy and t_xy must have the same batch")
+    if matches is None and ts < s:
+        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
+    if on_dev:
+        import torch
+
+        mi = None if matches is None else matches.to(torch.int32).contiguous().reshape(b, s)
+        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
+        cn = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
+        if out is not None:
+            om, oi, oc, ob = out
+            for t, shape, dt in ((om, (b, 9), torch.float64), (oi, (b, s), torch.uint8), (oc, (b,), torch.int32),
+                                 (ob, (b,), torch.int32)):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                    raise ValueError(f"out must be contiguous tensors: float64 {(b, 9)}, uint8 {(b, s)}, int32 {(b,)}, "
+                                     f"int32 {(b,)}")
+        else:
+            om = torch.zeros((b, 9), dtype=torch.float64, device=pq.device)
+            oi = torch.zeros((b, s), dtype=torch.uint8, device=pq.device)
+            oc = torch.zeros((b,), dtype=torch.int32, device=pq.device)
+            ob = torch.zeros((b,), dtype=torch.int32, device=pq.device)
+    else:
+        if out is not None:
+            raise ValueError("out= is for device tensors")
+        mi = None if matches is None else np.ascontiguousarray(np.asarray(matches).astype(np.int32).reshape(b, s))
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
+        cn = None if counts is None else np.ascontiguousarray(np.asarray(counts).astype(np.int32).reshape(b))
+        om, oi = np.zeros((b, 9), np.float64), np.zeros((b, s), np.uint8)
+        oc, ob = np.zeros((b,), np.int32), np.zeros((b,), np.int32)
+    (cx, cy), scale = conditioning(image_size)
+    opts = fd_ransac_opts(MODELS[model], int(hypotheses), int(seed) & 0xFFFFFFFF, float(threshold), float(cx), float(cy),
+                          float(scale))
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_ransac(ctx.ptr, b, ctypes.byref(opts), _ptr(pq), _ptr(cn), s, _ptr(pt), ts, _ptr(mi), _ptr(v),
+                               _ptr(om), _ptr(oi), _ptr(oc), _ptr(ob), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return GeometryResult(om, oi, oc, ob)

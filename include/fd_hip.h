@@ -553,6 +553,83 @@ int fd_flow_lk(fd_ctx *ctx, int batch, int rows, int cols, int levels, const fd_
                const float *xy, const uint8_t *valid, const int32_t *counts, int32_t stride, const float *guess_xy,
                float *out_xy, uint8_t *out_status, float *out_err, int32_t *out_counts, int io_on_device);
 
+/* ---- RANSAC verification of matches and tracks (MI355X extension) ------------------------------------ */
+#define FD_RANSAC_FUNDAMENTAL 0 /* fundamental matrix from m = 8 correspondences */
+#define FD_RANSAC_HOMOGRAPHY 1  /* homography from m = 4 correspondences */
+#define FD_RANSAC_MAX_HYPOTHESES 4096
+
+typedef struct fd_ransac_opts {
+    int32_t model;      /* FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY */
+    int32_t hypotheses; /* 1..4096, all evaluated: no early exit */
+    uint32_t seed;
+    float threshold;    /* pixels, finite, > 0: Sampson distance (F), forward transfer error (H) */
+    float center_x, center_y, scale; /* fixed conditioning transform, finite, scale > 0 */
+} fd_ransac_opts;
+
+/*
+ * fd_ransac -- geometric verification of the correspondences of every frame of a batch: the model (F or H)
+ * of the minimal sample with the most inliers among a fixed number of hypotheses, and the inlier mask.
+ * The stage is an outlier filter whose mask feeds the next call (fd_flow_lk's valid, the prior features of
+ * fd_points_detect); the model is the best minimal-sample model, not a refit. The reference has no such
+ * stage: the contract is this text, a definite sequence. All floating point is double, every operation
+ * rounded once, no contraction, f64 division correctly rounded.
+ *
+ * q_xy: float [batch][q_stride][2], t_xy: float [batch][t_stride][2], stored (x, y). q_counts int32 [batch]
+ * (NULL: q_stride each; bits 25..31 ignored). match_idx int32 [batch][q_stride] as a matcher's out_idx
+ * leaves it (NULL: slot i pairs with slot i, the tracker's case). pair_valid uint8 [batch][q_stride]: a
+ * slot takes part only where the byte is exactly 1, so fd_flow_lk's out_status passes as it is (NULL: all).
+ *
+ * Correspondences of frame b: slot i is one when i < q_counts[b], pair_valid is NULL or 1 at the slot,
+ * j = match_idx ? match_idx[i] : i satisfies 0 <= j < t_stride, and all four coordinates are finite.
+ * They are taken in ascending i and numbered 0..n-1, each with four conditioned coordinates
+ *   x = ((double)q.x - (double)center_x) * (double)scale, y likewise with center_y, (u, v) the same of t_xy[j].
+ *
+ * Sampler (uint32 arithmetic): mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16.
+ * Hypothesis h of frame b: base = mix(mix(seed + 0x9E3779B9*b) + h). Pick k = 0..m-1 tries a = 0..31:
+ * r = mix(base + 32k + a), idx = ((uint64)r * n) >> 32; the first idx not among the earlier picks is taken;
+ * 32 failed tries make the hypothesis invalid. n < m: no hypothesis is valid.
+ *
+ * Rows of the 8 x 9 system. F, per pick: [u*x, u*y, u, v*x, v*y, v, x, y, 1]. H, per pick, two rows, in
+ * pick order: [x, y, 1, 0, 0, 0, -(u*x), -(u*y), -u] and [0, 0, 0, x, y, 1, -(v*x), -(v*y), -v].
+ *
+ * Null vector, Gaussian elimination with complete pivoting. For k = 0..7: the pivot is the entry of largest
+ * |A[r][c]| over r = k..7 (outer, ascending), c = k..8 (inner, ascending), compared with a strict > starting
+ * from -1 at (k, k) (a NaN never wins); p0 = the pivot magnitude of step 0; the hypothesis is invalid unless
+ * best > 1e-12 * p0; rows k <-> r and columns k <-> c are swapped (the column permutation recorded); for
+ * r = k+1..7: f = A[r][k] / A[k][k], A[r][c] = A[r][c] - f * A[k][c] for c = k+1..8. Back substitution:
+ * x[8] = 1; for k = 7..0: s = 0.0, s = s + A[k][c] * x[c] over c ascending from k+1, x[k] = (0.0 - s) / A[k][k].
+ * The column permutation is undone; a non-finite entry makes the hypothesis invalid.
+ *
+ * Score, on conditioned coordinates with t = (double)threshold * (double)scale. F: l = F (x, y, 1),
+ * m0, m1 the first two entries of F^T (u, v, 1), each a left-to-right sum of three products,
+ * e = u*l0 + v*l1 + l2; inlier iff e*e <= (t*t) * (l0*l0 + l1*l1 + m0*m0 + m1*m1). H: w = h6*x + h7*y + h8,
+ * dx = (h0*x + h1*y + h2) - u*w, dy = (h3*x + h4*y + h5) - v*w; inlier iff dx*dx + dy*dy <= (t*t) * (w*w).
+ * A NaN fails the compare. The best hypothesis is the valid one with the most inliers, the lowest index
+ * among equals (the matchers' rule). A frame with no valid hypothesis has no model.
+ *
+ * Outputs. out_model double [batch][9], row-major 3 x 3 in pixel coordinates: with
+ * T = [[s, 0, -(s*cx)], [0, s, -(s*cy)], [0, 0, 1]] the F model is T^T (F T) and the H model T^-1 (H T),
+ * T^-1 = [[1.0/s, 0, cx], [0, 1.0/s, cy], [0, 0, 1]], every product plain triple loops, each sum from 0.0
+ * with the inner index ascending; the result is divided by its entry of largest magnitude (strict > from -1,
+ * so the lowest index among equals), which becomes exactly 1.0. A frame with no model gets nine zeros.
+ * out_inlier uint8 [batch][q_stride] (NULL to skip): 1 for a correspondence the best model classifies as an
+ * inlier by the test above, 0 for every other slot below q_counts[b]; slots >= q_counts[b] are not written.
+ * out_counts [batch] (NULL to skip): the number of ones. out_best [batch] (NULL to skip): the winning
+ * hypothesis index, or -1. q_stride 0: nothing but out_counts = 0, out_best = -1 and a zero model.
+ *
+ * The arrays are device pointers when io_on_device: the call is then asynchronous on the context's stream,
+ * and graph-capturable once a first call of the shape has sized the workspace. Host pointers otherwise:
+ * staged through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, q_xy, t_xy or out_model NULL; batch < 1; a negative stride; match_idx NULL
+ * with t_stride < q_stride; an option outside its range above or not finite.
+ */
+int fd_ransac(fd_ctx *ctx, int batch, const fd_ransac_opts *opts,
+              const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+              const float *t_xy, int32_t t_stride,
+              const int32_t *match_idx, const uint8_t *pair_valid,
+              double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
+              int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

@@ -13,6 +13,9 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      against the one before, fd_pyr_build (3 levels) of frames 0..62 and 1..63, and fd_flow_lk
                      (r 7, the defaults) of frame i's keypoints into frame i + 1, 10 calls (--fb: with the
                      forward-backward check, two k_flow_lk launches per call)
+  --shape fastverify FAST (need 500, dist 15) + BRIEF-256 on the 64 frames of fastflow's moving scene, fd_brief_match of
+                     frame i against frame i + 1 and fd_ransac (256 hypotheses, threshold 1 px) on the matches, the
+                     fundamental matrix and then the homography, 10 calls
   --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
                      128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
                      baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
@@ -35,7 +38,7 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "fastverify", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
@@ -151,6 +154,30 @@ elif a.shape == "fastflow":  # detect -> pyramids -> track on consecutive frames
     moved = (out[0] - res.xy[:-1])[out[1] == 1]
     print("keypoints per frame (mean):", float(n.mean()), "tracked (mean):", float(out[3].float().mean()),
           "median displacement of the tracked:", moved.median(0).values.tolist())
+elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consecutive frames of one moving scene
+    kind = "fast"
+    base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
+    base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)
+    frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
+    out = None
+    for _ in range(a.calls or 10):
+        res = fd.detect_points(kind, frames, 500, 15, THR[kind])
+        if out is None:
+            s = res.xy.shape[1]
+            out = (torch.empty((63, s), dtype=torch.int32, device="cuda"), torch.empty((63, s, 2), dtype=torch.int32, device="cuda"),
+                   torch.empty((63,), dtype=torch.int32, device="cuda"))
+            geo = [(torch.empty((63, 9), dtype=torch.float64, device="cuda"), torch.empty((63, s), dtype=torch.uint8, device="cuda"),
+                    torch.empty((63,), dtype=torch.int32, device="cuda"), torch.empty((63,), dtype=torch.int32, device="cuda"))
+                   for _ in range(2)]
+        bits, valid = fd.brief_compute(frames, res.xy, res.counts, length=256, half_patch_size=8, with_valid=True)
+        fd.brief_match(bits[:-1], bits[1:], res.counts[:-1], res.counts[1:], valid[:-1], valid[1:], max_distance=64,
+                       max_ratio=0.9, out=out)
+        for model, o in zip(("fundamental", "homography"), geo):
+            fd.verify_geometry(res.xy[:-1], res.xy[1:], matches=out[0], counts=res.counts[:-1], model=model, hypotheses=256,
+                               threshold=1.0, image_size=(720, 1280), out=o)
+    print("matches per frame pair (mean):", float(out[2].float().mean()), "inliers F / H (mean):",
+          float(geo[0][2].float().mean()), float(geo[1][2].float().mean()), "frames without a model:",
+          int((geo[0][3] < 0).sum()), int((geo[1][3] < 0).sum()))
 elif a.shape == "nnmatch":
     kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
     B, S = 64, 240
