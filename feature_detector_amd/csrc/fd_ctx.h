@@ -73,7 +73,8 @@ struct fd_ctx {
     // the guided matchers' host-pointer calls stage both sets' positions ([batch][stride][2]) here
     fdrt::DevBuf m_qxy, m_txy;
     // fd_pyr_build's host-output pyramid; fd_flow_lk: the backward pass's results ([batch][stride] positions
-    // and status) and the staging of host-pointer calls (inputs, outputs)
+    // and status) and the staging of host-pointer calls (inputs, outputs); fd_points_refine's host-pointer
+    // calls stage their feature arrays in the same buffers (f_xy, f_valid, f_counts, f_oxy, f_ost, f_ocnt)
     fdrt::DevBuf f_pyr, f_bxy, f_bst, f_xy, f_valid, f_counts, f_guess, f_oxy, f_ost, f_oerr, f_ocnt;
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the

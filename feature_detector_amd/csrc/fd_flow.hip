@@ -23,7 +23,7 @@
 // from the forward result with the original position as the guess; it reads the forward status as its
 // valid flag (valid_is_status). k_flow_finish applies the round-trip test and counts the tracked slots per
 // frame, one global atomic per workgroup.
-#include "fd_match_common.h"
+#include "fd_window.h"
 
 namespace fdk {
 namespace {
@@ -57,59 +57,6 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyr_down(const uint8_t *__restr
         dst[fr * ocols + xi] = static_cast<uint8_t>(s >> 2);
     }
 }
-
-constexpr int kFlowWaves = 4;
-constexpr int kFlowThreads = kFlowWaves * kWave;
-constexpr int kFlowPitch = 24;  // LDS patch row pitch in bytes: 2 * 10 + 4, the widest template patch
-constexpr int kFlowPatch = kFlowPitch * kFlowPitch;
-
-// Orders a wave's LDS accesses for the compiler. The hardware needs nothing: one wave's LDS instructions
-// execute in order, and the waves of a workgroup share no LDS here.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Exact sum over the wave of one int32 per lane (|sum| may pass 2^31): low and high halves apart.
-__device__ __forceinline__ int64_t wave_sum_i32(int32_t v) {
-    const uint32_t lo = wave_total_add(static_cast<uint32_t>(v) & 0xFFFFu);            // <= 64 * 65535
-    const int32_t hi = static_cast<int32_t>(wave_total_add(static_cast<uint32_t>(v >> 16)));  // |.| <= 64 * 32768
-    return static_cast<int64_t>(hi) * 65536 + static_cast<int64_t>(lo);
-}
-
-// The P x P pixels from (x0, y0) of a level into the wave's patch, reads clamped to the level's edge.
-__device__ __forceinline__ void stage_patch(uint8_t *patch, const uint8_t *img, int rows, int cols, int x0, int y0, int P,
-                                            int lane) {
-    const int px = lane & 31, par = lane >> 5;
-    if (px < P) {
-        const int xx = min(max(x0 + px, 0), cols - 1);
-        for (int py = par; py < P; py += 2) {
-            const int yy = min(max(y0 + py, 0), rows - 1);
-            patch[py * kFlowPitch + px] = img[static_cast<int64_t>(yy) * cols + xx];
-        }
-    }
-}
-
-struct Weights {
-    int w00, w10, w01, w11;
-};
-// ix = floor(x), and the four integer weights of the fraction in 1/1024 steps (truncated)
-__device__ __forceinline__ void split_pos(float x, float y, int &ix, int &iy, Weights &w) {
-    const float fx = floorf(x), fy = floorf(y);
-    ix = static_cast<int>(fx);
-    iy = static_cast<int>(fy);
-    const int qx = static_cast<int>((x - fx) * 1024.0f), qy = static_cast<int>((y - fy) * 1024.0f);
-    w.w00 = (1024 - qx) * (1024 - qy);
-    w.w10 = qx * (1024 - qy);
-    w.w01 = (1024 - qx) * qy;
-    w.w11 = qx * qy;
-}
-__device__ __forceinline__ int raw_sum(const uint8_t *p, const Weights &w) {
-    return w.w00 * p[0] + w.w10 * p[1] + w.w01 * p[kFlowPitch] + w.w11 * p[kFlowPitch + 1];
-}
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }
 
 template <int ROUNDS>
 __global__ __launch_bounds__(kFlowThreads) void k_flow_lk(FlowArgs a) {

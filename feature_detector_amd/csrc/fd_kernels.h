@@ -402,6 +402,22 @@ struct FlowFinishArgs {
     int32_t *out_counts;         // [batch] += tracked slots (zeroed by the caller), or null
 };
 
+// Sub-pixel corner refinement (fd_refine.hip) on the frames [batch][rows][cols]; the per-frame counts come
+// from k_flow_finish (FlowFinishArgs without a backward pass).
+struct RefineArgs {
+    const uint8_t *frames;
+    int batch, rows, cols, stride;
+    int r, max_iters;            // half window 1..10
+    float eps2;                  // epsilon * epsilon (float)
+    float max_shift;
+    double tau;                  // (double)min_eigen * 1024.0 * (r + 1)^4
+    const float *xy;             // [batch][stride][2] (x, y); may be out_xy
+    const uint8_t *valid;        // [batch][stride] or null (= all valid)
+    const int32_t *counts;       // [batch] or null (= stride); bits 25..31 ignored
+    float *out_xy;               // [batch][stride][2]
+    uint8_t *out_status;         // [batch][stride]
+};
+
 // RANSAC verification (fd_ransac.hip): one block for the three kernels. k_ransac_compact fills corr, cidx,
 // n and zeroes best; k_ransac_hyp fills models and raises best; k_ransac_finish writes the outputs.
 struct RansacArgs {
@@ -431,6 +447,7 @@ hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);
 hipError_t launch_flow_finish(const FlowFinishArgs &a, hipStream_t s);
+hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 hipError_t launch_mask_boxes(const float *prior_xy, const int32_t *prior_frame, int n_prior, int dist, int rows,
                              int cols, uint32_t *mask, int mask_wpr, hipStream_t s);
 hipError_t launch_fast_mask_scan(const uint32_t *mask, int mask_wpr, int batch, int rows, int cols, int32_t *row_base,

@@ -1,6 +1,6 @@
 // Device code shared by the two matchers (fd_match.hip, fd_nn_match.hip): a frame's entry count and the
 // epilogue that turns a lane's (best, second) into the outputs.
-// The count helpers also serve the other per-keypoint kernels (fd_brief.hip, fd_nn.hip, fd_flow.hip).
+// The count helpers also serve the other per-keypoint kernels (fd_brief.hip, fd_nn.hip, fd_flow.hip, fd_refine.hip).
 #pragma once
 
 #include "fd_device.h"

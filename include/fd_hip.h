@@ -553,6 +553,81 @@ int fd_flow_lk(fd_ctx *ctx, int batch, int rows, int cols, int levels, const fd_
                const float *xy, const uint8_t *valid, const int32_t *counts, int32_t stride, const float *guess_xy,
                float *out_xy, uint8_t *out_status, float *out_err, int32_t *out_counts, int io_on_device);
 
+/* ---- Sub-pixel corner refinement (MI355X extension: the reference's detectors stop at integer pixels) -- */
+typedef struct fd_refine_opts {
+    int32_t half_window; /* r in 1..10: the window is (2r + 1)^2 pixels */
+    int32_t max_iters;   /* 1..100 */
+    float epsilon;       /* > 0: stop after a step of length <= epsilon (pixels) */
+    float min_eigen;     /* >= 0: as fd_flow_opts.min_eigen, of the weighted mean gradient matrix */
+    float max_shift;     /* > 0, finite: largest |refined - xy| per axis, in pixels */
+} fd_refine_opts;
+
+/* out_status values of fd_points_refine: 1 is the only "refined" */
+enum fd_refine_status {
+    FD_REFINE_INVALID = 0,  /* valid flag 0 */
+    FD_REFINE_REFINED = 1,
+    FD_REFINE_OUTSIDE = 2,  /* xy not finite or outside the frame, or the iteration left the frame */
+    FD_REFINE_FLAT = 3,     /* the window's gradient matrix fails the level test */
+    FD_REFINE_DIVERGED = 4  /* moved further than max_shift from xy, or a non-finite step */
+};
+
+/*
+ * fd_points_refine -- the cornerSubPix step between detection and tracking: for every feature xy of every
+ * frame of a batch, the point c whose offsets to the window's pixels are orthogonal to the gradients there
+ * (c + G^-1 sum w g g^T p, iterated), on frames [batch][rows][cols] uint8. A device pyramid of fd_pyr_build
+ * passes as frames as it is: its level 0 is at offset 0. Like fd_flow_lk the contract is this text, a definite
+ * arithmetic sequence in which every window sum is an exact integer (any summation order gives it) and only
+ * the 2 x 2 solve is floating point.
+ *
+ * xy, valid, counts, stride and io_on_device are fd_flow_lk's: xy float [batch][stride][2], stored (x, y);
+ * counts int32 [batch] (NULL: stride each; bits 25..31 ignored, so fd_points_detect's counts pass as they
+ * are); valid uint8 [batch][stride] (NULL: all valid). out_xy may be xy itself (in place): a slot reads its
+ * position once and writes it once. S(u, v) is fd_flow_lk's raw bilinear sum on the frame (floor, the
+ * fraction truncated to 1/1024, reads clamped to the frame's edge).
+ *
+ * Per feature slot below counts[b]:
+ *   valid 0: status 0, out_xy = xy.
+ *   xy not finite or outside [0, cols - 1] x [0, rows - 1]: status 2, out_xy = xy.
+ *   c = xy (float). At most max_iters iterations:
+ *   1. In-frame test: 0 <= c.x <= (float)(cols - 1) and 0 <= c.y <= (float)(rows - 1) (false on NaN);
+ *      failing it gives status 2.
+ *   2. Gradients at c, for integer offsets u, v in [-r, r] (arithmetic shifts):
+ *        Gx = (S(u + 1, v) - S(u - 1, v) + 2^15) >> 16,  Gy = (S(u, v + 1) - S(u, v - 1) + 2^15) >> 16
+ *      (32 times the central difference in intensity units per pixel; |G| <= 4080).
+ *   3. With the integer weight w(u, v) = (r + 1 - |u|)(r + 1 - |v|) (a tent; sum w = (r + 1)^4):
+ *        G11 = sum w Gx^2,  G12 = sum w Gx Gy,  G22 = sum w Gy^2
+ *        B1 = sum w (Gx^2 u + Gx Gy v),  B2 = sum w (Gx Gy u + Gy^2 v)
+ *      exact integers. A single term can pass 2^31 (r = 10: w |u| 2 4080^2 up to 1.1e10); the totals stay
+ *      below 2^42, so their conversion to double is exact.
+ *   4. Level test, in double, every operation rounded once, no contraction:
+ *        tau = (double)min_eigen * 1024.0 * (double)((r + 1)^4)
+ *        e11 = g11 - tau; e22 = g22 - tau; det = g11 * g22 - g12 * g12
+ *        usable iff det > 0 && e11 > 0 && e22 > 0 && e11 * e22 - g12 * g12 >= 0
+ *      (fd_flow_lk's step 4 on the weighted matrix). Not usable: status 3.
+ *   5. In double sx = (g22 * b1 - g12 * b2) / det, sy = (g11 * b2 - g12 * b1) / det; in float fx = (float)sx,
+ *      fy = (float)sy; c = c + (fx, fy), one float add per axis.
+ *      !(fabsf(c.x - xy.x) <= max_shift && fabsf(c.y - xy.y) <= max_shift): status 4 (a non-finite step fails
+ *      the test too). The loop stops after the update when fx * fx + fy * fy <= epsilon * epsilon (float,
+ *      every product rounded).
+ *   Running out of iterations is not a loss: status 1, out_xy = c (the in-frame test is step 1's alone: the
+ *   last update is not followed by one, so a refined c may lie up to max_shift outside the frame).
+ *   Status 2, 3 and 4 hand xy back, so out_xy is always a usable position array.
+ *
+ * Outputs: out_status uint8 (enum fd_refine_status), out_xy, out_counts [batch] (NULL to skip): the status-1
+ * slots below counts[b]. Slots >= counts[b] are not written. stride 0: nothing but out_counts = 0.
+ * frames is a device pointer when frames_on_device, else a host pointer staged through the context as
+ * fd_pyr_build stages host frames. The feature arrays (xy, valid, counts and the outputs) are device
+ * pointers when io_on_device. With device frames and device feature arrays the call is kernels on the
+ * context's stream only: asynchronous and graph-capturable (no workspace is involved). Host feature arrays
+ * are staged through context buffers, complete on return; so is a call with host frames.
+ * FD_ERR_INVALID: ctx, opts, frames, xy, out_xy or out_status NULL; batch, rows or cols < 1; a negative
+ * stride; an option outside its range above or not finite.
+ */
+int fd_points_refine(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                     const fd_refine_opts *opts,
+                     const float *xy, const uint8_t *valid, const int32_t *counts, int32_t stride,
+                     float *out_xy, uint8_t *out_status, int32_t *out_counts, int io_on_device);
+
 /* ---- RANSAC verification of matches and tracks (MI355X extension) ------------------------------------ */
 #define FD_RANSAC_FUNDAMENTAL 0 /* fundamental matrix from m = 8 correspondences */
 #define FD_RANSAC_HOMOGRAPHY 1  /* homography from m = 4 correspondences */

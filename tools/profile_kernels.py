@@ -13,6 +13,9 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      against the one before, fd_pyr_build (3 levels) of frames 0..62 and 1..63, and fd_flow_lk
                      (r 7, the defaults) of frame i's keypoints into frame i + 1, 10 calls (--fb: with the
                      forward-backward check, two k_flow_lk launches per call)
+  --shape strefine   Shi-Tomasi (need 500, dist 15) on the 64 frames of fastflow's moving scene, fd_points_refine (r 5, 20
+                     iterations) of every frame's corners in place, fd_pyr_build (3 levels) and fd_flow_lk (r 7) of
+                     frame i's refined corners into frame i + 1, 10 calls
   --shape fastverify FAST (need 500, dist 15) + BRIEF-256 on the 64 frames of fastflow's moving scene, fd_brief_match of
                      frame i against frame i + 1 and fd_ransac (256 hypotheses, threshold 1 px) on the matches, the
                      fundamental matrix and then the homography, 10 calls
@@ -38,7 +41,7 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "fastverify", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
@@ -153,6 +156,29 @@ elif a.shape == "fastflow":  # detect -> pyramids -> track on consecutive frames
     n = (res.counts[:-1] & 0x1FFFFFF).float()
     moved = (out[0] - res.xy[:-1])[out[1] == 1]
     print("keypoints per frame (mean):", float(n.mean()), "tracked (mean):", float(out[3].float().mean()),
+          "median displacement of the tracked:", moved.median(0).values.tolist())
+elif a.shape == "strefine":  # detect -> refine -> pyramids -> track on consecutive frames of one moving scene
+    kind = "shi_tomasi"
+    base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
+    base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)
+    frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
+    out = None
+    for _ in range(a.calls or 10):
+        res = fd.detect_points(kind, frames, 500, 15, THR[kind])
+        if out is None:
+            s = res.xy.shape[1]
+            rst, rcnt = torch.empty((64, s), dtype=torch.uint8, device="cuda"), torch.empty((64,), dtype=torch.int32, device="cuda")
+            out = (torch.empty((63, s, 2), dtype=torch.float32, device="cuda"), torch.empty((63, s), dtype=torch.uint8, device="cuda"),
+                   torch.empty((63, s), dtype=torch.float32, device="cuda"), torch.empty((63,), dtype=torch.int32, device="cuda"))
+        start = res.xy.clone()
+        fd.refine_points(frames, res.xy, counts=res.counts, half_window=5, max_iters=20, out=(res.xy, rst, rcnt))
+        p0, p1 = fd.build_pyramid(frames[:-1], 3), fd.build_pyramid(frames[1:], 3)
+        fd.track_lk(p0, p1, res.xy[:-1], counts=res.counts[:-1], levels=3, half_window=7, out=out)
+    n = (res.counts & 0x1FFFFFF).float()
+    step = (res.xy - start)[rst == 1].abs()
+    moved = (out[0] - res.xy[:-1])[out[1] == 1]
+    print("corners per frame (mean):", float(n.mean()), "refined (mean):", float(rcnt.float().mean()),
+          "median |refinement| per axis:", step.median(0).values.tolist(), "tracked (mean):", float(out[3].float().mean()),
           "median displacement of the tracked:", moved.median(0).values.tolist())
 elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consecutive frames of one moving scene
     kind = "fast"
