@@ -7,7 +7,6 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -63,24 +62,19 @@ struct fd_ctx {
     bool sel_dirty = true;
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
-    fdrt::DevBuf b_uv, b_counts, b_bits, b_valid;
-    // fd_brief_match: the cross-check's reverse table ([batch][t_stride] best query of every train
-    // descriptor), and the staging of host-pointer calls (query / train inputs, outputs)
-    fdrt::DevBuf m_rev, m_qbits, m_qvalid, m_qcounts, m_tbits, m_tvalid, m_tcounts, m_idx, m_dist, m_counts;
-    // fd_nn_match shares them (descriptors staged in m_qbits / m_tbits) and adds the norms of both sets
-    // ([batch][q_stride], then [batch][t_stride])
-    fdrt::DevBuf m_norm;
-    // the guided matchers' host-pointer calls stage both sets' positions ([batch][stride][2]) here
-    fdrt::DevBuf m_qxy, m_txy;
-    // fd_pyr_build's host-output pyramid; fd_flow_lk: the backward pass's results ([batch][stride] positions
-    // and status) and the staging of host-pointer calls (inputs, outputs); fd_points_refine's host-pointer
-    // calls stage their feature arrays in the same buffers (f_xy, f_valid, f_counts, f_oxy, f_ost, f_ocnt)
-    fdrt::DevBuf f_pyr, f_bxy, f_bst, f_xy, f_valid, f_counts, f_guess, f_oxy, f_ost, f_oerr, f_ocnt;
+    // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors)
+    // stage their arrays here, in call order (fdrt::HostIo); the widest call is a guided match: 8 inputs, 3 outputs
+    static constexpr int kStaging = 11;
+    fdrt::DevBuf staging[kStaging];
+    // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
+    // fd_nn_match's norms of both sets ([batch][q_stride], then [batch][t_stride])
+    fdrt::DevBuf m_rev, m_norm;
+    // fd_flow_lk: the backward pass's results ([batch][stride] positions and status)
+    fdrt::DevBuf f_bxy, f_bst;
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
-    // per-frame best-hypothesis words; then the staging of host-pointer calls (inputs, outputs)
+    // per-frame best-hypothesis words
     fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best;
-    fdrt::DevBuf g_qxy, g_txy, g_counts, g_idx, g_valid, g_omodel, g_oinl, g_ocnt, g_obest;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate
@@ -172,16 +166,65 @@ int setup_priors(fd_ctx *c, int batch, int rows, int cols, int dist, const float
 // captured into a graph: refused at entry, before any work is enqueued.
 int refuse_sync_under_capture(fd_ctx *c, int outputs_on_device);
 
-// Host outputs of the per-keypoint stages (BRIEF, NN descriptors): the kernel writes slots [0, counts[b])
-// of frame b only (all `stride` without counts). Copies that prefix of every array back, frame by frame,
-// so that the caller's buffers keep their contents past it as the device path does, and synchronises.
+// Host outputs of the per-keypoint stages: the kernel writes slots [0, counts[b]) of frame b only (all `stride`
+// without counts). Copies that prefix of every array back, frame by frame, so that the caller's buffers keep
+// their contents past it as the device path does, and synchronises.
 struct SlotArray {
     void *dst;
     const void *src;
     size_t slot_bytes;
 };
-int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t stride,
-                      std::initializer_list<SlotArray> arrays);
+int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t stride, const std::vector<SlotArray> &arrays);
+
+// The arrays of one keypoint-stage call, host or device (io_on_device). Device-side: in / out / out_slots hand
+// the caller's pointer on and finish does nothing, so the call touches no staging buffer and enqueues its
+// kernels and memsets only. Host-side: every non-null array takes the next buffer of fd_ctx::staging (so an
+// output never shares its input's, even where the host pointers are equal), inputs (and `preload`ed outputs)
+// are uploaded on the stream, and finish copies the outputs back (`out` arrays whole, `out_slots` arrays by
+// copy_back_written) and synchronises, once. A null pointer stays null; n == 0 stages without a copy.
+// That sync is why an entry point calls refuse_sync_under_capture before it builds one.
+class HostIo {
+  public:
+    HostIo(fd_ctx *c, int io_on_device) : c_(c), dev_(io_on_device != 0) {}
+    template <typename T>
+    hipError_t in(const T *p, size_t n, const T *&dev) {
+        void *d = nullptr;
+        const hipError_t e = stage(p, sizeof(T) * n, true, d);
+        dev = static_cast<const T *>(d);
+        return e;
+    }
+    template <typename T>
+    hipError_t out(T *p, size_t n, T *&dev) {
+        return out_array(p, sizeof(T) * n, 0, false, dev);
+    }
+    // a [batch][stride] output of `per_slot` elements per slot, `slots` = batch * stride
+    template <typename T>
+    hipError_t out_slots(T *p, size_t slots, size_t per_slot, T *&dev, bool preload = false) {
+        return out_array(p, sizeof(T) * per_slot * slots, sizeof(T) * per_slot, preload, dev);
+    }
+    // counts: the call's host counts (the written prefix of every out_slots array)
+    int finish(const int32_t *counts, int batch, int32_t stride);
+
+  private:
+    hipError_t stage(const void *p, size_t bytes, bool upload, void *&dev);
+    template <typename T>
+    hipError_t out_array(T *p, size_t bytes, size_t slot_bytes, bool preload, T *&dev) {
+        void *d = nullptr;
+        const hipError_t e = stage(p, bytes, preload, d);
+        dev = static_cast<T *>(d);
+        if (e == hipSuccess && p && !dev_) (slot_bytes ? slots_ : whole_).push_back({p, d, slot_bytes ? slot_bytes : bytes});
+        return e;
+    }
+    fd_ctx *c_;
+    bool dev_;
+    int used_ = 0;
+    std::vector<SlotArray> whole_, slots_;  // host-side outputs: {host, staged, bytes (whole_) or bytes per slot (slots_)}
+};
+
+// A call without slots (stride 0): every frame's count is 0, on the side of the outputs.
+int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device);
+// k_flow_finish after zeroing its counts (fd_flow_lk, fd_points_refine).
+int finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin);
 
 // Host threads of the line stage and the PNG decoder (OMP_NUM_THREADS caps, FD_LINE_THREADS overrides).
 int default_line_threads();

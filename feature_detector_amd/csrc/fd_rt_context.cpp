@@ -2,7 +2,9 @@
 // grow-only device workspace, the status words) and the staging of host frames and prior features.
 // The stages are in fd_rt_points.cpp (point detectors), fd_rt_select.cpp (selection driver),
 // fd_rt_lsd.cpp (LSD map and lines), fd_rt_stages.cpp (PNG, BRIEF compute, NN), fd_rt_match.cpp (the two
-// descriptor matchers) and fd_rt_flow.cpp (pyramid, tracker); fd_ctx.h is their shared header.
+// descriptor matchers), fd_rt_flow.cpp (pyramid, tracker), fd_rt_refine.cpp (corner refinement) and
+// fd_rt_ransac.cpp (RANSAC); fd_ctx.h is their shared header. The keypoint stages' host-pointer calls all
+// go through one staging path, HostIo, below.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -141,8 +143,7 @@ int refuse_sync_under_capture(fd_ctx *c, int outputs_on_device) {
     return FD_OK;
 }
 
-int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t stride,
-                      std::initializer_list<SlotArray> arrays) {
+int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t stride, const std::vector<SlotArray> &arrays) {
     for (int b = 0; b < batch; ++b) {
         const int n = counts ? std::min<int64_t>(static_cast<uint32_t>(counts[b]) & fdk::kCountMask, stride) : stride;
         if (n <= 0) continue;
@@ -154,6 +155,30 @@ int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t strid
                                              hipMemcpyDeviceToHost, c->stream));
     }
     FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FD_OK;
+}
+
+hipError_t HostIo::stage(const void *p, size_t bytes, bool upload, void *&dev) {
+    dev = const_cast<void *>(p);
+    if (dev_ || !p) return hipSuccess;
+    if (used_ == fd_ctx::kStaging) return hipErrorInvalidValue;  // a call wider than the pool: a programming error
+    DevBuf &b = c_->staging[used_++];
+    const hipError_t e = ensure(c_, b, bytes);
+    if (e != hipSuccess) return e;
+    dev = b.p;
+    return upload && bytes ? hipMemcpyAsync(dev, p, bytes, hipMemcpyHostToDevice, c_->stream) : hipSuccess;
+}
+
+int HostIo::finish(const int32_t *counts, int batch, int32_t stride) {
+    if (dev_) return FD_OK;
+    for (const SlotArray &a : whole_)
+        FD_HIP_TRY(c_, hipMemcpyAsync(a.dst, a.src, a.slot_bytes, hipMemcpyDeviceToHost, c_->stream));
+    return copy_back_written(c_, counts, batch, stride, slots_);  // synchronises
+}
+
+int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device) {
+    if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+    if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
     return FD_OK;
 }
 

@@ -25,6 +25,12 @@ bool pyr_offsets(int batch, int rows, int cols, int levels, int64_t *off) {
 
 }  // namespace
 
+int fdrt::finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin) {
+    if (fin.out_counts) FD_HIP_TRY(c, hipMemsetAsync(fin.out_counts, 0, sizeof(int32_t) * fin.batch, c->stream));
+    FD_HIP_TRY(c, fdk::launch_flow_finish(fin, c->stream));
+    return FD_OK;
+}
+
 extern "C" {
 
 int fd_pyr_layout(int batch, int rows, int cols, int levels, int64_t *offsets) {
@@ -48,7 +54,7 @@ int fd_pyr_build(fd_ctx *c, const uint8_t *frames, int frames_on_device, int bat
     FD_HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = refuse_sync_under_capture(c, pyr_on_device && frames_on_device))) return rc;
     uint8_t *dpyr = pyr;
-    if (!pyr_on_device) FD_HIP_TRY(c, ensure_as(c, c->f_pyr, static_cast<size_t>(off[levels]), dpyr));
+    if (!pyr_on_device) FD_HIP_TRY(c, ensure_as(c, c->staging[0], static_cast<size_t>(off[levels]), dpyr));
     const size_t bytes0 = static_cast<size_t>(batch) * rows * cols;
     FD_HIP_TRY(c, hipMemcpyAsync(dpyr, frames, bytes0, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                  c->stream));
@@ -85,11 +91,7 @@ int fd_flow_lk(fd_ctx *c, int batch, int rows, int cols, int levels, const fd_fl
         return fail(c, FD_ERR_INVALID, "fb_max_dist and max_error must be finite");
     FD_HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = refuse_sync_under_capture(c, io_on_device))) return rc;
-    if (stride == 0) {  // no slots: every frame tracks 0 features
-        if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-        if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
-        return FD_OK;
-    }
+    if (stride == 0) return zero_counts(c, out_counts, batch, io_on_device);  // no slots: every frame tracks 0 features
     const size_t slots = static_cast<size_t>(batch) * stride;
     const int n = (2 * opts->half_window + 1) * (2 * opts->half_window + 1);
     const bool fb = opts->fb_max_dist >= 0.0f;
@@ -105,46 +107,22 @@ int fd_flow_lk(fd_ctx *c, int batch, int rows, int cols, int levels, const fd_fl
     a.eps2 = opts->epsilon * opts->epsilon;
     a.max_error = opts->max_error;
     a.tau = static_cast<double>(opts->min_eigen) * 1024.0 * n;
-    int32_t *dcounts_out = out_counts;
-    if (io_on_device) {
-        a.xy = xy;
-        a.valid = valid;
-        a.counts = counts;
-        a.guess = guess_xy;
-        a.out_xy = out_xy;
-        a.out_status = out_status;
-        a.out_err = out_err;
-    } else {
-        FD_HIP_TRY(c, ensure_as(c, c->f_xy, 2 * slots, a.xy));
-        FD_HIP_TRY(c, hipMemcpyAsync(c->f_xy.p, xy, sizeof(float) * 2 * slots, hipMemcpyHostToDevice, c->stream));
-        if (valid) {
-            FD_HIP_TRY(c, ensure_as(c, c->f_valid, slots, a.valid));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_valid.p, valid, slots, hipMemcpyHostToDevice, c->stream));
-        }
-        if (counts) {
-            FD_HIP_TRY(c, ensure_as(c, c->f_counts, batch, a.counts));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_counts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
-        }
-        if (guess_xy) {
-            FD_HIP_TRY(c, ensure_as(c, c->f_guess, 2 * slots, a.guess));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_guess.p, guess_xy, sizeof(float) * 2 * slots, hipMemcpyHostToDevice, c->stream));
-        }
-        FD_HIP_TRY(c, ensure_as(c, c->f_oxy, 2 * slots, a.out_xy));
-        FD_HIP_TRY(c, ensure_as(c, c->f_ost, slots, a.out_status));
-        if (out_err) {  // slots with valid 0 keep the caller's out_err: it goes up first
-            FD_HIP_TRY(c, ensure_as(c, c->f_oerr, slots, a.out_err));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_oerr.p, out_err, sizeof(float) * slots, hipMemcpyHostToDevice, c->stream));
-        }
-        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->f_ocnt, batch, dcounts_out));
-    }
-    FD_HIP_TRY(c, fdk::launch_flow_lk(a, c->stream));
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, io.in(xy, 2 * slots, a.xy));
+    FD_HIP_TRY(c, io.in(valid, slots, a.valid));
+    FD_HIP_TRY(c, io.in(counts, batch, a.counts));
+    FD_HIP_TRY(c, io.in(guess_xy, 2 * slots, a.guess));
+    FD_HIP_TRY(c, io.out_slots(out_xy, slots, 2, a.out_xy));
+    FD_HIP_TRY(c, io.out_slots(out_status, slots, 1, a.out_status));
+    FD_HIP_TRY(c, io.out_slots(out_err, slots, 1, a.out_err, true));  // slots with valid 0 keep the caller's out_err
     fdk::FlowFinishArgs fin{};
+    FD_HIP_TRY(c, io.out(out_counts, batch, fin.out_counts));
+    FD_HIP_TRY(c, fdk::launch_flow_lk(a, c->stream));
     fin.xy = a.xy;
     fin.status = a.out_status;
     fin.counts = a.counts;
     fin.batch = batch;
     fin.stride = stride;
-    fin.out_counts = dcounts_out;
     if (fb) {
         // the way back: from the forward result in the next frame towards xy in the previous one
         fdk::FlowArgs r = a;
@@ -167,17 +145,8 @@ int fd_flow_lk(fd_ctx *c, int batch, int rows, int cols, int levels, const fd_fl
         fin.back_status = bst;
         fin.fb2 = opts->fb_max_dist * opts->fb_max_dist;
     }
-    if (fb || dcounts_out) {
-        if (dcounts_out) FD_HIP_TRY(c, hipMemsetAsync(dcounts_out, 0, sizeof(int32_t) * batch, c->stream));
-        FD_HIP_TRY(c, fdk::launch_flow_finish(fin, c->stream));
-    }
-    if (!io_on_device) {
-        if (out_counts)
-            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, dcounts_out, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-        return copy_back_written(c, counts, batch, stride,
-                                 {{out_xy, a.out_xy, 2 * sizeof(float)}, {out_status, a.out_status, 1}, {out_err, a.out_err, sizeof(float)}});
-    }
-    return FD_OK;
+    if ((fb || fin.out_counts) && (rc = finish_counts(c, fin))) return rc;
+    return io.finish(counts, batch, stride);
 }
 
 }  // extern "C"

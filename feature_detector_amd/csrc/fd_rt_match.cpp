@@ -105,34 +105,15 @@ int check_gate(fd_ctx *c, const fd_match_gate *gate, const float *q_xy, const fl
     return FD_OK;
 }
 
-// Host-pointer calls: one set's three arrays into their staging buffers (absent ones stay null).
-int stage_side(fd_ctx *c, Side &s, size_t slot_bytes, size_t slots, int batch, DevBuf &ddesc, DevBuf &dvalid,
-               DevBuf &dcounts) {
-    FD_HIP_TRY(c, ensure(c, ddesc, slot_bytes * slots));
-    if (slots) FD_HIP_TRY(c, hipMemcpyAsync(ddesc.p, s.desc, slot_bytes * slots, hipMemcpyHostToDevice, c->stream));
-    s.desc = ddesc.p;
-    if (s.valid) {
-        FD_HIP_TRY(c, ensure(c, dvalid, slots));
-        if (slots) FD_HIP_TRY(c, hipMemcpyAsync(dvalid.p, s.valid, slots, hipMemcpyHostToDevice, c->stream));
-        s.valid = as<uint8_t>(dvalid);
-    }
-    if (s.counts) {
-        FD_HIP_TRY(c, ensure(c, dcounts, sizeof(int32_t) * batch));
-        FD_HIP_TRY(c, hipMemcpyAsync(dcounts.p, s.counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
-        s.counts = as<int32_t>(dcounts);
-    }
-    return FD_OK;
-}
-
-// Host-pointer guided calls: both position arrays into their staging buffers.
-int stage_gate_xy(fd_ctx *c, Side &q, size_t qslots, Side &t, size_t tslots) {
-    FD_HIP_TRY(c, ensure(c, c->m_qxy, sizeof(float) * 2 * qslots));
-    FD_HIP_TRY(c, ensure(c, c->m_txy, sizeof(float) * 2 * tslots));
-    if (qslots) FD_HIP_TRY(c, hipMemcpyAsync(c->m_qxy.p, q.xy, sizeof(float) * 2 * qslots, hipMemcpyHostToDevice, c->stream));
-    if (tslots) FD_HIP_TRY(c, hipMemcpyAsync(c->m_txy.p, t.xy, sizeof(float) * 2 * tslots, hipMemcpyHostToDevice, c->stream));
-    q.xy = as<float>(c->m_qxy);
-    t.xy = as<float>(c->m_txy);
-    return FD_OK;
+// One set's arrays as the kernels take them: the caller's device pointers, or their staged copies.
+hipError_t stage_side(HostIo &io, Side &s, size_t slot_bytes, size_t slots, int batch) {
+    const uint8_t *desc = static_cast<const uint8_t *>(s.desc);
+    hipError_t e = io.in(desc, slot_bytes * slots, desc);
+    s.desc = desc;
+    if (e == hipSuccess) e = io.in(s.valid, slots, s.valid);
+    if (e == hipSuccess) e = io.in(s.counts, batch, s.counts);
+    if (e == hipSuccess) e = io.in(s.xy, 2 * slots, s.xy);
+    return e;
 }
 
 // A matcher call. With cross_check the kernel runs twice, first with the roles swapped into the reverse
@@ -142,7 +123,7 @@ int stage_gate_xy(fd_ctx *c, Side &q, size_t qslots, Side &t, size_t tslots) {
 template <class M>
 int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match_gate *gate, Side q, Side t,
               int32_t *out_idx, decltype(M::Args::out_dist) out_dist, int32_t *out_counts, int io_on_device) {
-    const int32_t *host_counts = q.counts;  // (of a host-pointer call: q and t are staged below)
+    const int32_t *host_counts = q.counts;  // (q and t are staged below)
     if (!opts || !q.desc || !t.desc || !out_idx) return fail(c, FD_ERR_INVALID, "bad arguments");
     int rc = check_gate(c, gate, q.xy, t.xy);
     if (rc) return rc;
@@ -150,25 +131,15 @@ int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match
     if ((rc = M::check(c, *opts))) return rc;
     FD_HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = refuse_sync_under_capture(c, io_on_device))) return rc;
-    if (q.stride == 0) {  // no query slots: every frame has 0 matches
-        if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-        if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
-        return FD_OK;
-    }
+    if (q.stride == 0) return zero_counts(c, out_counts, batch, io_on_device);  // no query slots: every frame has 0 matches
     const size_t qslots = static_cast<size_t>(batch) * q.stride, tslots = static_cast<size_t>(batch) * t.stride;
     typename M::Args a{};
-    a.out_idx = out_idx;
-    a.out_dist = out_dist;
-    a.out_counts = out_counts;
-    if (!io_on_device) {
-        const size_t bytes = M::slot_bytes(*opts);
-        if ((rc = stage_side(c, q, bytes, qslots, batch, c->m_qbits, c->m_qvalid, c->m_qcounts))) return rc;
-        if ((rc = stage_side(c, t, bytes, tslots, batch, c->m_tbits, c->m_tvalid, c->m_tcounts))) return rc;
-        if (gate && (rc = stage_gate_xy(c, q, qslots, t, tslots))) return rc;
-        FD_HIP_TRY(c, ensure_as(c, c->m_idx, qslots, a.out_idx));
-        if (out_dist) FD_HIP_TRY(c, ensure_as(c, c->m_dist, 2 * qslots, a.out_dist));
-        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->m_counts, batch, a.out_counts));
-    }
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, stage_side(io, q, M::slot_bytes(*opts), qslots, batch));
+    FD_HIP_TRY(c, stage_side(io, t, M::slot_bytes(*opts), tslots, batch));
+    FD_HIP_TRY(c, io.out_slots(out_idx, qslots, 1, a.out_idx));
+    FD_HIP_TRY(c, io.out_slots(out_dist, qslots, 2, a.out_dist));
+    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
     a.a_counts = q.counts;
     a.b_counts = t.counts;
     a.a_stride = q.stride;
@@ -190,13 +161,7 @@ int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match
     }
     if (a.out_counts) FD_HIP_TRY(c, hipMemsetAsync(a.out_counts, 0, sizeof(int32_t) * batch, c->stream));
     FD_HIP_TRY(c, M::launch(a, c->stream));
-    if (!io_on_device) {
-        if (out_counts)
-            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-        return copy_back_written(c, host_counts, batch, q.stride,
-                                 {{out_idx, a.out_idx, sizeof(int32_t)}, {out_dist, a.out_dist, 2 * sizeof(*out_dist)}});
-    }
-    return FD_OK;
+    return io.finish(host_counts, batch, q.stride);
 }
 
 }  // namespace

@@ -60,48 +60,18 @@ int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_x
     FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
     FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 9, a.models));
     FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
-    if (io_on_device) {
-        a.q_xy = q_xy;
-        a.t_xy = t_xy;
-        a.q_counts = q_counts;
-        a.match_idx = match_idx;
-        a.pair_valid = pair_valid;
-        a.out_model = out_model;
-        a.out_inlier = out_inlier;
-        a.out_counts = out_counts;
-        a.out_best = out_best;
-    } else {
-        FD_HIP_TRY(c, ensure_as(c, c->g_qxy, 2 * qs, a.q_xy));
-        FD_HIP_TRY(c, hipMemcpyAsync(c->g_qxy.p, q_xy, sizeof(float) * 2 * qs, hipMemcpyHostToDevice, c->stream));
-        FD_HIP_TRY(c, ensure_as(c, c->g_txy, 2 * ts, a.t_xy));
-        if (ts) FD_HIP_TRY(c, hipMemcpyAsync(c->g_txy.p, t_xy, sizeof(float) * 2 * ts, hipMemcpyHostToDevice, c->stream));
-        if (q_counts) {
-            FD_HIP_TRY(c, ensure_as(c, c->g_counts, batch, a.q_counts));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->g_counts.p, q_counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
-        }
-        if (match_idx) {
-            FD_HIP_TRY(c, ensure_as(c, c->g_idx, qs, a.match_idx));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->g_idx.p, match_idx, sizeof(int32_t) * qs, hipMemcpyHostToDevice, c->stream));
-        }
-        if (pair_valid) {
-            FD_HIP_TRY(c, ensure_as(c, c->g_valid, qs, a.pair_valid));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->g_valid.p, pair_valid, qs, hipMemcpyHostToDevice, c->stream));
-        }
-        FD_HIP_TRY(c, ensure_as(c, c->g_omodel, static_cast<size_t>(9) * batch, a.out_model));
-        if (out_inlier) FD_HIP_TRY(c, ensure_as(c, c->g_oinl, qs, a.out_inlier));
-        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->g_ocnt, batch, a.out_counts));
-        if (out_best) FD_HIP_TRY(c, ensure_as(c, c->g_obest, batch, a.out_best));
-    }
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, a.q_xy));
+    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
+    FD_HIP_TRY(c, io.in(q_counts, batch, a.q_counts));
+    FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
+    FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
+    FD_HIP_TRY(c, io.out(out_model, static_cast<size_t>(9) * batch, a.out_model));
+    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
+    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
+    FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
     FD_HIP_TRY(c, fdk::launch_ransac(a, c->stream));
-    if (!io_on_device) {
-        FD_HIP_TRY(c, hipMemcpyAsync(out_model, a.out_model, sizeof(double) * 9 * batch, hipMemcpyDeviceToHost, c->stream));
-        if (out_counts)
-            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, a.out_counts, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-        if (out_best)
-            FD_HIP_TRY(c, hipMemcpyAsync(out_best, a.out_best, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-        return copy_back_written(c, q_counts, batch, q_stride, {{out_inlier, a.out_inlier, 1}});  // synchronises
-    }
-    return FD_OK;
+    return io.finish(q_counts, batch, q_stride);
 }
 
 }  // extern "C"

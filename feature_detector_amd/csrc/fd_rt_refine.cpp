@@ -25,11 +25,7 @@ int fd_points_refine(fd_ctx *c, const uint8_t *frames, int frames_on_device, int
         return fail(c, FD_ERR_INVALID, "max_shift must be finite and > 0");
     FD_HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = refuse_sync_under_capture(c, io_on_device && frames_on_device))) return rc;
-    if (stride == 0) {  // no slots: every frame refines 0 features
-        if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-        if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
-        return FD_OK;
-    }
+    if (stride == 0) return zero_counts(c, out_counts, batch, io_on_device);  // no slots: every frame refines 0 features
     const size_t slots = static_cast<size_t>(batch) * stride;
     const int r1 = opts->half_window + 1;
     fdk::RefineArgs a{};
@@ -43,45 +39,24 @@ int fd_points_refine(fd_ctx *c, const uint8_t *frames, int frames_on_device, int
     a.eps2 = opts->epsilon * opts->epsilon;
     a.max_shift = opts->max_shift;
     a.tau = static_cast<double>(opts->min_eigen) * 1024.0 * static_cast<double>(r1 * r1 * r1 * r1);
-    int32_t *dcounts_out = out_counts;
-    if (io_on_device) {
-        a.xy = xy;
-        a.valid = valid;
-        a.counts = counts;
-        a.out_xy = out_xy;
-        a.out_status = out_status;
-    } else {  // the tracker's staging buffers: the two stages never overlap on one context
-        FD_HIP_TRY(c, ensure_as(c, c->f_xy, 2 * slots, a.xy));
-        FD_HIP_TRY(c, hipMemcpyAsync(c->f_xy.p, xy, sizeof(float) * 2 * slots, hipMemcpyHostToDevice, c->stream));
-        if (valid) {
-            FD_HIP_TRY(c, ensure_as(c, c->f_valid, slots, a.valid));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_valid.p, valid, slots, hipMemcpyHostToDevice, c->stream));
-        }
-        if (counts) {
-            FD_HIP_TRY(c, ensure_as(c, c->f_counts, batch, a.counts));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->f_counts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
-        }
-        FD_HIP_TRY(c, ensure_as(c, c->f_oxy, 2 * slots, a.out_xy));
-        FD_HIP_TRY(c, ensure_as(c, c->f_ost, slots, a.out_status));
-        if (out_counts) FD_HIP_TRY(c, ensure_as(c, c->f_ocnt, batch, dcounts_out));
-    }
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, io.in(xy, 2 * slots, a.xy));
+    FD_HIP_TRY(c, io.in(valid, slots, a.valid));
+    FD_HIP_TRY(c, io.in(counts, batch, a.counts));
+    FD_HIP_TRY(c, io.out_slots(out_xy, slots, 2, a.out_xy));  // (its own buffer, also where out_xy == xy)
+    FD_HIP_TRY(c, io.out_slots(out_status, slots, 1, a.out_status));
+    fdk::FlowFinishArgs fin{};
+    FD_HIP_TRY(c, io.out(out_counts, batch, fin.out_counts));
     FD_HIP_TRY(c, fdk::launch_refine(a, c->stream));
-    if (dcounts_out) {
-        fdk::FlowFinishArgs fin{};
+    if (fin.out_counts) {
         fin.status = a.out_status;
         fin.counts = a.counts;
         fin.batch = batch;
         fin.stride = stride;
-        fin.out_counts = dcounts_out;
-        FD_HIP_TRY(c, hipMemsetAsync(dcounts_out, 0, sizeof(int32_t) * batch, c->stream));
-        FD_HIP_TRY(c, fdk::launch_flow_finish(fin, c->stream));
+        if ((rc = finish_counts(c, fin))) return rc;
     }
-    if (!io_on_device) {
-        if (out_counts)
-            FD_HIP_TRY(c, hipMemcpyAsync(out_counts, dcounts_out, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, c->stream));
-        return copy_back_written(c, counts, batch, stride, {{out_xy, a.out_xy, 2 * sizeof(float)}, {out_status, a.out_status, 1}});
-    }
-    if (!frames_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's frames have been read
+    if ((rc = io.finish(counts, batch, stride))) return rc;
+    if (io_on_device && !frames_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's frames have been read
     return FD_OK;
 }
 

@@ -102,29 +102,14 @@ int fd_brief_compute(fd_ctx *c, const uint8_t *frames, int frames_on_device, int
     a.length = opts->length;
     a.half = opts->half_patch_size;
     a.sampler = opts->sampler;
-    if (io_on_device) {
-        a.uv = uv;
-        a.counts = counts;
-        a.out_bits = out_bits;
-        a.out_valid = out_valid;
-    } else {
-        FD_HIP_TRY(c, ensure_as(c, c->b_uv, 2 * slots, a.uv));
-        FD_HIP_TRY(c, ensure_as(c, c->b_bits, nw * slots, a.out_bits));
-        FD_HIP_TRY(c, hipMemcpyAsync(c->b_uv.p, uv, sizeof(float) * 2 * slots, hipMemcpyHostToDevice, c->stream));
-        if (counts) {
-            FD_HIP_TRY(c, ensure_as(c, c->b_counts, batch, a.counts));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->b_counts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice,
-                                         c->stream));
-        }
-        if (out_valid) FD_HIP_TRY(c, ensure_as(c, c->b_valid, slots, a.out_valid));
-    }
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, io.in(uv, 2 * slots, a.uv));
+    FD_HIP_TRY(c, io.in(counts, batch, a.counts));
+    FD_HIP_TRY(c, io.out_slots(out_bits, slots, nw, a.out_bits));
+    FD_HIP_TRY(c, io.out_slots(out_valid, slots, 1, a.out_valid));
     FD_HIP_TRY(c, fdk::launch_brief(a, c->stream));
-    if (!io_on_device) {
-        return copy_back_written(c, counts, batch, stride,
-                                 {{out_bits, a.out_bits, sizeof(uint32_t) * nw}, {out_valid, a.out_valid, 1}});
-    } else if (!frames_on_device) {
-        FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host frames must stay valid until copied
-    }
+    if ((rc = io.finish(counts, batch, stride))) return rc;
+    if (io_on_device && !frames_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host frames must stay valid until copied
     return FD_OK;
 }
 
@@ -391,25 +376,13 @@ int fd_nn_descriptors(fd_ctx *c, const float *map, int map_on_device, int map_la
         FD_HIP_TRY(c, ensure_as(c, c->n_map, mapn, a.map));
         FD_HIP_TRY(c, hipMemcpyAsync(c->n_map.p, map, sizeof(float) * mapn, hipMemcpyHostToDevice, c->stream));
     }
-    if (io_on_device) {
-        a.xy = xy;
-        a.counts = counts;
-        a.out = out;
-    } else {
-        FD_HIP_TRY(c, ensure_as(c, c->n_xy, 2 * slots, a.xy));
-        FD_HIP_TRY(c, ensure_as(c, c->n_out, channels * slots, a.out));
-        FD_HIP_TRY(c, hipMemcpyAsync(c->n_xy.p, xy, sizeof(float) * 2 * slots, hipMemcpyHostToDevice, c->stream));
-        if (counts) {
-            FD_HIP_TRY(c, ensure_as(c, c->n_counts, batch, a.counts));
-            FD_HIP_TRY(c, hipMemcpyAsync(c->n_counts.p, counts, sizeof(int32_t) * batch, hipMemcpyHostToDevice, c->stream));
-        }
-    }
+    HostIo io(c, io_on_device);
+    FD_HIP_TRY(c, io.in(xy, 2 * slots, a.xy));
+    FD_HIP_TRY(c, io.in(counts, batch, a.counts));
+    FD_HIP_TRY(c, io.out_slots(out, slots, channels, a.out));
     FD_HIP_TRY(c, fdk::launch_nn_desc(a, c->stream));
-    if (!io_on_device) {
-        return copy_back_written(c, counts, batch, stride, {{out, a.out, sizeof(float) * channels}});
-    } else if (!map_on_device) {
-        FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if (const int rc = io.finish(counts, batch, stride)) return rc;
+    if (io_on_device && !map_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FD_OK;
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import FD_SAMPLE_BILINEAR, FD_SAMPLE_TRUNCATE, fd_brief_opts
+from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
 
 SAMPLERS = {"bilinear": FD_SAMPLE_BILINEAR, "truncate": FD_SAMPLE_TRUNCATE}
@@ -36,46 +37,21 @@ def brief_compute(frames, uv, counts=None, length: int = 256, half_patch_size: i
     ctx = _resolve_ctx(ctx, frames, uv)
     nw = (int(length) + 31) // 32
     opts = fd_brief_opts(int(length), int(half_patch_size), smp)
-    if _is_torch_device_tensor(uv):
-        import torch
-
-        uv_t = uv.to(torch.float32).contiguous()
-        if uv_t.dim() == 2:
-            uv_t = uv_t.unsqueeze(0)
-        if uv_t.shape[0] != b or uv_t.shape[2] != 2:
-            raise ValueError("uv must be [batch, S, 2] matching frames")
-        s = int(uv_t.shape[1])
-        cnt_t = None if counts is None else counts.to(torch.int32).contiguous()
-        if out is not None:
-            if tuple(out.shape) != (b, s, nw) or out.dtype != torch.int32 or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous int32 tensor of shape {(b, s, nw)}")
-            bits = out
-        else:
-            bits = torch.zeros((b, s, nw), dtype=torch.int32, device=uv_t.device)
-        valid = torch.zeros((b, s), dtype=torch.uint8, device=uv_t.device) if with_valid else None
-        _bind_stream(ctx, True)
-        rc = _lib.load().fd_brief_compute(
-            ctx.ptr, ctypes.c_void_p(fptr), f_on_dev, b, r, c, ctypes.byref(opts), ctypes.c_void_p(uv_t.data_ptr()),
-            ctypes.c_void_p(cnt_t.data_ptr()) if cnt_t is not None else None, s, ctypes.c_void_p(bits.data_ptr()),
-            ctypes.c_void_p(valid.data_ptr()) if valid is not None else None, 1)
-        _lib.check(ctx.ptr, rc)
-        del keep_f
-        return (bits, valid) if with_valid else bits
-    uv_h = np.asarray(uv, np.float32)
-    if uv_h.ndim == 2:
-        uv_h = uv_h[None]
-    uv_h = np.ascontiguousarray(uv_h)
-    if uv_h.shape[0] != b or uv_h.shape[2] != 2:
-        raise ValueError("uv must be [batch, S, 2] matching frames")
-    s = int(uv_h.shape[1])
-    cnt_h = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
-    bits = np.zeros((b, s, nw), np.uint32)
-    valid = np.zeros((b, s), np.uint8) if with_valid else None
-    _bind_stream(ctx, bool(f_on_dev))
-    rc = _lib.load().fd_brief_compute(
-        ctx.ptr, ctypes.c_void_p(fptr), f_on_dev, b, r, c, ctypes.byref(opts), ctypes.c_void_p(uv_h.ctypes.data),
-        ctypes.c_void_p(cnt_h.ctypes.data) if cnt_h is not None else None, s, ctypes.c_void_p(bits.ctypes.data),
-        ctypes.c_void_p(valid.ctypes.data) if valid is not None else None, 0)
+    on_dev = _is_torch_device_tensor(uv)
+    msg = "uv must be [batch, S, 2] matching frames"
+    puv = positions(uv, "uv", on_dev, convert=True, msg=msg)
+    if puv.shape[0] != b:
+        raise ValueError(msg)
+    s = int(puv.shape[1])
+    cn = slot_arg(counts, "int32", (b,), on_dev)
+    dev = puv.device if on_dev else None
+    # (device words are int32: torch has no uint32 arithmetic; host calls take no out= and ignore one)
+    bits, = outputs([((b, s, nw), "int32" if on_dev else "uint32", 0)], (out,) if on_dev and out is not None else None,
+                    on_dev, dev, f"out must be a contiguous int32 tensor of shape {(b, s, nw)}")
+    valid = outputs([((b, s), "uint8", 0)], None, on_dev, dev)[0] if with_valid else None
+    _bind_stream(ctx, on_dev or bool(f_on_dev))
+    rc = _lib.load().fd_brief_compute(ctx.ptr, ctypes.c_void_p(fptr), f_on_dev, b, r, c, ctypes.byref(opts), ptr(puv), ptr(cn),
+                                      s, ptr(bits), ptr(valid), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     del keep_f
     return (bits, valid) if with_valid else bits

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import fd_flow_opts
+from ._slots import f32, outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
 
 
@@ -41,12 +42,6 @@ class Pyramid:
         return self.data[self.offsets[l]:self.offsets[l] + self.batch * r * c].reshape(self.batch, r, c)
 
 
-def _ptr(x):
-    if x is None:
-        return None
-    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
-
-
 def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_out: bool | None = None) -> Pyramid:
     """fd_pyr_build for a batch of uint8 frames [B, rows, cols] (or [rows, cols]): level 0 is the frames,
     every further level the rounded 2 x 2 box mean of the one below it.
@@ -55,7 +50,7 @@ def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_ou
     copy: graph-capturable). Host (numpy) frames give a numpy pyramid, or with device_out=True a device
     pyramid (what track_lk builds from host frames).
     """
-    ptr, on_dev, b, r, c, keep = _frames(frames)
+    fptr, on_dev, b, r, c, keep = _frames(frames)
     ctx = _resolve_ctx(ctx, frames)
     off = pyramid_layout(b, r, c, levels)
     dev_out = bool(on_dev) if device_out is None else bool(device_out)
@@ -68,7 +63,7 @@ def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_ou
     else:
         data = np.zeros((off[-1],), np.uint8)
     _bind_stream(ctx, bool(on_dev))
-    rc = _lib.load().fd_pyr_build(ctx.ptr, ctypes.c_void_p(ptr), on_dev, b, r, c, int(levels), _ptr(data), 1 if dev_out else 0)
+    rc = _lib.load().fd_pyr_build(ctx.ptr, ctypes.c_void_p(fptr), on_dev, b, r, c, int(levels), ptr(data), 1 if dev_out else 0)
     _lib.check(ctx.ptr, rc)
     return Pyramid(data, b, r, c, int(levels), off)
 
@@ -118,23 +113,7 @@ def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 
     on_dev = _is_torch_device_tensor(xy)
     ctx = _resolve_ctx(ctx, xy, prev.data if isinstance(prev, Pyramid) else prev,
                        next.data if isinstance(next, Pyramid) else next)
-    if on_dev:
-        import torch
-
-        if xy.dtype != torch.float32:
-            raise TypeError("xy must be float32")
-        pxy = xy.contiguous()
-        if pxy.dim() == 2:
-            pxy = pxy.unsqueeze(0)
-    else:
-        pxy = np.asarray(xy)
-        if pxy.dtype != np.float32:
-            raise TypeError("xy must be float32")
-        pxy = np.ascontiguousarray(pxy)
-        if pxy.ndim == 2:
-            pxy = pxy[None]
-    if len(pxy.shape) != 3 or pxy.shape[2] != 2:
-        raise ValueError("xy must be [batch, S, 2] or [S, 2]")
+    pxy = positions(xy, "xy", on_dev)
     b, s = int(pxy.shape[0]), int(pxy.shape[1])
     pp, pn = _device_pyramid(prev, levels, ctx, "prev"), _device_pyramid(next, levels, ctx, "next")
     if (pp.batch, pp.rows, pp.cols) != (pn.batch, pn.rows, pn.cols):
@@ -143,44 +122,15 @@ def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 
         raise ValueError("xy and the frames must have the same batch")
     if guess is not None and _is_torch_device_tensor(guess) != on_dev:
         raise ValueError("guess must be on the side (host / device) of xy")
-    if on_dev:
-        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
-        cn = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
-        g = None
-        if guess is not None:
-            if guess.dtype != torch.float32:
-                raise TypeError("guess must be float32")
-            g = guess.contiguous().reshape(b, s, 2)
-        if out is not None:
-            oxy, ost, oerr, ocnt = out
-            for t, shape, dt in ((oxy, (b, s, 2), torch.float32), (ost, (b, s), torch.uint8), (oerr, (b, s), torch.float32),
-                                 (ocnt, (b,), torch.int32)):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-                    raise ValueError(f"out must be contiguous tensors: float32 {(b, s, 2)}, uint8 {(b, s)}, "
-                                     f"float32 {(b, s)}, int32 {(b,)}")
-        else:
-            oxy = torch.zeros((b, s, 2), dtype=torch.float32, device=pxy.device)
-            ost = torch.zeros((b, s), dtype=torch.uint8, device=pxy.device)
-            oerr = torch.zeros((b, s), dtype=torch.float32, device=pxy.device)
-            ocnt = torch.zeros((b,), dtype=torch.int32, device=pxy.device)
-    else:
-        if out is not None:
-            raise ValueError("out= is for device tensors")
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
-        cn = None if counts is None else np.ascontiguousarray(np.asarray(counts).astype(np.int32).reshape(b))
-        g = None
-        if guess is not None:
-            g = np.asarray(guess)
-            if g.dtype != np.float32:
-                raise TypeError("guess must be float32")
-            g = np.ascontiguousarray(g).reshape(b, s, 2)
-        oxy, ost = np.zeros((b, s, 2), np.float32), np.zeros((b, s), np.uint8)
-        oerr, ocnt = np.zeros((b, s), np.float32), np.zeros((b,), np.int32)
+    v, cn = slot_arg(valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev)
+    g = None if guess is None else f32(guess, "guess", on_dev).reshape(b, s, 2)
+    oxy, ost, oerr, ocnt = outputs((((b, s, 2), "float32", 0), ((b, s), "uint8", 0), ((b, s), "float32", 0),
+                                    ((b,), "int32", 0)), out, on_dev, pxy.device if on_dev else None)
     opts = fd_flow_opts(int(half_window), int(max_iters), float(epsilon), float(min_eigen), float(fb_max_dist),
                         float(max_error))
     _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_flow_lk(ctx.ptr, b, pp.rows, pp.cols, int(levels), ctypes.byref(opts), _ptr(pp.data), _ptr(pn.data),
-                                _ptr(pxy), _ptr(v), _ptr(cn), s, _ptr(g), _ptr(oxy), _ptr(ost), _ptr(oerr), _ptr(ocnt),
+    rc = _lib.load().fd_flow_lk(ctx.ptr, b, pp.rows, pp.cols, int(levels), ctypes.byref(opts), ptr(pp.data), ptr(pn.data),
+                                ptr(pxy), ptr(v), ptr(cn), s, ptr(g), ptr(oxy), ptr(ost), ptr(oerr), ptr(ocnt),
                                 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return FlowResult(oxy, ost, oerr, ocnt)

@@ -10,10 +10,9 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 
-import numpy as np
-
 from . import _lib
 from ._lib import fd_ransac_opts
+from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
 MODELS = {"fundamental": _lib.FD_RANSAC_FUNDAMENTAL, "homography": _lib.FD_RANSAC_HOMOGRAPHY}
@@ -25,12 +24,6 @@ class GeometryResult:
     inliers: object  # uint8 [B, S]: 1 = a correspondence the model classifies as an inlier
     counts: object   # int32 [B]: inliers per frame
     best: object     # int32 [B]: the winning hypothesis, -1: no model
-
-
-def _ptr(x):
-    if x is None:
-        return None
-    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
 
 
 def conditioning(image_size=None):
@@ -69,61 +62,21 @@ def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: st
         raise ValueError("t_xy must be on the side (host / device) of q_xy")
     ctx = _resolve_ctx(ctx, q_xy, t_xy)
 
-    def positions(x, name):
-        if on_dev:
-            import torch
-
-            if x.dtype != torch.float32:
-                raise TypeError(f"{name} must be float32")
-            x = x.contiguous()
-            x = x.unsqueeze(0) if x.dim() == 2 else x
-        else:
-            x = np.asarray(x)
-            if x.dtype != np.float32:
-                raise TypeError(f"{name} must be float32")
-            x = np.ascontiguousarray(x)
-            x = x[None] if x.ndim == 2 else x
-        if len(x.shape) != 3 or x.shape[2] != 2:
-            raise ValueError(f"{name} must be [batch, S, 2] or [S, 2]")
-        return x
-
-    pq, pt = positions(q_xy, "q_xy"), positions(t_xy, "t_xy")
+    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
     b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
     if int(pt.shape[0]) != b:
         raise ValueError("q_xy and t_xy must have the same batch")
     if matches is None and ts < s:
         raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
-    if on_dev:
-        import torch
-
-        mi = None if matches is None else matches.to(torch.int32).contiguous().reshape(b, s)
-        v = None if valid is None else valid.to(torch.uint8).contiguous().reshape(b, s)
-        cn = None if counts is None else counts.to(torch.int32).contiguous().reshape(b)
-        if out is not None:
-            om, oi, oc, ob = out
-            for t, shape, dt in ((om, (b, 9), torch.float64), (oi, (b, s), torch.uint8), (oc, (b,), torch.int32),
-                                 (ob, (b,), torch.int32)):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
-                    raise ValueError(f"out must be contiguous tensors: float64 {(b, 9)}, uint8 {(b, s)}, int32 {(b,)}, "
-                                     f"int32 {(b,)}")
-        else:
-            om = torch.zeros((b, 9), dtype=torch.float64, device=pq.device)
-            oi = torch.zeros((b, s), dtype=torch.uint8, device=pq.device)
-            oc = torch.zeros((b,), dtype=torch.int32, device=pq.device)
-            ob = torch.zeros((b,), dtype=torch.int32, device=pq.device)
-    else:
-        if out is not None:
-            raise ValueError("out= is for device tensors")
-        mi = None if matches is None else np.ascontiguousarray(np.asarray(matches).astype(np.int32).reshape(b, s))
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
-        cn = None if counts is None else np.ascontiguousarray(np.asarray(counts).astype(np.int32).reshape(b))
-        om, oi = np.zeros((b, 9), np.float64), np.zeros((b, s), np.uint8)
-        oc, ob = np.zeros((b,), np.int32), np.zeros((b,), np.int32)
+    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
+    cn = slot_arg(counts, "int32", (b,), on_dev)
+    om, oi, oc, ob = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
+                             on_dev, pq.device if on_dev else None)
     (cx, cy), scale = conditioning(image_size)
     opts = fd_ransac_opts(MODELS[model], int(hypotheses), int(seed) & 0xFFFFFFFF, float(threshold), float(cx), float(cy),
                           float(scale))
     _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_ransac(ctx.ptr, b, ctypes.byref(opts), _ptr(pq), _ptr(cn), s, _ptr(pt), ts, _ptr(mi), _ptr(v),
-                               _ptr(om), _ptr(oi), _ptr(oc), _ptr(ob), 1 if on_dev else 0)
+    rc = _lib.load().fd_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
+                               ptr(om), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return GeometryResult(om, oi, oc, ob)

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import fd_match_gate, fd_match_opts, fd_nn_match_opts
+from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
 
@@ -25,12 +26,6 @@ class MatchResult:
     idx: object     # int32 [B, Sq]: accepted train index per query slot, else -1
     dist: object    # [B, Sq, 2]: raw best / second-best distance (-1: absent); int32 (brief_match) or float32 (nn_match)
     counts: object  # int32 [B]: accepted matches per frame
-
-
-def _ptr(x):
-    if x is None:
-        return None
-    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data)
 
 
 def _guided(q_xy, t_xy, radius) -> bool:
@@ -53,20 +48,10 @@ def _gate(q_xy, t_xy, radius, on_dev, b, sq, st):
     for xy, s, name in ((q_xy, sq, "q"), (t_xy, st, "t")):
         if _is_torch_device_tensor(xy) != on_dev:
             raise ValueError(f"{name}_xy must be on the side (host / device) of the descriptors")
-        if on_dev:
-            import torch
-
-            if xy.dtype != torch.float32:
-                raise TypeError(f"{name}_xy must be float32")
-            p = xy.contiguous()
-        else:
-            p = np.asarray(xy)
-            if p.dtype != np.float32:
-                raise TypeError(f"{name}_xy must be float32")
-            p = np.ascontiguousarray(p)
-        shape = tuple(int(d) for d in p.shape)
-        if shape != (b, s, 2) and not (b == 1 and shape == (s, 2)):
-            raise ValueError(f"{name}_xy must be [{b}, {s}, 2]" + (f" or [{s}, 2]" if b == 1 else ""))
+        msg = f"{name}_xy must be [{b}, {s}, 2]" + (f" or [{s}, 2]" if b == 1 else "")
+        p = positions(xy, f"{name}_xy", on_dev, msg=msg)
+        if tuple(int(d) for d in p.shape) != (b, s, 2):
+            raise ValueError(msg)
         sides.append(p)
     return fd_match_gate(rx, ry), sides[0], sides[1]
 
@@ -82,45 +67,24 @@ def _side(x, valid, counts, on_dev, name, check):
         x = x[None]
     check(x, xp, name)
     b, s = int(x.shape[0]), int(x.shape[1])
-    if on_dev:
-        x = x.contiguous()
-        v = None if valid is None else valid.to(xp.uint8).contiguous().reshape(b, s)
-        c = None if counts is None else counts.to(xp.int32).contiguous().reshape(b)
-    else:
-        x = np.ascontiguousarray(x)
-        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, np.uint8).reshape(b, s))
-        c = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
-    return x, v, c, b, s
+    x = x.contiguous() if on_dev else np.ascontiguousarray(x)
+    return x, slot_arg(valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev), b, s
 
 
-def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg):
+def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg=None):
     """What both matchers end with: the outputs (dist: the distances' dtype name; out: the caller's tensors,
-    checked against out_msg's shapes), then the entry point `entry`, or with a gate `entry`_guided."""
+    checked against their shapes), then the entry point `entry`, or with a gate `entry`_guided."""
     (qx, qv, qc, b, sq), (tx, tv, tc, _, st) = q, t
-    shapes = ((b, sq), (b, sq, 2), (b,))
-    if on_dev:
-        import torch
-
-        if out is not None:
-            idx, dst, counts = out
-            for ten, shape, dt in zip(out, shapes, (torch.int32, getattr(torch, dist), torch.int32)):
-                if tuple(ten.shape) != shape or ten.dtype != dt or not ten.is_contiguous():
-                    raise ValueError(out_msg.format(*shapes))
-        else:
-            idx = torch.full(shapes[0], -1, dtype=torch.int32, device=qx.device)
-            dst = torch.full(shapes[1], -1, dtype=getattr(torch, dist), device=qx.device)
-            counts = torch.zeros(shapes[2], dtype=torch.int32, device=qx.device)
-    else:
-        if out is not None:
-            raise ValueError("out= is for device tensors")
-        idx, dst, counts = np.full(shapes[0], -1, np.int32), np.full(shapes[1], -1, dist), np.zeros(shapes[2], np.int32)
+    specs = (((b, sq), "int32", -1), ((b, sq, 2), dist, -1), ((b,), "int32", 0))
+    idx, dst, counts = outputs(specs, out, on_dev, qx.device if on_dev else None,
+                               out_msg and out_msg.format(*(shape for shape, _, _ in specs)))
     _bind_stream(ctx, on_dev)
-    head, outs = (ctx.ptr, b, ctypes.byref(opts)), (_ptr(idx), _ptr(dst), _ptr(counts), 1 if on_dev else 0)
-    qa, ta = (_ptr(qx), _ptr(qv), _ptr(qc), sq), (_ptr(tx), _ptr(tv), _ptr(tc), st)
+    head, outs = (ctx.ptr, b, ctypes.byref(opts)), (ptr(idx), ptr(dst), ptr(counts), 1 if on_dev else 0)
+    qa, ta = (ptr(qx), ptr(qv), ptr(qc), sq), (ptr(tx), ptr(tv), ptr(tc), st)
     if gate is None:
         rc = getattr(_lib.load(), entry)(*head, *qa, *ta, *outs)
     else:
-        rc = getattr(_lib.load(), entry + "_guided")(*head, ctypes.byref(gate[0]), *qa, _ptr(gate[1]), *ta, _ptr(gate[2]),
+        rc = getattr(_lib.load(), entry + "_guided")(*head, ctypes.byref(gate[0]), *qa, ptr(gate[1]), *ta, ptr(gate[2]),
                                                      *outs)
     _lib.check(ctx.ptr, rc)
     return MatchResult(idx, dst, counts)
@@ -202,5 +166,4 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
         raise ValueError("q_desc and t_desc must have the same dim")
     opts = fd_nn_match_opts(dim, float(max_distance), float(max_ratio), 1 if cross_check else 0)
     gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4])
-    return _run(ctx, "fd_nn_match", opts, q, t, gate, on_dev, "float32", out,
-                "out must be contiguous tensors: int32 {}, float32 {}, int32 {}")
+    return _run(ctx, "fd_nn_match", opts, q, t, gate, on_dev, "float32", out)
