@@ -62,8 +62,8 @@ struct fd_ctx {
     bool sel_dirty = true;
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
-    // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors)
-    // stage their arrays here, in call order (fdrt::HostIo); the widest call is a guided match: 8 inputs, 3 outputs
+    // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest call is a guided match: 8 inputs, 3 outputs
     static constexpr int kStaging = 11;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
@@ -185,7 +185,9 @@ int copy_back_written(fd_ctx *c, const int32_t *counts, int batch, int32_t strid
 // That sync is why an entry point calls refuse_sync_under_capture before it builds one.
 class HostIo {
   public:
-    HostIo(fd_ctx *c, int io_on_device) : c_(c), dev_(io_on_device != 0) {}
+    // first: the staging buffer the call's arrays start at (a call whose inputs and outputs are on different
+    // sides builds one HostIo per side, the second past the first's arrays)
+    HostIo(fd_ctx *c, int io_on_device, int first = 0) : c_(c), dev_(io_on_device != 0), used_(first) {}
     template <typename T>
     hipError_t in(const T *p, size_t n, const T *&dev) {
         void *d = nullptr;
@@ -217,7 +219,7 @@ class HostIo {
     }
     fd_ctx *c_;
     bool dev_;
-    int used_ = 0;
+    int used_;
     std::vector<SlotArray> whole_, slots_;  // host-side outputs: {host, staged, bytes (whole_) or bytes per slot (slots_)}
 };
 

@@ -440,7 +440,19 @@ struct RansacArgs {
     int32_t *out_counts, *out_best;  // [batch] or null
 };
 
+// Image warp (fd_warp.hip): every destination pixel of out [batch][out_rows][out_cols] sampled from the frames
+// [batch][rows][cols] at the position a per-frame model gives (fd_frames_warp of include/fd_hip.h).
+struct WarpArgs {
+    const uint8_t *frames;
+    const double *params;        // [batch][9 | 22], or one set for every frame (shared)
+    uint8_t *out, *mask;         // [batch][out_rows][out_cols], any byte alignment; mask null: not written
+    int batch, rows, cols, out_rows, out_cols;
+    int model, shared, fill;     // FD_WARP_*; fill 0..255
+    int tiles;                   // launch_warp's: workgroup columns per destination row
+};
+
 // Launchers (stream-ordered, no allocation, no synchronisation: graph-capturable).
+hipError_t launch_warp(WarpArgs a, hipStream_t s);
 // the three kernels of fd_ransac, in order
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it

@@ -3,6 +3,7 @@
 // from LDS bytes with four wave-uniform integer weights, and the exact wave total of an int32 per lane.
 #pragma once
 
+#include "fd_bilinear.h"
 #include "fd_match_common.h"
 
 namespace fdk {
@@ -40,20 +41,7 @@ __device__ __forceinline__ void stage_patch(uint8_t *patch, const uint8_t *img, 
     }
 }
 
-struct Weights {
-    int w00, w10, w01, w11;
-};
-// ix = floor(x), and the four integer weights of the fraction in 1/1024 steps (truncated)
-__device__ __forceinline__ void split_pos(float x, float y, int &ix, int &iy, Weights &w) {
-    const float fx = floorf(x), fy = floorf(y);
-    ix = static_cast<int>(fx);
-    iy = static_cast<int>(fy);
-    const int qx = static_cast<int>((x - fx) * 1024.0f), qy = static_cast<int>((y - fy) * 1024.0f);
-    w.w00 = (1024 - qx) * (1024 - qy);
-    w.w10 = qx * (1024 - qy);
-    w.w01 = (1024 - qx) * qy;
-    w.w11 = qx * qy;
-}
+// (split_pos and its four weights: fd_bilinear.h)
 __device__ __forceinline__ int raw_sum(const uint8_t *p, const Weights &w) {
     return w.w00 * p[0] + w.w10 * p[1] + w.w01 * p[kFlowPitch] + w.w11 * p[kFlowPitch + 1];
 }

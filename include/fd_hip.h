@@ -705,6 +705,69 @@ int fd_ransac(fd_ctx *ctx, int batch, const fd_ransac_opts *opts,
               double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
               int io_on_device);
 
+/* ---- Image warp by a homography or a camera model (MI355X extension) --------------------------------- */
+#define FD_WARP_HOMOGRAPHY 0 /* params: double[9], row-major 3 x 3, fd_ransac's out_model layout */
+#define FD_WARP_CAMERA 1     /* params: double[22], below */
+
+typedef struct fd_warp_opts {
+    int32_t model;         /* FD_WARP_HOMOGRAPHY or FD_WARP_CAMERA */
+    int32_t shared_params; /* 1: one parameter set for every frame; 0: params is [batch][P] */
+    int32_t fill;          /* 0..255: value of destination pixels with no source */
+} fd_warp_opts;
+
+/*
+ * fd_frames_warp -- every pixel of out [batch][out_rows][out_cols] uint8 sampled bilinearly from the frame
+ * of frames [batch][rows][cols] uint8 with its index, at the source position a small per-frame model gives:
+ * registration of a frame by fd_ransac's homography, and lens undistortion / stereo rectification ahead of
+ * fd_points_detect. The reference has no such stage: the contract is this text, a definite sequence. All
+ * floating point up to the source position is double, every operation rounded once, no contraction, f64
+ * division correctly rounded (fd_ransac's conventions). params: double [batch][P], or [P] for every frame
+ * when shared_params; P = 9 or 22.
+ *
+ * Source position (sx, sy) of destination pixel (x, y) of frame b, x and y converted exactly to double.
+ * FD_WARP_HOMOGRAPHY, h = the frame's nine parameters: the map is destination -> source (inverse map):
+ *   X = (h0*x + h1*y) + h2;  Y = (h3*x + h4*y) + h5;  W = (h6*x + h7*y) + h8;  sx = X / W;  sy = Y / W
+ * There is no test on the sign of W: fd_ransac normalises by its largest entry, so a valid model may have
+ * W < 0 everywhere. Consequence: call fd_ransac with q = the previous frame's features and t = the next
+ * frame's; its H maps previous-frame pixels to next-frame pixels, so passing out_model as it is warps the
+ * next frame onto the previous one. No inversion is needed, and with params_on_device no host round trip.
+ * FD_WARP_CAMERA, the 22 parameters in order: the destination (ideal pinhole) intrinsics fxn, fyn, cxn, cyn;
+ * r0..r8, row-major, the rotation taking a destination ray to a source-camera ray (the identity for plain
+ * undistortion, the transposed rectifying rotation for stereo); the source intrinsics fx, fy, cx, cy; the
+ * distortion coefficients k1, k2, p1, p2, k3 (OpenCV's order):
+ *   a = (x - cxn) / fxn;  b = (y - cyn) / fyn
+ *   X = (r0*a + r1*b) + r2;  Y = (r3*a + r4*b) + r5;  W = (r6*a + r7*b) + r8;  xn = X / W;  yn = Y / W
+ *   q2 = xn*xn + yn*yn;  q4 = q2*q2;  q6 = q4*q2
+ *   rad = ((1.0 + k1*q2) + k2*q4) + k3*q6;  m = 2.0*(xn*yn)
+ *   xd = (xn*rad + p1*m) + p2*(q2 + 2.0*(xn*xn));  yd = (yn*rad + p1*(q2 + 2.0*(yn*yn))) + p2*m
+ *   sx = fx*xd + cx;  sy = fy*yd + cy
+ * (a depends on the column only and b on the row only: computing them once per column or row gives the same
+ * bits.)
+ *
+ * Sampling, both models: px = (float)sx, py = (float)sy, rounded to nearest. The pixel has a source iff
+ * 0 <= px <= (float)(cols - 1) and 0 <= py <= (float)(rows - 1); the test is false on NaN, so W = 0,
+ * infinities and NaN parameters all land on "no source". With a source: out = (S(0, 0) + 2^19) >> 20 with
+ * fd_flow_lk's raw bilinear sum S on the frame at (px, py) (floor, the fraction truncated to 1/1024, reads
+ * clamped to the frame's edge), and mask 1. Without: out = fill, mask 0. Consequences: the identity
+ * homography with equal shapes copies the frame bit for bit (a zero fraction gives S = 2^20 I), and an
+ * integer translation copies the shifted overlap and fills the rest. A warped frame is what fd_flow_lk and
+ * fd_points_refine would read at the same float positions, rounded to a byte.
+ *
+ * out_mask uint8 [batch][out_rows][out_cols] (NULL to skip). out must not overlap frames. No alignment beyond
+ * a byte is asked of frames, out or out_mask, and out_cols may be odd. Each of frames, params and the outputs
+ * (out and out_mask together) is a device pointer when its *_on_device flag is set. With all three on the
+ * device the call is kernels on the context's stream only: asynchronous and graph-capturable (no workspace
+ * is involved). Host frames are staged through the context as fd_pyr_build stages them, host params and
+ * outputs through context buffers; a call with any host array is complete on return. out_rows or out_cols
+ * 0: nothing is written, and the call succeeds.
+ * FD_ERR_INVALID: ctx, opts, frames, params or out NULL; batch, rows or cols < 1; a negative out dimension;
+ * model or shared_params outside {0, 1}; fill outside 0..255. Parameter values are never rejected: they are
+ * device data, and a bad model gives fill.
+ */
+int fd_frames_warp(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                   const fd_warp_opts *opts, const double *params, int params_on_device,
+                   int out_rows, int out_cols, uint8_t *out, uint8_t *out_mask /* NULL to skip */, int out_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

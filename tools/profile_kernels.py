@@ -19,6 +19,10 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
   --shape fastverify FAST (need 500, dist 15) + BRIEF-256 on the 64 frames of fastflow's moving scene, fd_brief_match of
                      frame i against frame i + 1 and fd_ransac (256 hypotheses, threshold 1 px) on the matches, the
                      fundamental matrix and then the homography, 10 calls
+  --shape warp       fd_frames_warp with a mask, on device tensors: a rotation by 3 degrees with scale 1.02 and a mild
+                     perspective (homography), then a barrel-distortion camera model, at 1920x1080 batch 64 (10
+                     calls each) and at 640x480 batch 1 (200 calls each), destination shape = source shape
+                     (--warp-size hd / vga: one of the two, so that a trace's statistics are one shape's)
   --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
                      128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
                      baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
@@ -41,13 +45,14 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
 p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
 p.add_argument("--fb", action="store_true", help="fastflow: track with the forward-backward check")
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
+p.add_argument("--warp-size", default="both", choices=["both", "hd", "vga"], help="warp: one of the two shapes (a trace per shape)")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
 g = torch.Generator(device="cuda")
@@ -204,6 +209,26 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
     print("matches per frame pair (mean):", float(out[2].float().mean()), "inliers F / H (mean):",
           float(geo[0][2].float().mean()), float(geo[1][2].float().mean()), "frames without a model:",
           int((geo[0][3] < 0).sum()), int((geo[1][3] < 0).sum()))
+elif a.shape == "warp":
+    import math
+
+    import numpy as np
+
+    kind = "homography, camera"
+    sizes = {"hd": (64, 1080, 1920, a.calls or 10), "vga": (1, 480, 640, a.calls or 200)}
+    for b, rows, cols, calls in (sizes.values() if a.warp_size == "both" else (sizes[a.warp_size],)):
+        frames = noise(b, rows, cols)
+        c, s_ = 1.02 * math.cos(math.radians(3.0)), 1.02 * math.sin(math.radians(3.0))
+        cx, cy = (cols - 1) / 2, (rows - 1) / 2
+        h = np.array([c, -s_, cx - (c * cx - s_ * cy), s_, c, cy - (s_ * cx + c * cy), 2e-5, -1e-5, 1.0])
+        K = np.array([[0.8 * cols, 0, cx], [0, 0.8 * cols, cy], [0, 0, 1.0]])
+        cam = fd.camera_params(K, K, [-0.25, 0.08, 0.001, -0.001, 0.0])
+        out = (torch.empty((b, rows, cols), dtype=torch.uint8, device="cuda"), torch.empty((b, rows, cols), dtype=torch.uint8, device="cuda"))
+        for model, prm in (("homography", h), ("camera", cam)):
+            dp = torch.from_numpy(prm).cuda()
+            for _ in range(calls):
+                fd.warp_frames(frames, dp, model=model, return_mask=True, out=out)
+            print(f"{model} {cols}x{rows}x{b}: pixels with a source {float(out[1].float().mean()):.4f}")
 elif a.shape == "nnmatch":
     kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
     B, S = 64, 240
