@@ -23,21 +23,48 @@ def mix(x):
     return x
 
 
-def sample(seed, b, h, n, m):
-    """The m distinct picks of hypothesis h of frame b among n correspondences, or None."""
+def sample_trace(seed, b, h, n, m):
+    """The sampler step by step: (picks, tries). picks are the distinct indices found, in order; tries[k] is
+    the number of draws pick k took (1..32). The sampler stops at the first pick that finds no new index in 32
+    draws, so an exhausted hypothesis has len(picks) < m. n < m gives ([], [])."""
+    picks, tries = [], []
     if n < m:
-        return None
+        return picks, tries
     base = mix(mix(seed + 0x9E3779B9 * b) + h)
-    picks = []
     for k in range(m):
         for a in range(32):
             idx = (mix(base + 32 * k + a) * n) >> 32
             if idx not in picks:
                 picks.append(idx)
+                tries.append(a + 1)
                 break
         else:
-            return None
-    return picks
+            break
+    return picks, tries
+
+
+def sample(seed, b, h, n, m):
+    """The m distinct picks of hypothesis h of frame b among n correspondences, or None."""
+    picks = sample_trace(seed, b, h, n, m)[0]
+    return picks if len(picks) == m and n >= m else None
+
+
+def exhausted(seed, b, n, m, hypotheses):
+    """The hypotheses of frame b whose sampler gives up (n >= m, a pick found no new index in 32 draws)."""
+    return [h for h in range(hypotheses) if n >= m and sample(seed, b, h, n, m) is None]
+
+
+# Pinned sampler cases of the tests, all with n equal to the sample size (tests/test_ransac_host.py confirms
+# each on the CPU). EXHAUSTING: (model, seed, hypotheses) whose frame 0 has exhausted hypotheses: for F the
+# hypotheses 70, 99, 220 and 250; for H, of the seeds below 64, the one whose first exhausted hypothesis (34)
+# comes earliest. EDGE_SEEDS: (model, seed, what hypothesis 0 does). With no outlier every valid hypothesis
+# counts all n, so the lowest valid index wins and hypothesis 0 decides `best`:
+#   "last draw": a pick of hypothesis 0 succeeds on its 32nd draw and 0 wins; a sampler that stops a draw early loses it;
+#   "dead": hypothesis 0 gives up while index 0, what an unfilled pick holds, is still free; a sampler that forgets
+#   the failure gives the solver distinct rows, a valid model, and 0 wins where it must not.
+EXHAUSTING = [(FUNDAMENTAL, 0, 256), (HOMOGRAPHY, 45, 1024)]
+EDGE_SEEDS = [(FUNDAMENTAL, 544, "last draw"), (FUNDAMENTAL, 99, "dead"), (HOMOGRAPHY, 853, "last draw"),
+              (HOMOGRAPHY, 71484, "dead")]
 
 
 def correspondences(q_xy, t_xy, count, match_idx, pair_valid, cx, cy, scale):

@@ -112,6 +112,48 @@ def test_nn_sizes_positions_and_radii(fd, kw):
     run_case(fd, "nn", G.nn_case(**kw))
 
 
+def raw_nn_guided_dev(fd, torch, c, q_off, t_off, **kw):
+    """fd_nn_match_guided through ctypes on device pointers, the descriptor sets as views q_off / t_off floats
+    into their allocations (unaligned.offset_view), the outputs between guards. Returns (idx, dist, counts)."""
+    from feature_detector_amd import _lib
+    from unaligned import guarded, offset_view, unguard
+
+    L, ctx = fd.load(), fd.default_context()
+    ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
+    B, Sq, St = c["q"].shape[0], c["q"].shape[1], c["t"].shape[1]
+    (dq, keep_q), (dt, keep_t) = offset_view(torch, c["q"], q_off), offset_view(torch, c["t"], t_off)
+    assert (dq.data_ptr() % 16 != 0) == (q_off != 0) and (dt.data_ptr() % 16 != 0) == (t_off != 0)
+    d = {k: None if c[k] is None else torch.from_numpy(np.ascontiguousarray(c[k])).cuda() for k in ("qv", "qc", "q_xy", "tv", "tc", "t_xy")}
+    p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    shapes = ((B, Sq), (B, Sq, 2), (B,))
+    bufs = [guarded(torch, s, SENT, ty) for s, ty in zip(shapes, (torch.int32, torch.float32, torch.int32))]
+    rx, ry = G.radii(c["radius"])
+    gate = _lib.fd_match_gate(rx, ry)
+    opts = _lib.fd_nn_match_opts(c["q"].shape[2], kw.get("max_distance", -1.0), kw.get("max_ratio", 0.0), int(kw.get("cross_check", 0)))
+    rc = L.fd_nn_match_guided(ctx.ptr, B, ctypes.byref(opts), ctypes.byref(gate), p(dq), p(d["qv"]), p(d["qc"]), Sq, p(d["q_xy"]),
+                              p(dt), p(d["tv"]), p(d["tc"]), St, p(d["t_xy"]), *(ctypes.c_void_p(ptr) for _, ptr in bufs), 1)
+    assert rc == 0, L.fd_last_error(ctx.ptr)
+    torch.cuda.synchronize()
+    del keep_q, keep_t
+    return tuple(unguard(buf, s, SENT) for (buf, _), s in zip(bufs, shapes))
+
+
+@pytest.mark.parametrize("dim,regime", [(128, "round"), (256, "int"), (4, "round")])
+def test_nn_unaligned_device_descriptors(fd, dim, regime):
+    """The gated instances on descriptor bases that are float-aligned but not 16-byte aligned: k_nn_norms and
+    the tile fill take their scalar loads. Train counts leave the last tile of either instance partial; with
+    the cross-check the reverse pass searches the (offset) query set. Equal to the restatement and to the same
+    call on aligned copies."""
+    torch = pytest.importorskip("torch")
+    c = G.nn_case(70, 130, B=2, qc=[70, 41], tc=[130, 77], flags=True, dim=dim, regime=regime, variant="tenth", radius=(12.0, 20.0))
+    for kw in ({}, dict(cross_check=True), every_test_on("nn", c)):
+        exp = ref("nn", c, fill=SENT, **kw)
+        assert exp[2].sum() > 0
+        for q_off, t_off in ((1, 0), (0, 3), (2, 2)):
+            assert_same(raw_nn_guided_dev(fd, torch, c, q_off, t_off, **kw), exp)
+        assert_same(raw_nn_guided_dev(fd, torch, c, 0, 0, **kw), exp)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_binding_host_and_device(fd, kind):
     """fd.brief_match / fd.nn_match with q_xy, t_xy, radius: numpy in, numpy out (-1 past the counts); torch

@@ -204,6 +204,98 @@ def test_tile_boundaries(fd, dim):
     assert_same((idx, dist, cnt), nn_match_ref(q, t, qc, tc, cross_check=True, fill=SENT))
 
 
+def raw_match_dev(fd, torch, q, t, q_off=0, t_off=0, qc=None, tc=None, qv=None, tv=None, max_distance=-1.0, max_ratio=0.0,
+                  cross_check=0):
+    """fd_nn_match through ctypes on device pointers: the descriptor sets are views q_off / t_off floats into
+    their allocations (unaligned.offset_view), the outputs lie between guards. Returns (idx, dist, counts)."""
+    from feature_detector_amd._lib import fd_nn_match_opts
+    from unaligned import guarded, offset_view, unguard
+
+    L, ctx = fd.load(), fd.default_context()
+    ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
+    B, Sq, St = q.shape[0], q.shape[1], t.shape[1]
+    (dq, keep_q), (dt, keep_t) = offset_view(torch, q, q_off), offset_view(torch, t, t_off)
+    for d, off in ((dq, q_off), (dt, t_off)):
+        assert (d.data_ptr() % 16 != 0) == (off != 0) and d.data_ptr() % 4 == 0
+    side = [None if x is None else torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (qv, qc, tv, tc)]
+    p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())  # noqa: E731
+    shapes = ((B, Sq), (B, Sq, 2), (B,))
+    bufs = [guarded(torch, s, SENT, dt_) for s, dt_ in zip(shapes, (torch.int32, torch.float32, torch.int32))]
+    opts = fd_nn_match_opts(q.shape[2], max_distance, max_ratio, int(cross_check))
+    rc = L.fd_nn_match(ctx.ptr, B, ctypes.byref(opts), p(dq), p(side[0]), p(side[1]), Sq, p(dt), p(side[2]), p(side[3]), St,
+                       *(ctypes.c_void_p(ptr) for _, ptr in bufs), 1)
+    assert rc == 0, L.fd_last_error(ctx.ptr)
+    torch.cuda.synchronize()
+    del keep_q, keep_t
+    return tuple(unguard(buf, s, SENT) for (buf, _), s in zip(bufs, shapes))
+
+
+UNALIGNED_COUNTS = dict(qc=np.array([70, 41], np.int32), tc=np.array([130, 77], np.int32))
+_unaligned_cache = {}
+
+
+def unaligned_case(dim, regime):
+    """The data of test_every_dim_class (B 2, 70 queries, 130 train entries, counts 130 and 77: the last
+    train tile of either instance is partial, also for the reverse pass over 70 and 41 queries), with the
+    restatement's answer for the cross-check off and on. Computed once."""
+    if (dim, regime) not in _unaligned_cache:
+        rng = np.random.default_rng(1000 + dim + (regime == "int"))
+        B, Sq, St = 2, 70, 130
+        if regime == "int":
+            q, t = int_sets(rng, B, Sq, St, dim)
+        else:
+            q, t = unit_rows(rng, B, Sq, dim), unit_rows(rng, B, St, dim)
+            t[:, 5:25] = (q[:, 30:50] + F32(0.1) * unit_rows(rng, B, 20, dim)).astype(F32)
+        tv = (rng.random((B, St)) < 0.85).astype(np.uint8)
+        # the bare cross-check asks the reverse pass about every query's best, also the random pairs whose
+        # mutual status turns on small differences of the reverse distances; with the ratio test only the
+        # planted, clear matches get that far
+        kws = (dict(), dict(cross_check=True), dict(max_ratio=0.9, cross_check=True))
+        exp = [nn_match_ref(q, t, UNALIGNED_COUNTS["qc"], UNALIGNED_COUNTS["tc"], None, tv, fill=SENT, **kw) for kw in kws]
+        assert exp[0][2].sum() > exp[1][2].sum() > exp[2][2].sum() > 0  # each test rejects some, keeps some
+        _unaligned_cache[dim, regime] = (q, t, tv, kws, exp)
+    return _unaligned_cache[dim, regime]
+
+
+@pytest.mark.parametrize("q_off,t_off", [(1, 0), (0, 2), (3, 1)], ids=["query", "train", "both"])
+@pytest.mark.parametrize("regime", ["int", "round"])
+@pytest.mark.parametrize("dim", [4, 128, 256])
+def test_unaligned_device_descriptors(fd, dim, regime, q_off, t_off):
+    """Descriptor bases that are float-aligned but not 16-byte aligned (views into a larger allocation): the
+    scalar load4 path of k_nn_norms and of k_nn_match's tile fill. With the cross-check the reverse pass
+    searches the query set, so an offset on the query alone reaches the tile fill too. At dim 4 a row is 16
+    bytes: every row is misaligned. Equal to the restatement and to the same call on aligned copies."""
+    torch = pytest.importorskip("torch")
+    q, t, tv, kws, exps = unaligned_case(dim, regime)
+    tb = R.instance(dim)[1]
+    assert all(int(n) % tb for n in UNALIGNED_COUNTS["tc"]) and all(int(n) % tb for n in UNALIGNED_COUNTS["qc"])
+    for kw, exp in zip(kws, exps):
+        got = raw_match_dev(fd, torch, q, t, q_off, t_off, tv=tv, **UNALIGNED_COUNTS, **kw)
+        assert_same(got, exp)
+        assert_same(raw_match_dev(fd, torch, q, t, 0, 0, tv=tv, **UNALIGNED_COUNTS, **kw), got)
+
+
+@pytest.mark.parametrize("dim", [4, 128, 256])
+def test_unaligned_views_through_the_binding(fd, dim):
+    """fd.nn_match on sliced torch views: the views are contiguous, so the binding passes their offset
+    pointers on as they are (Tensor.contiguous() returns a contiguous tensor itself, no copy)."""
+    torch = pytest.importorskip("torch")
+    from unaligned import offset_view
+
+    q, t, tv, kws, exps = unaligned_case(dim, "round")
+    (dq, keep_q), (dt, keep_t) = offset_view(torch, q, 1), offset_view(torch, t, 2)
+    assert dq.data_ptr() % 16 == 4 and dt.data_ptr() % 16 == 8
+    assert dq.contiguous().data_ptr() == dq.data_ptr() and dt.contiguous().data_ptr() == dt.data_ptr()
+    side = [torch.from_numpy(x).cuda() for x in (UNALIGNED_COUNTS["qc"], UNALIGNED_COUNTS["tc"], tv)]
+    for kw, exp in zip(kws, exps):
+        out = (torch.full((2, 70), SENT, dtype=torch.int32, device="cuda"),
+               torch.full((2, 70, 2), SENT, dtype=torch.float32, device="cuda"),
+               torch.full((2,), SENT, dtype=torch.int32, device="cuda"))
+        fd.nn_match(dq, dt, side[0], side[1], None, side[2], out=out, **kw)
+        torch.cuda.synchronize()
+        assert_same(out, exp)
+
+
 def test_zero_strides(fd):
     z = unit_rows(np.random.default_rng(1), 2, 4, 8)
     # q_stride 0: no work, counts zeroed; t_stride 0: as all train counts 0

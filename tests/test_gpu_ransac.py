@@ -141,6 +141,162 @@ def test_match_index_valid_bytes_and_non_finite(fd, ctx, model):
     check(fd, ctx, q, q.copy() + np.float32(1.5), counts=counts, valid=valid, model=model, hypotheses=128, seed=5)
 
 
+# ---- the sampler's "no new index in 32 draws" exit ---------------------------------------------------------
+EXHAUSTING = R.EXHAUSTING  # (model, seed, hypotheses) with n equal to the sample size whose frame 0 has exhausted hypotheses
+
+
+def minimal_frame(model, seed=0, pad=3):
+    """One frame whose count is the sample size (no outliers), in a stride `pad` slots longer."""
+    m = R.SAMPLE[model]
+    q, t, _ = R.planted_scene(model, seed, n=m + pad, outliers=0)
+    return q[None], t[None], [m]
+
+
+@pytest.mark.parametrize("model,seed,hypotheses", EXHAUSTING)
+def test_sampler_exhaustion(fd, ctx, model, seed, hypotheses):
+    """n = sample size: the last pick has one free index, so some hypotheses give up. Such a lane goes on
+    through the solver, the scoring loop and the wave reduction with ok = false: it must not win."""
+    m = R.SAMPLE[model]
+    dead = R.exhausted(seed, 0, m, m, hypotheses)
+    assert len(dead) >= 1, "these inputs do not reach the sampler's exit"
+    q, t, counts = minimal_frame(model)
+    detail = []
+    exp = R.ransac_ref(q, t, counts, model=model, hypotheses=hypotheses, seed=seed, center=CENTER, scale=SCALE, detail=detail)
+    score, valid = detail[0]
+    assert not valid[dead].any() and valid.any() and exp[3][0] >= 0 and exp[3][0] not in dead
+    check(fd, ctx, q, t, counts=counts, model=model, hypotheses=hypotheses, seed=seed)
+
+
+@pytest.mark.parametrize("model,seed,hypotheses", EXHAUSTING)
+def test_sampler_exhaustion_beside_a_normal_frame(fd, ctx, model, seed, hypotheses):
+    """Batch 2: frame 0 has n equal to the sample size (dead lanes among its hypotheses), then n below it
+    (every lane dead); frame 1 is a normal scene whose outputs must be those it has alone."""
+    m = R.SAMPLE[model]
+    assert len(R.exhausted(seed, 0, m, m, hypotheses)) >= 1
+    q, t = scenes(model, 40, 2, seed=6)
+    opt = dict(model=model, hypotheses=hypotheses, seed=seed)
+    exp = check(fd, ctx, q, t, counts=[m, 40], **opt)
+    none = check(fd, ctx, q, t, counts=[m - 1, 40], **opt)
+    assert exp[3][0] >= 0 and none[3][0] == -1 and exp[3][1] >= 0 and exp[2][1] >= 20
+    # frame 1's hypotheses depend on its frame index, so "alone" is the same batch with frame 0 emptied
+    alone = R.ransac_ref(q, t, [0, 40], fill=SENT_INL, center=CENTER, scale=SCALE, **opt)
+    for with_dead, all_dead, one in zip(exp, none, alone):
+        assert np.array_equal(with_dead[1:].view(np.uint8), one[1:].view(np.uint8))
+        assert np.array_equal(all_dead[1:].view(np.uint8), one[1:].view(np.uint8))
+
+
+EDGE_SEEDS = R.EDGE_SEEDS  # (model, seed, what hypothesis 0 does): see tests/ransac_ref.py
+
+
+@pytest.mark.parametrize("model,seed,what", EDGE_SEEDS)
+def test_sampler_edge_decides_the_winner(fd, ctx, model, seed, what):
+    m = R.SAMPLE[model]
+    picks, tries = R.sample_trace(seed, 0, 0, m, m)
+    if what == "last draw":
+        assert len(picks) == m and max(tries) == 32
+    else:
+        assert len(picks) < m and 0 not in picks
+    q, t, counts = minimal_frame(model)
+    detail = []
+    exp = check(fd, ctx, q, t, counts=counts, model=model, hypotheses=64, seed=seed, detail=detail)
+    score, valid = detail[0]
+    assert valid.sum() >= 2 and np.all(score[valid] == m)
+    assert (exp[3][0] == 0) == (what == "last draw") and valid[0] == (what == "last draw")
+
+
+# ---- k_ransac_compact across its 256-slot chunks ----------------------------------------------------------
+SEAM_S = 600  # chunks 0..255, 256..511, 512..599
+
+
+def _punch(q, t, idx, valid, slots):
+    """Make every slot of `slots` a hole, cycling through the six ways a slot is not taken."""
+    T = t.shape[0]
+    for i, s in enumerate(slots):
+        kind = i % 6
+        if kind == 0:
+            valid[s] = 0
+        elif kind == 1:
+            valid[s] = 2 + i % 250
+        elif kind == 2:
+            idx[s] = -1
+        elif kind == 3:
+            idx[s] = T + i % 3
+        elif kind == 4:
+            q[s, i % 2] = np.nan
+        else:
+            t[s, i % 2] = np.inf if i % 4 else -np.inf  # (match_idx is the identity: only slot s reads t[s])
+
+
+def seam_holes(pattern):
+    """(hole slots, count word) of one frame of SEAM_S slots."""
+    rng = np.random.default_rng(pattern)
+    S = SEAM_S
+    if pattern == 0:
+        return [255, 256], S
+    if pattern == 1:
+        return [511, 512], S
+    if pattern == 2:  # the whole first chunk untaken
+        return list(range(256)), S
+    if pattern == 3:  # a whole chunk taken between two sparse ones
+        return sorted(rng.choice(256, 200, replace=False).tolist() + (512 + rng.choice(88, 60, replace=False)).tolist()), S
+    if pattern in (4, 5):  # exactly 256 / 257 survivors
+        return sorted(rng.choice(S, S - (256 if pattern == 4 else 257), replace=False).tolist()), S
+    # a count word of 520 with flag bits: the last chunk is 512..519 (kept whole), the slots past it stay as they were
+    word = int(np.array([520 | (1 << 25) | (1 << 28) | (1 << 31)], np.uint32).view(np.int32)[0])
+    return list(range(3, 512, 7)) + [255, 256], word
+
+
+SEAM_FRAMES = [(0, 1, 2), (3, 4, 5), (6, 2, 4)]
+
+
+@pytest.mark.parametrize("model", MODELS)
+@pytest.mark.parametrize("patterns", SEAM_FRAMES)
+def test_compaction_across_chunk_seams(fd, ctx, model, patterns):
+    """q_stride 600, batch 3, a different hole pattern per frame: the running base of k_ransac_compact over
+    three chunks with holes on, before and after the seams. A wrong carry shifts cidx, hence the inlier mask,
+    of the slots at or past 256; the mask has ones in every chunk that has a survivor."""
+    S = SEAM_S
+    q, t, idx, valid, counts = [], [], [], [], []
+    for b, p in enumerate(patterns):
+        qb, tb, _ = R.planted_scene(model, 100 + 10 * p + b, n=S, outliers=150)
+        ib, vb = np.arange(S, dtype=np.int32), np.ones(S, np.uint8)
+        holes, word = seam_holes(p)
+        _punch(qb, tb, ib, vb, holes)
+        n = min(word & R.COUNT_MASK, S)
+        survivors = np.setdiff1d(np.arange(n), holes)
+        assert len(R.correspondences(qb, tb, word, ib, vb, 0.0, 0.0, 1.0)[1]) == len(survivors)
+        if p in (4, 5):
+            assert len(survivors) == 252 + p
+        q.append(qb), t.append(tb), idx.append(ib), valid.append(vb), counts.append(word)
+    q, t, idx, valid = np.stack(q), np.stack(t), np.stack(idx), np.stack(valid)
+    counts = np.array(counts, np.int32)
+    exp = check(fd, ctx, q, t, counts=counts, idx=idx, valid=valid, model=model, hypotheses=128, seed=3)
+    for b, p in enumerate(patterns):
+        holes, word = seam_holes(p)
+        n = min(word & R.COUNT_MASK, S)
+        assert exp[3][b] >= 0 and not exp[1][b, holes].any() and np.all(exp[1][b, n:] == SENT_INL)
+        for lo in range(0, n, 256):
+            chunk = np.arange(lo, min(lo + 256, n))
+            if len(np.setdiff1d(chunk, holes)):
+                assert exp[1][b, chunk].sum() >= 1, (p, lo)
+        assert exp[1][b, 256:n].sum() >= 2 and exp[1][b, 512:n].sum() >= 1  # the slots a wrong carry moves
+
+
+# ---- the documented maximum of 4096 hypotheses: 64 wave-groups per frame ----------------------------------
+@pytest.mark.parametrize("model", MODELS)
+def test_hypothesis_cap(fd, ctx, model):
+    """Batch 2 with different counts: blockIdx.x / groups at its widest, and the tie rule across workgroups:
+    the tied best hypotheses lie in at least two groups of 64 and the lowest index wins."""
+    q, t = scenes(model, 40, 2, seed=1)
+    detail = []
+    exp = check(fd, ctx, q, t, counts=[40, 33], model=model, hypotheses=4096, seed=2, detail=detail)
+    for b in range(2):
+        score, valid = detail[b]
+        tied = np.flatnonzero(valid & (score == score[valid].max()))
+        assert len(set((tied // 64).tolist())) >= 2 and exp[3][b] == tied[0]
+        assert tied[-1] // 64 > tied[0] // 64 and exp[2][b] == score[tied[0]]
+
+
 def test_degenerate_inputs_have_no_model(fd, ctx):
     """All points identical (both models), q_xy == t_xy with F (rank below 8), collinear points with H."""
     rng = np.random.default_rng(2)

@@ -70,6 +70,51 @@ def test_sampler_failure_path_at_n_equal_m():
     assert not detail[0][1][[p is None for p in picks]].any()
 
 
+def test_pinned_exhausting_seeds():
+    """The (model, seed, hypotheses) the GPU tests run to reach the sampler's exit do reach it, and the
+    restatement marks those hypotheses invalid and picks none of them."""
+    assert R.exhausted(0, 0, 8, 8, 256) == [70, 99, 220, 250]
+    assert R.exhausted(45, 0, 4, 4, 1024)[0] == 34
+    assert R.exhausted(0, 0, 7, 8, 256) == [] and R.sample(0, 0, 0, 7, 8) is None  # n < m is not exhaustion
+    for model, seed, hypotheses in R.EXHAUSTING:
+        m = R.SAMPLE[model]
+        dead = R.exhausted(seed, 0, m, m, hypotheses)
+        assert len(dead) >= 1
+        for h in dead:
+            picks, tries = R.sample_trace(seed, 0, h, m, m)
+            assert len(picks) == len(tries) < m and len(set(picks)) == len(picks)
+        q, t, _ = R.planted_scene(model, 0, n=m, outliers=0)
+        detail = []
+        exp = R.ransac_ref(q[None], t[None], model=model, hypotheses=hypotheses, seed=seed, center=CENTER, scale=SCALE, detail=detail)
+        assert not detail[0][1][dead].any() and exp[3][0] >= 0 and exp[3][0] not in dead
+
+
+@pytest.mark.parametrize("model,seed,what", R.EDGE_SEEDS)
+def test_pinned_edge_seeds(model, seed, what):
+    """Hypothesis 0 of these seeds is the one a sampler that is wrong at its exit gets wrong, and it decides `best`."""
+    m = R.SAMPLE[model]
+    picks, tries = R.sample_trace(seed, 0, 0, m, m)
+    if what == "last draw":
+        assert R.sample(seed, 0, 0, m, m) == picks and max(tries) == 32
+    else:
+        assert R.sample(seed, 0, 0, m, m) is None and len(picks) < m and 0 not in picks
+    q, t, _ = R.planted_scene(model, 0, n=m, outliers=0)
+    detail = []
+    exp = R.ransac_ref(q[None], t[None], model=model, hypotheses=64, seed=seed, center=CENTER, scale=SCALE, detail=detail)
+    score, valid = detail[0]
+    assert valid.sum() >= 2 and np.all(score[valid] == m) and (exp[3][0] == 0) == (what == "last draw")
+
+
+def test_sample_trace_is_the_sampler():
+    for m in (4, 8):
+        for n in (m - 1, m, m + 1, 50):
+            for h in range(300):
+                picks, tries = R.sample_trace(3, 1, h, n, m)
+                full = len(picks) == m
+                assert (R.sample(3, 1, h, n, m) == picks) if full else (R.sample(3, 1, h, n, m) is None)
+                assert all(1 <= a <= 32 for a in tries) and len(tries) == len(picks)
+
+
 def test_correspondence_list_rules():
     q = np.arange(20, dtype=np.float32).reshape(10, 2)
     t = q[:6] + 100
