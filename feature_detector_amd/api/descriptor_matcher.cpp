@@ -5,44 +5,13 @@
 #include "feature_detector/descriptor_matcher.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 
 #include "fd_hip.h"
+#include "vec2_pack.h"
 
 namespace feature_detector {
 
 namespace {
-
-// What both matchers do alike with their members (ctx_, device_, error_).
-bool FailWith(std::string &error, const std::string &what) {
-    error = what;
-    std::fprintf(stderr, "[feature_detector] %s\n", error.c_str());
-    return false;
-}
-
-void SetDevice(fd_ctx *&ctx, int &device_member, int device) {
-    if (ctx && device != device_member) {
-        fd_ctx_destroy(ctx);
-        ctx = nullptr;
-    }
-    device_member = device;
-}
-
-// The context, created on first use (device < 0: FD_DEVICE, else device 0).
-fd_ctx *Acquire(fd_ctx *&ctx, int device, std::string &error) {
-    if (!ctx) {
-        if (device < 0) {
-            const char *e = std::getenv("FD_DEVICE");
-            device = e ? std::atoi(e) : 0;
-        }
-        if (fd_ctx_create(device, &ctx) != FD_OK) {
-            ctx = nullptr;
-            FailWith(error, "fd_ctx_create failed (no MI355X visible?)");
-        }
-    }
-    return ctx;
-}
 
 // std::vector<bool> descriptors -> [n][words] uint32, bit i = bit i % 32 of word i / 32 (fd_brief_compute's layout)
 bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<uint32_t> &words) {
@@ -56,26 +25,11 @@ bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<
     return true;
 }
 
-// Vec2 positions -> [n][2] floats (x, y)
-std::vector<float> Flatten(const std::vector<Vec2> &uv) {
-    std::vector<float> xy(2 * uv.size());
-    for (size_t i = 0; i < uv.size(); ++i) {
-        xy[2 * i] = uv[i].x();
-        xy[2 * i + 1] = uv[i].y();
-    }
-    return xy;
-}
-
 bool BadRadius(float r) { return !std::isfinite(r) || r < 0.0f; }
 
 }  // namespace
 
-BriefMatcher::~BriefMatcher() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
-void BriefMatcher::set_device(int device) { SetDevice(ctx_, device_, device); }
-fd_ctx *BriefMatcher::Context() { return Acquire(ctx_, device_, error_); }
-bool BriefMatcher::Fail(const std::string &what) { return FailWith(error_, what); }
+BriefMatcher::~BriefMatcher() = default;
 
 bool BriefMatcher::Match(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
                          std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
@@ -97,17 +51,17 @@ bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<Br
                        const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
     train_index.assign(query.size(), -1);
     if (distance) distance->assign(query.size(), -1);
-    if (query.empty() || train.empty()) return Fail("Match: empty input");
+    if (query.empty() || train.empty()) return context_.Fail("Match: empty input");
     const size_t length = query[0].size();
-    if (length < 1 || length > 256) return Fail("Match: descriptor length outside 1..256");
+    if (length < 1 || length > 256) return context_.Fail("Match: descriptor length outside 1..256");
     std::vector<uint32_t> q, t;
-    if (!Pack(query, length, q) || !Pack(train, length, t)) return Fail("Match: descriptors of unequal length");
+    if (!Pack(query, length, q) || !Pack(train, length, t)) return context_.Fail("Match: descriptors of unequal length");
     if ((query_valid && query_valid->size() != query.size()) || (train_valid && train_valid->size() != train.size()))
-        return Fail("Match: one valid flag per descriptor is needed");
+        return context_.Fail("Match: one valid flag per descriptor is needed");
     if (query_uv && (query_uv->size() != query.size() || train_uv->size() != train.size()))
-        return Fail("MatchGuided: one position per descriptor is needed");
-    if (query_uv && (BadRadius(radius_x) || BadRadius(radius_y))) return Fail("MatchGuided: a radius must be finite and >= 0");
-    fd_ctx *ctx = Context();
+        return context_.Fail("MatchGuided: one position per descriptor is needed");
+    if (query_uv && (BadRadius(radius_x) || BadRadius(radius_y))) return context_.Fail("MatchGuided: a radius must be finite and >= 0");
+    fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     fd_match_opts o{static_cast<int32_t>(length), options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
     std::vector<int32_t> dist(2 * query.size(), -1);
@@ -125,19 +79,14 @@ bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<Br
     }
     if (rc != FD_OK) {
         train_index.assign(query.size(), -1);
-        return Fail(std::string("fd_brief_match: ") + fd_last_error(ctx));
+        return context_.FailCall("fd_brief_match");
     }
     if (distance)
         for (size_t i = 0; i < query.size(); ++i) (*distance)[i] = dist[2 * i];
     return true;
 }
 
-NNDescriptorMatcher::~NNDescriptorMatcher() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
-void NNDescriptorMatcher::set_device(int device) { SetDevice(ctx_, device_, device); }
-fd_ctx *NNDescriptorMatcher::Context() { return Acquire(ctx_, device_, error_); }
-bool NNDescriptorMatcher::Fail(const std::string &what) { return FailWith(error_, what); }
+NNDescriptorMatcher::~NNDescriptorMatcher() = default;
 
 bool NNDescriptorMatcher::Match(const float *query, int32_t n_query, const float *train, int32_t n_train, int32_t dim,
                                 std::vector<int32_t> &train_index, std::vector<float> *distance,
@@ -161,13 +110,13 @@ bool NNDescriptorMatcher::Run(const float *query, int32_t n_query, const float *
     const size_t nq = n_query > 0 ? static_cast<size_t>(n_query) : 0;
     train_index.assign(nq, -1);
     if (distance) distance->assign(nq, -1.0f);
-    if (!query || !train || n_query < 1 || n_train < 1) return Fail("Match: empty input");
-    if (dim < 4 || dim > 256 || (dim & 3)) return Fail("Match: dim must be a multiple of 4 in 4..256");
+    if (!query || !train || n_query < 1 || n_train < 1) return context_.Fail("Match: empty input");
+    if (dim < 4 || dim > 256 || (dim & 3)) return context_.Fail("Match: dim must be a multiple of 4 in 4..256");
     if ((query_valid && query_valid->size() != nq) || (train_valid && train_valid->size() != static_cast<size_t>(n_train)))
-        return Fail("Match: one valid flag per descriptor is needed");
-    if (guided && (!query_xy || !train_xy)) return Fail("MatchGuided: positions are needed");
-    if (guided && (BadRadius(radius_x) || BadRadius(radius_y))) return Fail("MatchGuided: a radius must be finite and >= 0");
-    fd_ctx *ctx = Context();
+        return context_.Fail("Match: one valid flag per descriptor is needed");
+    if (guided && (!query_xy || !train_xy)) return context_.Fail("MatchGuided: positions are needed");
+    if (guided && (BadRadius(radius_x) || BadRadius(radius_y))) return context_.Fail("MatchGuided: a radius must be finite and >= 0");
+    fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     fd_nn_match_opts o{dim, options_.kMaxDistance, options_.kMaxRatio, options_.kCrossCheck ? 1 : 0};
     std::vector<float> dist(2 * nq, -1.0f);
@@ -183,7 +132,7 @@ bool NNDescriptorMatcher::Run(const float *query, int32_t n_query, const float *
     }
     if (rc != FD_OK) {
         train_index.assign(nq, -1);
-        return Fail(std::string("fd_nn_match: ") + fd_last_error(ctx));
+        return context_.FailCall("fd_nn_match");
     }
     if (distance)
         for (size_t i = 0; i < nq; ++i) (*distance)[i] = dist[2 * i];

@@ -9,8 +9,6 @@
 #include "feature_detector/feature_line_detector.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 
 #include "fd_hip.h"
 
@@ -21,38 +19,16 @@ FeatureLineDetector::FeatureLineDetector() {
     sorted_pixels_.reserve(10000);  // feature_line_detector.cpp:8-9
 }
 
-FeatureLineDetector::~FeatureLineDetector() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
-
-void FeatureLineDetector::set_device(int device) {
-    if (ctx_ && device != device_) {
-        fd_ctx_destroy(ctx_);
-        ctx_ = nullptr;
-    }
-    device_ = device;
-}
-
-bool FeatureLineDetector::EnsureContext() {
-    if (ctx_) return true;
-    if (device_ < 0) {
-        const char *e = std::getenv("FD_DEVICE");
-        device_ = e ? std::atoi(e) : 0;
-    }
-    if (fd_ctx_create(device_, &ctx_) != FD_OK) {
-        ctx_ = nullptr;
-        error_ = "fd_ctx_create failed (no MI355X visible?)";
-        std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-        return false;
-    }
-    return true;
-}
+FeatureLineDetector::~FeatureLineDetector() = default;
 
 bool FeatureLineDetector::DetectGoodFeatures(const GrayImage &image, const uint32_t needed_feature_num,
                                              std::vector<Vec4> &features) {
     if (image.data() == nullptr || image.rows() < 2 || image.cols() < 2) return false;  // :14
     if (needed_feature_num == 0) return true;                                           // :15
-    if (!EnsureContext()) return false;
+    // this class writes the resolved default ordinal back, so a later set_device() is compared with it
+    if (!context_.get() && context_.device() < 0) context_.set_device(DeviceContext::DefaultDevice());
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
 
     const fd_lsd_opts opts{options_.kMinValidGradientNorm, options_.kMinToleranceAngleResidualInRad,
                            options_.kMinValidLineLengthInPixel, options_.kMaxToleranceInlierRation};
@@ -64,21 +40,14 @@ bool FeatureLineDetector::DetectGoodFeatures(const GrayImage &image, const uint3
     sorted_pixels_.clear();
     rectangles_.clear();
     const uint8_t *dframe = nullptr;
-    if (fd_ctx_stage(ctx_, image.data(), static_cast<int64_t>(image.rows()) * image.cols(), &dframe) != FD_OK) {
-        error_ = std::string("fd_ctx_stage: ") + fd_last_error(ctx_);
-        std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-        return false;
-    }
+    if (fd_ctx_stage(ctx, image.data(), static_cast<int64_t>(image.rows()) * image.cols(), &dframe) != FD_OK)
+        return context_.FailCall("fd_ctx_stage");
     std::vector<fd_lsd_rect> rects(256);
     int32_t count = 0;
     for (;;) {
-        const int rc = fd_lsd_lines(ctx_, dframe, 1, 1, image.rows(), image.cols(), &opts, needed_feature_num,
+        const int rc = fd_lsd_lines(ctx, dframe, 1, 1, image.rows(), image.cols(), &opts, needed_feature_num,
                                     rects.data(), static_cast<int32_t>(rects.size()), &count, 1);
-        if (rc != FD_OK) {
-            error_ = std::string("fd_lsd_lines: ") + fd_last_error(ctx_);
-            std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-            return false;
-        }
+        if (rc != FD_OK) return context_.FailCall("fd_lsd_lines");
         if (count <= static_cast<int32_t>(rects.size())) break;
         rects.resize(static_cast<size_t>(count));  // more segments than slots: run again with room for all
     }
@@ -114,12 +83,13 @@ void FeatureLineDetector::Materialise() const {
     if (!staged_) return;
     if (!ComputeLineLevelAngleMap()) return;
     // is_used as the reference's regions leave it (every listed pixel; unlisted ones are invalid)
+    fd_ctx *ctx = context_.get();
     int64_t n = 0;
-    fd_lsd_lines_state(ctx_, nullptr, nullptr, nullptr, nullptr, 0, &n);
+    fd_lsd_lines_state(ctx, nullptr, nullptr, nullptr, nullptr, 0, &n);
     std::vector<int32_t> idx(static_cast<size_t>(n));
     std::vector<float> nv(static_cast<size_t>(n)), av(static_cast<size_t>(n));
     std::vector<uint8_t> used(static_cast<size_t>(n));
-    if (n > 0) fd_lsd_lines_state(ctx_, idx.data(), nv.data(), av.data(), used.data(), n, &n);
+    if (n > 0) fd_lsd_lines_state(ctx, idx.data(), nv.data(), av.data(), used.data(), n, &n);
     const int32_t pc = last_cols_ - 1;
     for (int64_t k = 0; k < n; ++k) pixels_(idx[k] / pc, idx[k] % pc).is_used = used[k] != 0;
 }
@@ -152,13 +122,9 @@ bool FeatureLineDetector::ComputeLineLevelAngleMap() const {
     std::vector<int32_t> idx(n);
     int64_t count = 0;
     ++map_passes_;
-    const int rc = fd_lsd_map(ctx_, staged_, 1, 1, rows, cols, last_min_norm_, norm.data(), angle.data(), valid.data(),
-                              idx.data(), static_cast<int64_t>(n), &count, 0);
-    if (rc != FD_OK) {
-        error_ = std::string("fd_lsd_map: ") + fd_last_error(ctx_);
-        std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-        return false;
-    }
+    const int rc = fd_lsd_map(context_.get(), staged_, 1, 1, rows, cols, last_min_norm_, norm.data(), angle.data(),
+                              valid.data(), idx.data(), static_cast<int64_t>(n), &count, 0);
+    if (rc != FD_OK) return context_.FailCall("fd_lsd_map");
     // Flags describe this call only (the reference carries is_used over between calls on a same-size
     // frame, and never clears sorted_pixels_; a fresh state per call is kept here).
     pixels_ = PixelMatrix();

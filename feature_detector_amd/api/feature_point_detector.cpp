@@ -4,19 +4,13 @@
 #include "feature_detector/feature_point_detector.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 
 #include "fd_hip.h"
+#include "vec2_pack.h"
 
 namespace feature_detector {
 
 namespace {
-
-int DefaultDevice() {
-    const char *e = std::getenv("FD_DEVICE");
-    return e ? std::atoi(e) : 0;
-}
 
 // DrawRectangleInMask (feature_point_detector.cpp:76-88): zero the clipped (2d+1)^2 box.
 void DrawBox(MatInt &mask, int32_t row, int32_t col, int32_t dist) {
@@ -31,36 +25,23 @@ void DrawBox(MatInt &mask, int32_t row, int32_t col, int32_t dist) {
 
 }  // namespace
 
-FeaturePointDetector::~FeaturePointDetector() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
+FeaturePointDetector::~FeaturePointDetector() = default;
 
-void FeaturePointDetector::set_device(int device) {
-    if (ctx_ && device != device_) {
-        fd_ctx_destroy(ctx_);
-        ctx_ = nullptr;
-    }
-    device_ = device;
-}
-
+// Where this class differs from the other users of DeviceContext: device() reports the resolved default
+// ordinal after the first call, a failed creation prints nothing here (DetectGoodFeatures then reports
+// "no device context"), and a fresh context gets the reference's tie order.
 fd_ctx *FeaturePointDetector::Context() {
-    if (!ctx_) {
-        if (device_ < 0) device_ = DefaultDevice();
-        if (fd_ctx_create(device_, &ctx_) != FD_OK) {
-            ctx_ = nullptr;
-            error_ = "fd_ctx_create failed (no MI355X visible?)";
-        } else {
-            // the drop-in reproduces the reference's std::sort order of equal responses (:58-60)
-            (void)fd_ctx_set_tie_order(ctx_, FD_TIES_REFERENCE);
-        }
+    if (!context_.get()) {
+        if (context_.device() < 0) context_.set_device(DeviceContext::DefaultDevice());
+        // the drop-in reproduces the reference's std::sort order of equal responses (:58-60)
+        if (fd_ctx *ctx = context_.Create()) (void)fd_ctx_set_tie_order(ctx, FD_TIES_REFERENCE);
     }
-    return ctx_;
+    return context_.get();
 }
 
+// with a context, every failure of this class carries the library's last message
 bool FeaturePointDetector::Fail(const std::string &what) {
-    error_ = what + (ctx_ ? std::string(": ") + fd_last_error(ctx_) : std::string());
-    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-    return false;
+    return context_.get() ? context_.FailCall(what) : context_.Fail(what);
 }
 
 // DetectGoodFeatures (feature_point_detector.cpp:7-25): the mask state of :12-16 (materialised on
@@ -101,17 +82,13 @@ bool FeaturePointDetector::DeferCandidatesToGpu(int kind) {
 // The built-in detectors: mask, candidates and selection as one fd_points_detect on the staged frame.
 bool FeaturePointDetector::DetectFused(const GrayImage &image, int kind, const uint32_t needed_feature_num,
                                        std::vector<Vec2> &features) {
-    fd_ctx *ctx = ctx_;
+    fd_ctx *ctx = context_.get();
     const int32_t rows = image.rows(), cols = image.cols();
     const uint8_t *dframe = nullptr;
     if (fd_ctx_stage(ctx, image.data(), static_cast<int64_t>(rows) * cols, &dframe) != FD_OK)
         return Fail("staging the image");
 
-    std::vector<float> prior(2 * features.size());
-    for (size_t i = 0; i < features.size(); ++i) {
-        prior[2 * i] = features[i].x();
-        prior[2 * i + 1] = features[i].y();
-    }
+    const std::vector<float> prior = Flatten(features);
     const int32_t nprior = static_cast<int32_t>(features.size());
     const fd_point_opts opts{options_.kMinFeatureDistance, options_.kMinValidResponse};
     const int32_t stride = static_cast<int32_t>(std::max<uint32_t>(needed_feature_num, 1u)) + 1;
@@ -122,10 +99,8 @@ bool FeaturePointDetector::DetectFused(const GrayImage &image, int kind, const u
                                     out.data(), stride, &count, 0);
     if (rc != FD_OK) return Fail("fd_points_detect");
 
-    for (int32_t i = 0; i < count; ++i) {
-        features.emplace_back(Vec2(out[2 * i], out[2 * i + 1]));
-        last_new_.emplace_back(Vec2(out[2 * i], out[2 * i + 1]));
-    }
+    last_new_ = Unflatten(out.data(), static_cast<size_t>(count));
+    features.insert(features.end(), last_new_.begin(), last_new_.end());
     staged_frame_ = dframe;
     last_reached_need_ = count > 0 && features.size() >= needed_feature_num;
     candidates_valid_ = false;
@@ -145,25 +120,19 @@ bool FeaturePointDetector::SelectOwnCandidates(const uint32_t needed_feature_num
         xs[i] = candidates_[i].second.x();
         ys[i] = candidates_[i].second.y();
     }
-    std::vector<float> prior(2 * features.size());
-    for (size_t i = 0; i < features.size(); ++i) {
-        prior[2 * i] = features[i].x();
-        prior[2 * i + 1] = features[i].y();
-    }
+    const std::vector<float> prior = Flatten(features);
     const int32_t nprior = static_cast<int32_t>(features.size());
     const fd_point_opts opts{options_.kMinFeatureDistance, options_.kMinValidResponse};
     const int32_t stride = static_cast<int32_t>(std::max<uint32_t>(needed_feature_num, 1u)) + 1;
     std::vector<float> out(2 * static_cast<size_t>(stride));
     const int64_t count_in = static_cast<int64_t>(n);
     int32_t count = 0;
-    const int rc = fd_points_select(ctx_, 1, last_rows_, last_cols_, &opts, resp.data(), xs.data(), ys.data(),
+    const int rc = fd_points_select(context_.get(), 1, last_rows_, last_cols_, &opts, resp.data(), xs.data(), ys.data(),
                                     &count_in, count_in, 0, nprior ? prior.data() : nullptr,
                                     nprior ? &nprior : nullptr, needed_feature_num, out.data(), stride, &count, 0);
     if (rc != FD_OK) return Fail("fd_points_select");
-    for (int32_t i = 0; i < count; ++i) {
-        features.emplace_back(Vec2(out[2 * i], out[2 * i + 1]));
-        last_new_.emplace_back(Vec2(out[2 * i], out[2 * i + 1]));
-    }
+    last_new_ = Unflatten(out.data(), static_cast<size_t>(count));
+    features.insert(features.end(), last_new_.begin(), last_new_.end());
     last_reached_need_ = count > 0 && features.size() >= needed_feature_num;
     mask_valid_ = false;
     return true;
@@ -173,19 +142,15 @@ bool FeaturePointDetector::SelectOwnCandidates(const uint32_t needed_feature_num
 // reference's ComputeCandidates pushes), recomputed on the GPU.
 bool FeaturePointDetector::FetchCandidates() {
     candidates_.clear();
-    if (fused_kind_ < 0 || !staged_frame_ || !ctx_) return false;
+    if (fused_kind_ < 0 || !staged_frame_ || !context_.get()) return false;
     const int64_t cap = static_cast<int64_t>(last_rows_) * last_cols_ / (fused_kind_ == FD_FAST ? 1 : 2) + 16;
     std::vector<float> resp(static_cast<size_t>(cap));
     std::vector<int32_t> xs(static_cast<size_t>(cap)), ys(static_cast<size_t>(cap));
-    std::vector<float> prior(2 * last_prior_.size());
-    for (size_t i = 0; i < last_prior_.size(); ++i) {
-        prior[2 * i] = last_prior_[i].x();
-        prior[2 * i + 1] = last_prior_[i].y();
-    }
+    const std::vector<float> prior = Flatten(last_prior_);
     const int32_t nprior = static_cast<int32_t>(last_prior_.size());
     const fd_point_opts opts{last_options_.kMinFeatureDistance, last_options_.kMinValidResponse};
     int64_t n = 0;
-    const int rc = fd_points_candidates(ctx_, fused_kind_, staged_frame_, 1, 1, last_rows_, last_cols_, &opts,
+    const int rc = fd_points_candidates(context_.get(), fused_kind_, staged_frame_, 1, 1, last_rows_, last_cols_, &opts,
                                         nprior ? prior.data() : nullptr, nprior ? &nprior : nullptr, resp.data(),
                                         xs.data(), ys.data(), cap, &n, nullptr, 0);
     if (rc != FD_OK) return Fail("fd_points_candidates");

@@ -7,45 +7,12 @@
 // own; the class is the convenience form for host images.
 #include "feature_detector/optical_flow_lk.h"
 
-#include <cstdio>
-#include <cstdlib>
-
 #include "fd_hip.h"
+#include "vec2_pack.h"
 
 namespace feature_detector {
 
-OpticalFlowLK::~OpticalFlowLK() {
-    if (ctx_) fd_ctx_destroy(ctx_);
-}
-
-void OpticalFlowLK::set_device(int device) {
-    if (ctx_ && device != device_) {
-        fd_ctx_destroy(ctx_);
-        ctx_ = nullptr;
-    }
-    device_ = device;
-}
-
-fd_ctx *OpticalFlowLK::Context() {
-    if (!ctx_) {
-        int dev = device_;
-        if (dev < 0) {
-            const char *e = std::getenv("FD_DEVICE");
-            dev = e ? std::atoi(e) : 0;
-        }
-        if (fd_ctx_create(dev, &ctx_) != FD_OK) {
-            ctx_ = nullptr;
-            Fail("fd_ctx_create failed (no MI355X visible?)");
-        }
-    }
-    return ctx_;
-}
-
-bool OpticalFlowLK::Fail(const std::string &what) {
-    error_ = what;
-    std::fprintf(stderr, "[feature_detector] %s\n", error_.c_str());
-    return false;
-}
+OpticalFlowLK::~OpticalFlowLK() = default;
 
 bool OpticalFlowLK::Track(const GrayImage &prev, const GrayImage &next, const std::vector<Vec2> &prev_uv,
                           std::vector<Vec2> &next_uv, std::vector<uint8_t> &status, std::vector<float> *error,
@@ -54,33 +21,26 @@ bool OpticalFlowLK::Track(const GrayImage &prev, const GrayImage &next, const st
     next_uv = prev_uv;
     status.assign(n, kInvalid);
     if (error) error->assign(n, -1.0f);
-    if (n == 0) return Fail("Track: no features");
-    if (guess_uv && guess_uv->size() != n) return Fail("Track: one guess per feature is needed");
-    if (!prev.data() || !next.data() || prev.rows() < 1 || prev.cols() < 1) return Fail("Track: empty image");
-    if (prev.rows() != next.rows() || prev.cols() != next.cols()) return Fail("Track: the images differ in size");
+    if (n == 0) return context_.Fail("Track: no features");
+    if (guess_uv && guess_uv->size() != n) return context_.Fail("Track: one guess per feature is needed");
+    if (!prev.data() || !next.data() || prev.rows() < 1 || prev.cols() < 1) return context_.Fail("Track: empty image");
+    if (prev.rows() != next.rows() || prev.cols() != next.cols()) return context_.Fail("Track: the images differ in size");
     const int rows = prev.rows(), cols = prev.cols(), levels = options_.kLevels;
     int64_t off[FD_PYR_MAX_LEVELS + 1];
     if (levels < 1 || levels > FD_PYR_MAX_LEVELS || fd_pyr_layout(1, rows, cols, levels, off) != FD_OK)
-        return Fail("Track: kLevels must be in 1..6 and the top level must keep a pixel");
-    fd_ctx *ctx = Context();
+        return context_.Fail("Track: kLevels must be in 1..6 and the top level must keep a pixel");
+    fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     const size_t total = static_cast<size_t>(off[levels]);
     pyramids_.resize(2 * total);
     if (fd_pyr_build(ctx, prev.data(), 0, 1, rows, cols, levels, pyramids_.data(), 0) != FD_OK ||
         fd_pyr_build(ctx, next.data(), 0, 1, rows, cols, levels, pyramids_.data() + total, 0) != FD_OK)
-        return Fail(std::string("fd_pyr_build: ") + fd_last_error(ctx));
+        return context_.FailCall("fd_pyr_build");
     const uint8_t *device = nullptr;
     if (fd_ctx_stage(ctx, pyramids_.data(), static_cast<int64_t>(2 * total), &device) != FD_OK)
-        return Fail(std::string("fd_ctx_stage: ") + fd_last_error(ctx));
-    std::vector<float> xy(2 * n), out(2 * n), guess(guess_uv ? 2 * n : 0);
-    for (size_t i = 0; i < n; ++i) {
-        xy[2 * i] = prev_uv[i].x();
-        xy[2 * i + 1] = prev_uv[i].y();
-        if (guess_uv) {
-            guess[2 * i] = (*guess_uv)[i].x();
-            guess[2 * i + 1] = (*guess_uv)[i].y();
-        }
-    }
+        return context_.FailCall("fd_ctx_stage");
+    const std::vector<float> xy = Flatten(prev_uv), guess = guess_uv ? Flatten(*guess_uv) : std::vector<float>();
+    std::vector<float> out(2 * n);
     const fd_flow_opts o{options_.kHalfWindow, options_.kMaxIterations, options_.kEpsilon, options_.kMinEigen,
                          options_.kMaxForwardBackward, options_.kMaxError};
     const int rc = fd_flow_lk(ctx, 1, rows, cols, levels, &o, device, device + total, xy.data(), nullptr, nullptr,
@@ -88,9 +48,9 @@ bool OpticalFlowLK::Track(const GrayImage &prev, const GrayImage &next, const st
                               error ? error->data() : nullptr, nullptr, 0);
     if (rc != FD_OK) {
         status.assign(n, kInvalid);
-        return Fail(std::string("fd_flow_lk: ") + fd_last_error(ctx));
+        return context_.FailCall("fd_flow_lk");
     }
-    for (size_t i = 0; i < n; ++i) next_uv[i] = Vec2(out[2 * i], out[2 * i + 1]);
+    next_uv = Unflatten(out.data(), n);
     return true;
 }
 

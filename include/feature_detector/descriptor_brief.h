@@ -12,8 +12,7 @@
 #include <vector>
 
 #include "descriptor.h"
-
-struct fd_ctx;
+#include "device_context.h"
 
 namespace feature_detector {
 
@@ -39,9 +38,9 @@ public:
 
     void set_sampler(int sampler) { sampler_ = sampler; }
     int sampler() const { return sampler_; }
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 protected:
     virtual bool ComputeForAllFeatures(const GrayImage &image, const std::vector<Vec2> &pixel_uv,
@@ -51,14 +50,11 @@ private:
     virtual bool ComputeForOneFeature(const GrayImage &image, const Vec2 &pixel_uv, BriefType &descriptor) const override;
     bool Run(const GrayImage &image, const Vec2 *uv, size_t n, std::vector<BriefType> &out,
              std::vector<uint8_t> *valid) const;
-    fd_ctx *Context() const;
 
 private:
     Options options_;
     int sampler_ = 0;  // FD_SAMPLE_BILINEAR
-    mutable fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    mutable std::string error_;
+    mutable DeviceContext context_;  // the reference's Compute is const; the context is created inside it
 };
 
 }  // namespace feature_detector

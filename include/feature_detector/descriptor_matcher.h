@@ -15,8 +15,7 @@
 #include <vector>
 
 #include "descriptor_brief.h"
-
-struct fd_ctx;
+#include "device_context.h"
 
 namespace feature_detector {
 
@@ -59,22 +58,18 @@ public:
     Options &options() { return options_; }
     const Options &options() const { return options_; }
 
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 private:
-    fd_ctx *Context();
-    bool Fail(const std::string &what);
     bool Run(const std::vector<BriefType> &query, const std::vector<BriefType> &train, const std::vector<Vec2> *query_uv,
              const std::vector<Vec2> *train_uv, float radius_x, float radius_y, std::vector<int32_t> &train_index,
              std::vector<int32_t> *distance, const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid);
 
 private:
     Options options_;
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    std::string error_;
+    DeviceContext context_;
 };
 
 /* Class NNDescriptorMatcher Declaration. */
@@ -118,13 +113,11 @@ public:
     Options &options() { return options_; }
     const Options &options() const { return options_; }
 
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 private:
-    fd_ctx *Context();
-    bool Fail(const std::string &what);
     bool Run(const float *query, int32_t n_query, const float *query_xy, const float *train, int32_t n_train,
              const float *train_xy, int32_t dim, bool guided, float radius_x, float radius_y,
              std::vector<int32_t> &train_index, std::vector<float> *distance, const std::vector<uint8_t> *query_valid,
@@ -132,9 +125,7 @@ private:
 
 private:
     Options options_;
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    std::string error_;
+    DeviceContext context_;
 };
 
 }  // namespace feature_detector

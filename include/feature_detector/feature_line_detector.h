@@ -9,9 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "device_context.h"
 #include "fd_types.h"
-
-struct fd_ctx;
 
 namespace feature_detector {
 
@@ -93,12 +92,11 @@ public:
 
     // MI355X extensions: GPU ordinal, last libfdhip error, and the number of dense map passes run so
     // far to materialise pixels() / sorted_pixels().
-    void set_device(int device);
-    const std::string &last_error() const { return error_; }
+    void set_device(int device) { context_.set_device(device); }
+    const std::string &last_error() const { return context_.last_error(); }
     int map_passes() const { return map_passes_; }
 
 private:
-    bool EnsureContext();
     // pixels_ / sorted_pixels_ as the reference leaves them (:56-97), from the GPU level-line map of
     // the frame staged by the last call, with each listed pixel's final is_used flag
     bool ComputeLineLevelAngleMap() const;
@@ -117,9 +115,7 @@ private:
     float last_min_norm_ = 0.0f;
     mutable int map_passes_ = 0;
 
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    mutable std::string error_;
+    mutable DeviceContext context_;  // the lazily materialised const accessors report their failures here
 };
 
 }  // namespace feature_detector

@@ -22,9 +22,8 @@
 #include <utility>
 #include <vector>
 
+#include "device_context.h"
 #include "fd_types.h"
-
-struct fd_ctx;
 
 namespace feature_detector {
 
@@ -62,9 +61,9 @@ public:
 
     // MI355X extensions: GPU ordinal used by this instance (default: $FD_DEVICE or 0), and the last
     // libfdhip error message.
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 protected:
     // For the built-in detectors' ComputeCandidates: instead of pushing candidates, hand the whole
@@ -99,9 +98,7 @@ private:
     std::vector<Vec2> last_prior_;
     std::vector<Vec2> last_new_;
     bool last_reached_need_ = false;
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    std::string error_;
+    DeviceContext context_;
 };
 
 /* Class FeaturePointHarrisDetector Declaration. */

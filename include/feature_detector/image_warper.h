@@ -10,9 +10,8 @@
 #include <cstdint>
 #include <string>
 
+#include "device_context.h"
 #include "fd_types.h"
-
-struct fd_ctx;
 
 namespace feature_detector {
 
@@ -46,19 +45,13 @@ public:
     Options &options() { return options_; }
     const Options &options() const { return options_; }
 
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
-
-private:
-    fd_ctx *Context();
-    bool Fail(const std::string &what);
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 private:
     Options options_;
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    std::string error_;
+    DeviceContext context_;
 };
 
 }  // namespace feature_detector

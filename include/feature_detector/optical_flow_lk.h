@@ -11,9 +11,8 @@
 #include <string>
 #include <vector>
 
+#include "device_context.h"
 #include "fd_types.h"
-
-struct fd_ctx;
 
 namespace feature_detector {
 
@@ -54,19 +53,13 @@ public:
     Options &options() { return options_; }
     const Options &options() const { return options_; }
 
-    void set_device(int device);
-    int device() const { return device_; }
-    const std::string &last_error() const { return error_; }
-
-private:
-    fd_ctx *Context();
-    bool Fail(const std::string &what);
+    void set_device(int device) { context_.set_device(device); }
+    int device() const { return context_.device(); }
+    const std::string &last_error() const { return context_.last_error(); }
 
 private:
     Options options_;
-    fd_ctx *ctx_ = nullptr;
-    int device_ = -1;
-    std::string error_;
+    DeviceContext context_;
     std::vector<uint8_t> pyramids_;  // both packed pyramids, built on the GPU into host memory, then staged in one upload
 };
 

@@ -4,37 +4,13 @@
 //   usage: fd_demo_refine <raw u8 gray file> <rows> <cols> [half_window] [max_shift]
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/corner_refiner.h"
 #include "feature_detector/feature_point_detector.h"
 
 using namespace feature_detector;
-
-static uint8_t *ReadFrame(const char *path, int rows, int cols) {
-    const size_t n = static_cast<size_t>(rows) * cols;
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(n));
-    FILE *f = std::fopen(path, "rb");
-    if (!f || std::fread(buf, 1, n, f) != n) {
-        std::fprintf(stderr, "cannot read %s\n", path);
-        std::exit(2);
-    }
-    std::fclose(f);
-    return buf;
-}
-
-static unsigned Bits(float v) {
-    unsigned u;
-    std::memcpy(&u, &v, sizeof(u));
-    return u;
-}
-
-static void PrintError(const std::string &e) {
-    std::printf("\"error\": \"");
-    for (char ch : e) std::putchar(ch == '"' || ch == '\\' || static_cast<unsigned char>(ch) < 32 ? ' ' : ch);
-    std::printf("\"");
-}
 
 int main(int argc, char **argv) {
     if (argc < 4) {

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/feature_point_detector.h"
 
 using namespace feature_detector;
@@ -95,15 +96,7 @@ int main(int argc, char **argv) {
     const int rows = std::atoi(argv[2]), cols = std::atoi(argv[3]);
     const int dist = std::atoi(argv[5]), need = std::atoi(argv[6]);
     const bool prior = argc > 7 && std::atoi(argv[7]) != 0;
-    std::vector<uint8_t> buf(static_cast<size_t>(rows) * cols);
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f || std::fread(buf.data(), 1, buf.size(), f) != buf.size()) {
-        std::fprintf(stderr, "cannot read %s\n", argv[1]);
-        return 2;
-    }
-    std::fclose(f);
-    GrayImage image;
-    image.SetImage(buf.data(), rows, cols, false);
+    GrayImage image(ReadFrame(argv[1], rows, cols), rows, cols, true);
 
     const bool harris = argc > 8 && std::string(argv[8]) == "harris";
     return harris ? Run<FeaturePointHarrisDetector>(image, argv[4], dist, need, prior)

@@ -7,23 +7,12 @@
 #include <cstdlib>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/descriptor_brief.h"
 #include "feature_detector/descriptor_matcher.h"
 #include "feature_detector/feature_point_detector.h"
 
 using namespace feature_detector;
-
-static uint8_t *ReadFrame(const char *path, int rows, int cols) {
-    const size_t n = static_cast<size_t>(rows) * cols;
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(n));
-    FILE *f = std::fopen(path, "rb");
-    if (!f || std::fread(buf, 1, n, f) != n) {
-        std::fprintf(stderr, "cannot read %s\n", path);
-        std::exit(2);
-    }
-    std::fclose(f);
-    return buf;
-}
 
 static std::vector<BriefType> Describe(const char *name, const GrayImage &image) {
     FeaturePointHarrisDetector detector;

@@ -1,6 +1,6 @@
 // Headless driver of BriefMatcher::MatchGuided and NNDescriptorMatcher::MatchGuided
 // (include/feature_detector/descriptor_matcher.h) for tests/test_cpp_match_guided.py.
-//   match_guided_demo <fixture> <radius_x> <radius_y> <max_ratio> <cross_check>
+//   fd_demo_match_guided <fixture> <radius_x> <radius_y> <max_ratio> <cross_check>
 // fixture: int32 n_query, n_train, dim, length; float query[n_query][dim]; float train[n_train][dim];
 //          uint32 query_bits[n_query][8]; uint32 train_bits[n_train][8]; float query_xy[n_query][2];
 //          float train_xy[n_train][2]; uint8 query_valid[n_query]; uint8 train_valid[n_train]
@@ -9,10 +9,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/descriptor_matcher.h"
 
 using feature_detector::BriefMatcher;
@@ -41,11 +41,7 @@ void PrintRun(const char *name, bool ok, const std::vector<int32_t> &index, cons
 void PrintRun(const char *name, bool ok, const std::vector<int32_t> &index, const std::vector<float> &distance) {
     PrintHead(name, ok, index);
     std::printf("], \"distance_bits\": [");
-    for (size_t i = 0; i < distance.size(); ++i) {
-        uint32_t u;
-        std::memcpy(&u, &distance[i], sizeof(u));
-        std::printf("%s%u", i ? ", " : "", u);
-    }
+    for (size_t i = 0; i < distance.size(); ++i) std::printf("%s%u", i ? ", " : "", Bits(distance[i]));
     std::printf("]}\n");
 }
 

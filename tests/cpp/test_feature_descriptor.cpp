@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/descriptor_brief.h"
 #include "feature_detector/feature_point_detector.h"
 
@@ -63,14 +64,7 @@ int main(int argc, char **argv) {
     }
     const int rows = std::atoi(argv[2]), cols = std::atoi(argv[3]);
     const int sampler = argc > 4 ? std::atoi(argv[4]) : 0;
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(static_cast<size_t>(rows) * cols));
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f || std::fread(buf, 1, static_cast<size_t>(rows) * cols, f) != static_cast<size_t>(rows) * cols) {
-        std::fprintf(stderr, "cannot read %s\n", argv[1]);
-        return 2;
-    }
-    std::fclose(f);
-    GrayImage image(buf, rows, cols, true);
+    GrayImage image(ReadFrame(argv[1], rows, cols), rows, cols, true);
     const int32_t feature_num_need = 10;  // :63
     const std::vector<Vec2> features = TestHarrisFeatureDetector(image, feature_num_need);
     TestBriefDescriptor(image, features, sampler);

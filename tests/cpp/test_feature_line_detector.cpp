@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/feature_line_detector.h"
 
 using namespace feature_detector;
@@ -16,14 +17,7 @@ int main(int argc, char **argv) {
         return 2;
     }
     const int rows = std::atoi(argv[2]), cols = std::atoi(argv[3]);
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(static_cast<size_t>(rows) * cols));
-    FILE *f = std::fopen(argv[1], "rb");
-    if (!f || std::fread(buf, 1, static_cast<size_t>(rows) * cols, f) != static_cast<size_t>(rows) * cols) {
-        std::fprintf(stderr, "cannot read %s\n", argv[1]);
-        return 2;
-    }
-    std::fclose(f);
-    GrayImage image(buf, rows, cols, true);
+    GrayImage image(ReadFrame(argv[1], rows, cols), rows, cols, true);
 
     FeatureLineDetector detector;  // :100-106
     std::vector<Vec4> features;

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/feature_point_detector.h"
 #include "feature_detector/image_io.h"
 
@@ -83,14 +84,7 @@ int main(int argc, char **argv) {
         }
         const int rows = std::atoi(argv[2]), cols = std::atoi(argv[3]);
         if (argc > 4) feature_num_need = std::atoi(argv[4]);
-        uint8_t *buf = static_cast<uint8_t *>(std::malloc(static_cast<size_t>(rows) * cols));
-        FILE *f = std::fopen(argv[1], "rb");
-        if (!f || std::fread(buf, 1, static_cast<size_t>(rows) * cols, f) != static_cast<size_t>(rows) * cols) {
-            std::fprintf(stderr, "cannot read %s\n", argv[1]);
-            return 2;
-        }
-        std::fclose(f);
-        image.SetImage(buf, rows, cols, true);
+        image.SetImage(ReadFrame(argv[1], rows, cols), rows, cols, true);
     }
 
     TestFastFeatureDetector(image, feature_num_need);  // :106-109

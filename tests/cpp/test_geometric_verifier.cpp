@@ -5,18 +5,12 @@
 //   usage: fd_demo_geometry <raw float32 file of n x 4: qx qy tx ty> <n> <rows> <cols> [model 0|1] [hypotheses] [seed]
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/geometric_verifier.h"
 
 using namespace feature_detector;
-
-static unsigned long long Bits(double v) {
-    unsigned long long u;
-    std::memcpy(&u, &v, sizeof(u));
-    return u;
-}
 
 static void Print(const char *test, bool ok, const std::vector<uint8_t> &inlier, const std::array<double, 9> &model, int32_t best) {
     std::printf("{\"test\": \"%s\", \"ok\": %s, \"best\": %d, \"inlier\": [", test, ok ? "true" : "false", best);

@@ -5,40 +5,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/image_warper.h"
 
 using namespace feature_detector;
-
-static uint8_t *ReadFrame(const char *path, int rows, int cols) {
-    const size_t n = static_cast<size_t>(rows) * cols;
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(n));
-    FILE *f = std::fopen(path, "rb");
-    if (!f || std::fread(buf, 1, n, f) != n) {
-        std::fprintf(stderr, "cannot read %s\n", path);
-        std::exit(2);
-    }
-    std::fclose(f);
-    return buf;
-}
-
-static void WriteBytes(const std::string &path, const std::vector<uint8_t> &v) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f || std::fwrite(v.data(), 1, v.size(), f) != v.size()) {
-        std::fprintf(stderr, "cannot write %s\n", path.c_str());
-        std::exit(2);
-    }
-    std::fclose(f);
-}
-
-static void PrintError(const std::string &e) {
-    std::printf("\"error\": \"");
-    for (char ch : e) std::putchar(ch == '"' || ch == '\\' || static_cast<unsigned char>(ch) < 32 ? ' ' : ch);
-    std::printf("\"");
-}
 
 static void Run(ImageWarper &warper, const char *test, const GrayImage &src, const std::vector<double> &params, int out_rows,
                 int out_cols, const std::string &prefix) {
@@ -47,11 +20,7 @@ static void Run(ImageWarper &warper, const char *test, const GrayImage &src, con
     GrayImage dst(out.data(), out_rows, out_cols);
     const bool ok = warper.Warp(src, params.data(), dst, mask.data());
     std::printf("{\"test\": \"%s\", \"ok\": %s, \"params_bits\": [", test, ok ? "true" : "false");
-    for (size_t i = 0; i < params.size(); ++i) {
-        unsigned long long u;
-        std::memcpy(&u, &params[i], sizeof(u));
-        std::printf("%s%llu", i ? ", " : "", u);
-    }
+    for (size_t i = 0; i < params.size(); ++i) std::printf("%s%llu", i ? ", " : "", Bits(params[i]));
     std::printf("], \"untouched\": %s, ", out[0] == 0xA5 && out[n - 1] == 0xA5 && mask[n / 2] == 0xA5 ? "true" : "false");
     PrintError(ok ? std::string() : warper.last_error());
     std::printf("}\n");

@@ -1,6 +1,6 @@
 // Headless driver of NNDescriptorMatcher (include/feature_detector/descriptor_matcher.h) for
 // tests/test_cpp_nn_match.py.
-//   nn_match_demo <fixture> [max_distance max_ratio cross_check]
+//   fd_demo_nn_match <fixture> [max_distance max_ratio cross_check]
 // fixture: int32 n_query, n_train, dim; float query[n_query][dim]; float train[n_train][dim];
 //          uint8 query_valid[n_query]; uint8 train_valid[n_train]
 // Prints one JSON line per run: without and with the valid flags, then the false cases. Distances are
@@ -8,9 +8,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/descriptor_matcher.h"
 
 using feature_detector::NNDescriptorMatcher;
@@ -21,11 +21,7 @@ void PrintRun(const char *name, bool ok, const std::vector<int32_t> &index, cons
     std::printf("{\"test\": \"%s\", \"ok\": %s, \"train_index\": [", name, ok ? "true" : "false");
     for (size_t i = 0; i < index.size(); ++i) std::printf("%s%d", i ? ", " : "", index[i]);
     std::printf("], \"distance_bits\": [");
-    for (size_t i = 0; i < distance.size(); ++i) {
-        uint32_t u;
-        std::memcpy(&u, &distance[i], sizeof(u));
-        std::printf("%s%u", i ? ", " : "", u);
-    }
+    for (size_t i = 0; i < distance.size(); ++i) std::printf("%s%u", i ? ", " : "", Bits(distance[i]));
     std::printf("]}\n");
 }
 

@@ -5,31 +5,13 @@
 //                       [levels] [half_window] [max_forward_backward]
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
+#include "demo_util.h"
 #include "feature_detector/feature_point_detector.h"
 #include "feature_detector/optical_flow_lk.h"
 
 using namespace feature_detector;
-
-static uint8_t *ReadFrame(const char *path, int rows, int cols) {
-    const size_t n = static_cast<size_t>(rows) * cols;
-    uint8_t *buf = static_cast<uint8_t *>(std::malloc(n));
-    FILE *f = std::fopen(path, "rb");
-    if (!f || std::fread(buf, 1, n, f) != n) {
-        std::fprintf(stderr, "cannot read %s\n", path);
-        std::exit(2);
-    }
-    std::fclose(f);
-    return buf;
-}
-
-static unsigned Bits(float v) {
-    unsigned u;
-    std::memcpy(&u, &v, sizeof(u));
-    return u;
-}
 
 int main(int argc, char **argv) {
     if (argc < 5) {

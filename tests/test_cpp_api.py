@@ -1,42 +1,34 @@
 """The C++ drop-in API (include/feature_detector/*, libfeature_detector.so) driven by headless
 restatements of the reference demos (tests/cpp/*.cpp mirror test/test_feature_point_detector.cpp and
 test/test_feature_line_detector.cpp). GPU tests compare with the oracle / the reference's counts."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
+import cpp_demo
+from cpp_demo import LIB, build as _build
+
 KIND = {"harris": 0, "shi_tomasi": 1, "fast": 2, "harris_prior": 0}
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0, "harris_prior": 30.0}
 
 
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
-
-
 def _run(prog, img, tmp_path, *extra):
+    """The demo's records in order, on `img` written as a raw frame."""
     raw = tmp_path / "frame.u8"
     np.ascontiguousarray(img, np.uint8).tofile(raw)
-    out = subprocess.run([os.path.join(LIB, prog), str(raw), str(img.shape[0]), str(img.shape[1]), *map(str, extra)],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr
-    return [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    return list(cpp_demo.run(prog, raw, img.shape[0], img.shape[1], *extra)[0].values())
 
 
 def test_api_builds_and_links():
     _build()
     for f in ("libfeature_detector.so", "fd_demo_points", "fd_demo_lines", "fd_demo_descriptor"):
         assert os.path.exists(os.path.join(LIB, f))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
     for sym in ("feature_detector::FeaturePointDetector::DetectGoodFeatures",
                 "feature_detector::FeaturePointDetector::SparsifyFeatures",
                 "feature_detector::FeatureLineDetector::DetectGoodFeatures",
                 "feature_detector::BriefDescriptor::ComputeForAllFeatures"):
-        assert sym in nm
+        assert cpp_demo.exported(sym)
 
 
 def test_without_gpu_calls_fail_loudly(tmp_path, image_png):

@@ -1,22 +1,16 @@
 """The C++ OpticalFlowLK (include/feature_detector/optical_flow_lk.h, an MI355X extension) driven by the
 headless demo tests/cpp/test_optical_flow.cpp (fd_demo_flow). The GPU tests compare with tests/flow_ref.py
 on the features the demo printed."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 import flow_ref as R
+from cpp_demo import LIB, build as _build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 RUNS = ((), (2, 4, 0.5))  # (levels, half_window, max_forward_backward); (): the class defaults
-
-
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
 
 
 @pytest.fixture(scope="module")
@@ -27,20 +21,14 @@ def demo_runs(tmp_path_factory, image_png):
     frames = [np.ascontiguousarray(image_png[24:264, 24:344]), np.ascontiguousarray(image_png[26:266, 21:341])]
     for i, f in enumerate(frames):
         f.tofile(d / f"frame{i}.u8")
-    runs = {}
-    for extra in RUNS:
-        out = subprocess.run([os.path.join(LIB, "fd_demo_flow"), str(d / "frame0.u8"), "240", "320", str(d / "frame1.u8"),
-                              *map(str, extra)], capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stderr
-        runs[extra] = {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+    runs = {extra: cpp_demo.run("fd_demo_flow", d / "frame0.u8", 240, 320, d / "frame1.u8", *extra)[0] for extra in RUNS}
     return frames, runs
 
 
 def test_demo_builds_and_exports_tracker():
     _build()
     assert os.path.exists(os.path.join(LIB, "fd_demo_flow"))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::OpticalFlowLK::Track" in nm
+    assert cpp_demo.exported("feature_detector::OpticalFlowLK::Track")
 
 
 @pytest.mark.gpu

@@ -1,21 +1,14 @@
 """The C++ BriefMatcher (include/feature_detector/descriptor_matcher.h, an MI355X extension) driven by
 the headless demo tests/cpp/test_descriptor_matcher.cpp (fd_demo_match). The GPU tests compare with
 tests/match_ref.py on the oracle's BRIEF bits of the features the demo printed."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
+from cpp_demo import LIB, build as _build
 from match_ref import match_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
-
-
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
 
 
 @pytest.fixture(scope="module")
@@ -26,21 +19,15 @@ def demo_runs(tmp_path_factory, image_png):
     frames = [image_png, np.roll(image_png, (3, 5), (0, 1))]
     for i, f in enumerate(frames):
         np.ascontiguousarray(f, np.uint8).tofile(d / f"frame{i}.u8")
-    runs = {}
-    for extra in ((), (64, 0.9, 1)):
-        out = subprocess.run([os.path.join(LIB, "fd_demo_match"), str(d / "frame0.u8"), str(image_png.shape[0]),
-                              str(image_png.shape[1]), str(d / "frame1.u8"), *map(str, extra)],
-                             capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stderr
-        runs[extra] = {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+    runs = {extra: cpp_demo.run("fd_demo_match", d / "frame0.u8", *image_png.shape, d / "frame1.u8", *extra)[0]
+            for extra in ((), (64, 0.9, 1))}
     return frames, runs
 
 
 def test_demo_builds_and_exports_matcher():
     _build()
     assert os.path.exists(os.path.join(LIB, "fd_demo_match"))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::BriefMatcher::Match" in nm
+    assert cpp_demo.exported("feature_detector::BriefMatcher::Match")
 
 
 @pytest.mark.gpu

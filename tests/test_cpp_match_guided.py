@@ -1,36 +1,28 @@
 """The C++ BriefMatcher::MatchGuided and NNDescriptorMatcher::MatchGuided
 (include/feature_detector/descriptor_matcher.h) driven by the headless program
-tests/cpp/test_descriptor_matcher_guided.cpp, which this test compiles against include/ and
-libfeature_detector.so. The GPU test compares with tests/match_guided_ref.py on a fixture the test writes."""
-import json
+tests/cpp/test_descriptor_matcher_guided.cpp (fd_demo_match_guided). The GPU test compares with
+tests/match_guided_ref.py on a fixture the test writes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 import match_guided_ref as G
 from match_guided_ref import match_guided_ref, nn_match_guided_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 F32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def demo(tmp_path_factory):
-    """The program, built against the drop-in library (rpath: the package's lib directory)."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
-    exe = tmp_path_factory.mktemp("match_guided") / "match_guided_demo"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra",
-                           "-I" + os.path.join(ROOT, "include"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "cpp", "test_descriptor_matcher_guided.cpp"), "-L" + LIB,
-                           "-lfeature_detector", "-lfdhip", "-Wl,-rpath," + LIB])
-    return str(exe)
+def demo():
+    """The program, built against the drop-in library."""
+    cpp_demo.build()
+    return "fd_demo_match_guided"
 
 
 def test_program_builds_against_the_headers(demo):
-    assert os.path.exists(demo)
+    assert os.path.exists(os.path.join(cpp_demo.LIB, demo))
 
 
 def _fixture(path, dim, length):
@@ -48,10 +40,7 @@ def _fixture(path, dim, length):
 @pytest.mark.parametrize("dim,length,rx,ry,ratio,cross", [(256, 256, 8.0, 8.0, 0.0, 0), (128, 100, 3.0, 11.0, 0.95, 1)])
 def test_match_guided_equals_ref(demo, tmp_path, dim, length, rx, ry, ratio, cross):
     b, n = _fixture(tmp_path / "fixture.bin", dim, length)
-    out = subprocess.run([demo, str(tmp_path / "fixture.bin"), *map(str, (rx, ry, ratio, cross))], capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0, out.stderr
-    res = {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+    res, _ = cpp_demo.run(demo, tmp_path / "fixture.bin", rx, ry, ratio, cross)
     kw = dict(max_ratio=ratio, cross_check=bool(cross))
     for name, valid in (("", (None, None)), ("_valid", (b["qv"], b["tv"]))):
         idx, dist, counts = match_guided_ref(b["q"], b["t"], b["q_xy"], b["t_xy"], (rx, ry), q_valid=valid[0],

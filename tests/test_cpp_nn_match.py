@@ -1,37 +1,27 @@
 """The C++ NNDescriptorMatcher (include/feature_detector/descriptor_matcher.h, an MI355X extension)
-driven by the headless program tests/cpp/test_nn_descriptor_matcher.cpp, which this test compiles against
-include/ and libfeature_detector.so. The GPU tests compare with tests/nn_match_ref.py on a fixture the
-test writes."""
-import json
+driven by the headless program tests/cpp/test_nn_descriptor_matcher.cpp (fd_demo_nn_match). The GPU tests
+compare with tests/nn_match_ref.py on a fixture the test writes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 from nn_match_ref import nn_match_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 F32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def demo(tmp_path_factory):
-    """The program, built against the drop-in library (rpath: the package's lib directory)."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
-    exe = tmp_path_factory.mktemp("nn_match") / "nn_match_demo"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra",
-                           "-I" + os.path.join(ROOT, "include"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "cpp", "test_nn_descriptor_matcher.cpp"), "-L" + LIB,
-                           "-lfeature_detector", "-lfdhip", "-Wl,-rpath," + LIB])
-    return str(exe)
+def demo():
+    """The program, built against the drop-in library."""
+    cpp_demo.build()
+    return "fd_demo_nn_match"
 
 
 def test_program_builds_and_library_exports_matcher(demo):
-    assert os.path.exists(demo)
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::NNDescriptorMatcher::Match" in nm
+    assert os.path.exists(os.path.join(cpp_demo.LIB, demo))
+    assert cpp_demo.exported("feature_detector::NNDescriptorMatcher::Match")
 
 
 def _fixture(path, dim):
@@ -57,10 +47,7 @@ def _fixture(path, dim):
 @pytest.mark.parametrize("dim", [256, 128])
 def test_nn_matcher_equals_ref(demo, tmp_path, dim, extra):
     q, t, qv, tv = _fixture(tmp_path / "fixture.bin", dim)
-    out = subprocess.run([demo, str(tmp_path / "fixture.bin"), *map(str, extra)], capture_output=True, text=True,
-                         timeout=300)
-    assert out.returncode == 0, out.stderr
-    res = {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+    res, _ = cpp_demo.run(demo, tmp_path / "fixture.bin", *extra)
     kw = dict(zip(("max_distance", "max_ratio", "cross_check"), extra))
     kw["cross_check"] = bool(kw.get("cross_check", 0))
     for name, valid in (("match", (None, None)), ("match_valid", (qv[None], tv[None]))):

@@ -1,23 +1,17 @@
 """The C++ GeometricVerifier (include/feature_detector/geometric_verifier.h, an MI355X extension) driven by
 the headless demo tests/cpp/test_geometric_verifier.cpp (fd_demo_geometry). The GPU tests compare what the
 demo printed with tests/ransac_ref.py."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 import ransac_ref as R
+from cpp_demo import LIB, build as _build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 RUNS = ((R.FUNDAMENTAL, 256, 0), (R.HOMOGRAPHY, 100, 7))  # (model, hypotheses, seed)
 CENTER, SCALE = R.conditioning((R.ROWS, R.COLS))
-
-
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
 
 
 @pytest.fixture(scope="module")
@@ -29,18 +23,14 @@ def demo_runs(tmp_path_factory):
         q, t, _ = R.planted_scene(model, 1)
         path = d / f"pairs{model}.f32"
         np.concatenate([q, t], axis=1).astype(np.float32).tofile(path)
-        out = subprocess.run([os.path.join(LIB, "fd_demo_geometry"), str(path), str(len(q)), str(R.ROWS), str(R.COLS), str(model),
-                              str(hyp), str(seed)], capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stderr
-        runs[model] = (q, t, {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))})
+        runs[model] = (q, t, cpp_demo.run("fd_demo_geometry", path, len(q), R.ROWS, R.COLS, model, hyp, seed)[0])
     return runs
 
 
 def test_demo_builds_and_exports_verifier():
     _build()
     assert os.path.exists(os.path.join(LIB, "fd_demo_geometry"))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::GeometricVerifier::Verify" in nm
+    assert cpp_demo.exported("feature_detector::GeometricVerifier::Verify")
 
 
 @pytest.mark.gpu

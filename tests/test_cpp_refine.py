@@ -1,29 +1,20 @@
 """The C++ CornerRefiner (include/feature_detector/corner_refiner.h, an MI355X extension) driven by the headless
 demo tests/cpp/test_corner_refiner.cpp (fd_demo_refine). The GPU tests compare with tests/refine_ref.py on the
 features the demo printed."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 import refine_ref as R
+from cpp_demo import LIB, build as _build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 RUNS = ((), (3, 1.5))  # (half_window, max_shift); (): the class defaults
 
 
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
-
-
-def _run(frame_path, extra):
-    out = subprocess.run([os.path.join(LIB, "fd_demo_refine"), str(frame_path), "240", "320", *map(str, extra)],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr
-    return {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+def _run(frame_path, extra, env=None):
+    return cpp_demo.run("fd_demo_refine", frame_path, 240, 320, *extra, env=env)
 
 
 @pytest.fixture(scope="module")
@@ -37,27 +28,22 @@ def frame(tmp_path_factory, image_png):
 
 @pytest.fixture(scope="module")
 def demo_runs(frame):
-    return {extra: _run(frame[1], extra) for extra in RUNS}
+    return {extra: _run(frame[1], extra)[0] for extra in RUNS}
 
 
 def test_demo_builds_and_exports_refiner():
     _build()
     assert os.path.exists(os.path.join(LIB, "fd_demo_refine"))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::CornerRefiner::Refine" in nm
+    assert cpp_demo.exported("feature_detector::CornerRefiner::Refine")
 
 
 def test_without_a_gpu_the_class_fails_loudly(frame):
     """No device visible to the demo: Refine returns false, the position stays, last_error() says why."""
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
-    out = subprocess.run([os.path.join(LIB, "fd_demo_refine"), str(frame[1]), "240", "320"], capture_output=True, text=True,
-                         timeout=300, env=env)
-    assert out.returncode == 0, out.stderr
-    res = {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}
+    res, stderr = _run(frame[1], (), cpp_demo.NO_GPU_ENV)
     c = res["centre"]
     assert c["ok"] is False and c["status"] == 0 and c["error"].strip()
     assert np.array_equal(np.array(c["xy_bits"], np.uint32).view(np.float32), np.array([160, 120], np.float32))
-    assert res["refine"]["ok"] is False and "fd_ctx_create" in out.stderr
+    assert res["refine"]["ok"] is False and "fd_ctx_create" in stderr
 
 
 @pytest.mark.gpu

@@ -1,29 +1,20 @@
 """The C++ ImageWarper (include/feature_detector/image_warper.h, an MI355X extension) driven by the headless
 demo tests/cpp/test_image_warper.cpp (fd_demo_warp). The GPU test compares the frames the demo wrote with
 tests/warp_ref.py on the parameter bits the demo printed."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_demo
 import warp_ref as W
+from cpp_demo import LIB, build as _build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "feature_detector_amd", "lib")
 OUT_SHAPE = (203, 331)
 
 
-def _build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
-
-
 def _run(frame_path, prefix, env=None):
-    out = subprocess.run([os.path.join(LIB, "fd_demo_warp"), str(frame_path), "240", "320", *map(str, OUT_SHAPE), str(prefix)],
-                         capture_output=True, text=True, timeout=300, env=env)
-    assert out.returncode == 0, out.stderr
-    return {r["test"]: r for r in (json.loads(l) for l in out.stdout.splitlines() if l.startswith("{"))}, out.stderr
+    return cpp_demo.run("fd_demo_warp", frame_path, 240, 320, *OUT_SHAPE, prefix, env=env)
 
 
 @pytest.fixture(scope="module")
@@ -38,14 +29,12 @@ def frame(tmp_path_factory, image_png):
 def test_demo_builds_and_exports_warper():
     _build()
     assert os.path.exists(os.path.join(LIB, "fd_demo_warp"))
-    nm = subprocess.run(["nm", "-DC", os.path.join(LIB, "libfeature_detector.so")], capture_output=True, text=True).stdout
-    assert "feature_detector::ImageWarper::Warp" in nm
+    assert cpp_demo.exported("feature_detector::ImageWarper::Warp")
 
 
 def test_without_a_gpu_the_class_fails_loudly(frame):
     """No device visible to the demo: Warp returns false, the destination stays, last_error() says why."""
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
-    res, stderr = _run(frame[1], frame[2] / "nogpu", env)
+    res, stderr = _run(frame[1], frame[2] / "nogpu", cpp_demo.NO_GPU_ENV)
     for test in ("homography", "camera"):
         assert res[test]["ok"] is False and res[test]["untouched"] is True and res[test]["error"].strip()
         assert not os.path.exists(str(frame[2] / "nogpu") + f".{test}.u8")

@@ -7,12 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "feature_detector_amd", "lib", "fd_demo_sparsify")
+import cpp_demo
+
+EXE = os.path.join(cpp_demo.LIB, "fd_demo_sparsify")
 
 
 def _run(xy, status, rows, cols, gr, gc, need, after):
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "feature_detector_amd", "api")])
+    cpp_demo.build()
     lines = [str(len(xy))] + [f"{x!r} {y!r} {s}" for (x, y), s in zip(xy.tolist(), status)]
     out = subprocess.run([EXE, str(rows), str(cols), str(gr), str(gc), str(need), str(after)],
                          input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
