@@ -30,6 +30,9 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, ui
 __device__ __forceinline__ uint32_t buf_load_u32(__amdgpu_buffer_rsrc_t r, int32_t byte_off) {
     return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
 }
+__device__ __forceinline__ uint32_t buf_load_u16(__amdgpu_buffer_rsrc_t r, int32_t byte_off) {
+    return static_cast<uint16_t>(__builtin_amdgcn_raw_buffer_load_b16(r, byte_off, 0, 0));
+}
 __device__ __forceinline__ uint32_t buf_load_u8(__amdgpu_buffer_rsrc_t r, int32_t byte_off) {
     return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b8(r, byte_off, 0, 0));
 }

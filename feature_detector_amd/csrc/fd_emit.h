@@ -43,24 +43,27 @@ constexpr int kPixWg = 256;
 // LDS accesses all issued before any is used (the histogram loops were chains of one LDS round trip,
 // and in the flush one exec-masked branch, per bin group); the clear by 16-byte stores (h is 16-byte
 // aligned in every LDS layout: DetectLdsT, LpLds, k_heat_candidates, k_cand_lists).
-constexpr int kHistPer = kHistBins / (4 * kPixWg);  // uint4 groups per thread
+// (WG: the workgroup's threads, for the kernels that run another size than kPixWg)
+template <int WG = kPixWg>
 __device__ __forceinline__ void hist_clear(uint32_t *h) {
+    constexpr int kHistPer = kHistBins / (4 * WG);  // uint4 groups per thread
     uint4 *h4 = reinterpret_cast<uint4 *>(h);
 #pragma unroll
-    for (int k = 0; k < kHistPer; ++k) h4[threadIdx.x + k * kPixWg] = make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < kHistPer; ++k) h4[threadIdx.x + k * WG] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
 }
 // The flush keeps one bin per lane per atomic instruction (64 consecutive dwords: a 4-dwords-per-lane
 // pattern spreads each wave instruction over 4x the 64-B atomic requests, measured +4.9 us at batch 1).
+template <int WG = kPixWg>
 __device__ __forceinline__ void hist_flush(const uint32_t *h, uint32_t *g) {
     __syncthreads();
-    constexpr int kPer = kHistBins / kPixWg;
+    constexpr int kPer = kHistBins / WG;
     uint32_t v[kPer];
 #pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = h[threadIdx.x + k * kPixWg];
+    for (int k = 0; k < kPer; ++k) v[k] = h[threadIdx.x + k * WG];
 #pragma unroll
     for (int k = 0; k < kPer; ++k)
-        if (v[k]) atomicAdd(&g[threadIdx.x + k * kPixWg], v[k]);
+        if (v[k]) atomicAdd(&g[threadIdx.x + k * WG], v[k]);
 }
 
 // Append the n (wave-uniform) candidates a wave staged in LDS to frame f's list: one returning atomic
@@ -95,9 +98,10 @@ __device__ __forceinline__ void wave_append(const CandList &l, int f, const floa
 //   visit(fn)     fn(response, raster index) for each of this lane's entries
 //   counted()     the entries are in `hist` already (counted when they were staged)
 //   flush(a, f)   the source's plain append (the wave's entries and their histogram counts)
-template <class Src>
+template <int WG = kPixWg, class Src>
 __device__ __forceinline__ void seg_list_flush(Src &src, const PointsArgs &a, int f, int g, bool active, uint32_t *hist,
-                                               const uint32_t *ovf, uint32_t (&wtot)[4], uint32_t &wg_base) {
+                                               const uint32_t *ovf, uint32_t (&wtot)[WG / kWave], uint32_t &wg_base) {
+    constexpr int kWaves = WG / kWave;
     const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
     if (!active) src.n = 0;
     const uint32_t wn = src.wave_total();
@@ -105,21 +109,23 @@ __device__ __forceinline__ void seg_list_flush(Src &src, const PointsArgs &a, in
     __syncthreads();
     if (*ovf) {  // part of the workgroup's list is already out unsorted: plain flush (frame marked)
         if (active) src.flush(a, f);
-        hist_flush(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
+        hist_flush<WG>(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);
         return;
     }
     // The segment's place in the list: one returning atomic, issued before the histogram work so that
     // its round trip overlaps the counting sort's scan (thread 0 waits for it only at its LDS store).
     uint32_t seg_base_early = 0;
-    const uint32_t seg_total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    uint32_t seg_total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+#pragma unroll
+    for (int q = 4; q < kWaves; ++q) seg_total += wtot[q];
     if (tid == 0 && seg_total) seg_base_early = atomicAdd(&a.list.count[f], seg_total);
     const uint32_t kb = a.list.key_base;
     const int lz = a.list.key_lz;
     if (!src.counted()) src.visit([&](float r, uint32_t) { atomicAdd(&hist[level0_bin(r, kb, lz)], 1u); });
-    hist_flush(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);  // (leads with a barrier)
+    hist_flush<WG>(hist, a.list.hist0 + static_cast<int64_t>(f) * kHistBins);  // (leads with a barrier)
     __syncthreads();
     // in place: hist[b] = entries of bins above b (exclusive scan in descending bin order)
-    constexpr int kPer = kHistBins / kPixWg;
+    constexpr int kPer = kHistBins / WG;
     uint32_t v[kPer], sum = 0;
 #pragma unroll
     for (int k = 0; k < kPer; ++k) sum += (v[k] = hist[kHistBins - 1 - (tid * kPer + k)]);
@@ -127,7 +133,7 @@ __device__ __forceinline__ void seg_list_flush(Src &src, const PointsArgs &a, in
     if (lane == kWave - 1) wtot[wv] = incl;
     __syncthreads();
     uint32_t run = incl - sum, total = 0;
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < kWaves; ++q) {
         run += q < wv ? wtot[q] : 0u;
         total += wtot[q];
     }

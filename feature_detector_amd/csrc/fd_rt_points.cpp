@@ -19,8 +19,12 @@ int choose_tile_h(int64_t batch, int tiles_x, int out_rows, int period, int max_
     if (h < period && period == 6) {
         // small launches: the tile's serial row chain is the latency; 3 rows (9 steps of the 6-row
         // ring, the loop stops early) measured best at 640x480 batch 1 (tile_h 6/4/3/2/1: K1 11.4 /
-        // 10.3 / 10.1 / 10.2 / 13.2 us, and k_select grows with the number of segments below 3)
-        h = 3;
+        // 10.3 / 10.1 / 10.2 / 13.2 us, and k_select grows with the number of segments below 3).
+        // Harris / Shi-Tomasi launches of this height in sorted-segment mode with thr >= 0 run
+        // k_corner_short (fd_points.hip): the same workgroup footprint and segments, so nothing here or in
+        // fd_ctx_reserve depends on it; 8 waves of two columns per lane per workgroup, no row ring
+        // (headline step 25.39 -> 24.06 us, profiles/r08_k1_short_tile_ab.txt).
+        h = 3;  // (fdk's kShortTileH: launch_corner tests tile_h against it)
     } else {
         h = std::max<int64_t>(h, period);
         h = ((h + period - 1) / period) * period;
