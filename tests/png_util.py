@@ -16,27 +16,58 @@ def _paeth(a, b, c):
     return np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
 
 
-def encode_png(img, filters=(0, 1, 2, 3, 4)):
-    """img: uint8 [rows, cols] (gray) or [rows, cols, C] with C in 2/3/4; row r uses filters[r % len]."""
+def encode_png(img, filters=(0, 1, 2, 3, 4), *, level=None, idat_split=(), before_idat=(), between_idat=(),
+               after_iend=b"", bit_depth=8, ctype=None, interlace=0, rows=None, cols=None, ihdr=True,
+               raw_edit=None, z_edit=None):
+    """img: uint8 [rows, cols] (gray) or [rows, cols, C] with C in 2/3/4; row r uses filters[r % len]
+    (a filter byte outside 0..4 is written as it is, with nothing predicted).
+
+    The defaults write signature, IHDR, one IDAT at zlib's default level, IEND. Options, for the streams
+    other encoders write and for the ones the decoder must refuse:
+      level         zlib level 0..9 (0: stored blocks)
+      idat_split    byte positions at which the compressed stream is cut into several IDAT chunks; a
+                    repeated position (or 0, or the stream's length) gives a zero-length IDAT
+      before_idat   (type, body) chunks between IHDR and the first IDAT
+      between_idat  (type, body) chunks after every IDAT but the last
+      after_iend    raw bytes appended after IEND
+      bit_depth, ctype, interlace, rows, cols   what IHDR says, whatever the data is
+      ihdr          False: no IHDR chunk
+      raw_edit      bytes -> bytes on the filtered scanlines before deflate
+      z_edit        bytes -> bytes on the compressed stream before it is cut into IDATs"""
     img = np.ascontiguousarray(img, np.uint8)
     if img.ndim == 2:
         img = img[:, :, None]
-    rows, cols, ch = img.shape
-    ctype = {1: 0, 2: 4, 3: 2, 4: 6}[ch]
-    stride = cols * ch
+    nrows, ncols, ch = img.shape
+    stride = ncols * ch
     raw = bytearray()
     prev = np.zeros(stride, np.int32)
-    for r in range(rows):
+    for r in range(nrows):
         cur = img[r].reshape(-1).astype(np.int32)
         ft = filters[r % len(filters)]
         a = np.concatenate([np.zeros(ch, np.int32), cur[:-ch]])
         c = np.concatenate([np.zeros(ch, np.int32), prev[:-ch]])
-        pred = {0: np.zeros_like(cur), 1: a, 2: prev, 3: (a + prev) >> 1, 4: _paeth(a, prev, c)}[ft]
+        pred = {1: a, 2: prev, 3: (a + prev) >> 1, 4: _paeth(a, prev, c)}.get(ft, np.zeros_like(cur))
         raw.append(ft)
         raw += ((cur - pred) & 0xFF).astype(np.uint8).tobytes()
         prev = cur
-    hdr = struct.pack(">IIBBBBB", cols, rows, 8, ctype, 0, 0, 0)
-    return b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", hdr) + _chunk(b"IDAT", zlib.compress(bytes(raw))) + _chunk(b"IEND", b"")
+    raw = bytes(raw)
+    if raw_edit is not None:
+        raw = bytes(raw_edit(raw))
+    z = zlib.compress(raw) if level is None else zlib.compress(raw, level)
+    if z_edit is not None:
+        z = bytes(z_edit(z))
+    hdr = struct.pack(">IIBBBBB", ncols if cols is None else cols, nrows if rows is None else rows, bit_depth,
+                      {1: 0, 2: 4, 3: 2, 4: 6}[ch] if ctype is None else ctype, 0, 0, interlace)
+    cuts = [0] + [int(x) for x in idat_split] + [len(z)]
+    assert cuts == sorted(cuts), "idat_split: ascending positions within the compressed stream"
+    parts = [z[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+    out = b"\x89PNG\r\n\x1a\n" + (_chunk(b"IHDR", hdr) if ihdr else b"")
+    out += b"".join(_chunk(t, body) for t, body in before_idat)
+    for k, part in enumerate(parts):
+        out += _chunk(b"IDAT", part)
+        if k + 1 < len(parts):
+            out += b"".join(_chunk(t, body) for t, body in between_idat)
+    return out + _chunk(b"IEND", b"") + bytes(after_iend)
 
 
 def decode_png(data):
@@ -50,6 +81,8 @@ def decode_png(data):
             ch = {0: 1, 4: 2, 2: 3, 6: 4}[body[9]]
         elif t == b"IDAT":
             idat += body
+        elif t == b"IEND":  # the stream ends here, whatever follows in the file
+            break
         pos += 12 + n
     raw = np.frombuffer(zlib.decompress(idat), np.uint8)
     stride = cols * ch
