@@ -75,6 +75,9 @@ struct fd_ctx {
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
     // per-frame best-hypothesis words
     fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best;
+    // fd_frames_equalize: the tiles' LUTs ([batch][tiles_y][tiles_x][256] bytes), then the columns' and rows'
+    // interpolation entries ([cols + rows] words)
+    fdrt::DevBuf e_ws;
     fdrt::DevBuf n_heat, n_map, n_xy, n_counts, n_out;
     fdrt::DevBuf dbg;
     // per-frame status of the last selection call: [batch] FD_FRAME_* flags, then [batch] candidate

@@ -451,7 +451,19 @@ struct WarpArgs {
     int tiles;                   // launch_warp's: workgroup columns per destination row
 };
 
+// Contrast-limited adaptive histogram equalization (fd_equalize.hip; fd_frames_equalize of include/fd_hip.h).
+struct EqualizeArgs {
+    const uint8_t *frames;       // [batch][rows][cols], any byte alignment
+    uint8_t *out;                // [batch][rows][cols], any byte alignment; may be frames
+    uint8_t *luts;               // workspace: [batch][tiles_y][tiles_x][256], dword aligned
+    uint32_t *tab;               // workspace: [cols] then [rows] interpolation entries, cell | fraction << 8
+    int batch, rows, cols, tiles_x, tiles_y, clip_milli;
+    int lanes_log2, chunks, row_split;  // launch_equalize's: lanes per tile row, workgroup columns per row, workgroups per row cell
+};
+
 // Launchers (stream-ordered, no allocation, no synchronisation: graph-capturable).
+// the three kernels of fd_frames_equalize, in order
+hipError_t launch_equalize(EqualizeArgs a, hipStream_t s);
 hipError_t launch_warp(WarpArgs a, hipStream_t s);
 // the three kernels of fd_ransac, in order
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);

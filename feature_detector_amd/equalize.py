@@ -1,0 +1,83 @@
+"""Contrast-limited adaptive histogram equalization over the C ABI (fd_frames_equalize).
+
+An MI355X extension (the reference has no such stage): the photometric pre-processing a visual-odometry front
+end runs ahead of detect_points (absolute response thresholds, FAST's intensity threshold) and track_lk
+(brightness constancy), so ingest -> equalize -> detect ... stays on the GPU. The arithmetic, integers only, is
+in include/fd_hip.h.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import fd_equalize_opts
+from ._slots import ptr
+from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+
+MAX_TILES = 32
+MAX_TILE_AREA = 1 << 24
+
+
+def _options(tiles, clip_limit, rows, cols):
+    """(tiles_x, tiles_y, clip_milli), checked as fd_frames_equalize checks them."""
+    if isinstance(tiles, (int, np.integer)):
+        tiles = (tiles, tiles)
+    if len(tiles) != 2:
+        raise ValueError("tiles must be (tiles_x, tiles_y) or one int")
+    tiles_x, tiles_y = int(tiles[0]), int(tiles[1])
+    if not 1 <= tiles_x <= min(MAX_TILES, cols) or not 1 <= tiles_y <= min(MAX_TILES, rows):
+        raise ValueError(f"tiles must be in [1, min({MAX_TILES}, cols)] x [1, min({MAX_TILES}, rows)]")
+    clip = 0.0 if clip_limit is None else float(clip_limit)
+    if not 0.0 <= clip <= 2.0e6:  # (false for NaN)
+        raise ValueError("clip_limit must be in [0, 2e6]")
+    if -(-cols // tiles_x) * -(-rows // tiles_y) > MAX_TILE_AREA:
+        raise ValueError("a tile must not have more than 2^24 pixels: use more tiles")
+    return tiles_x, tiles_y, int(round(clip * 1000))
+
+
+def equalize_frames(frames, tiles=(8, 8), clip_limit=3.0, out=None, ctx: Context | None = None):
+    """fd_frames_equalize: CLAHE of every frame (OpenCV's createCLAHE(clip_limit, tiles) semantics in exact
+    integer arithmetic; the tiles are the frame cut without padding).
+
+    frames: uint8 [B, rows, cols] or [rows, cols], numpy or a torch device tensor. tiles: (tiles_x, tiles_y) or
+    one int for both, each 1..32 and no larger than its dimension. clip_limit: a float, 0 or None: no clipping
+    (tiles 1 and no clipping is plain global histogram equalization).
+
+    Returns the equalized frames in the frames' shape, on the frames' side: a torch tensor for device frames
+    (asynchronous on torch's current stream; kernels only and graph-capturable once a call of the shape has
+    run), numpy otherwise. out: a preallocated contiguous uint8 array or tensor of the frames' shape on the
+    frames' side; it may be frames itself (in place).
+    """
+    fptr, f_dev, b, rows, cols, keep = _frames(frames)
+    if rows < 1 or cols < 1 or b < 1:
+        raise ValueError("frames must not be empty")
+    tiles_x, tiles_y, clip_milli = _options(tiles, clip_limit, rows, cols)
+    on_dev = bool(f_dev)
+    shape = tuple(keep.shape)
+    if out is None:
+        if on_dev:
+            import torch
+
+            out = torch.empty(shape, dtype=torch.uint8, device=keep.device)
+        else:
+            out = np.empty(shape, np.uint8)
+    else:
+        if _is_torch_device_tensor(out) != on_dev:
+            raise ValueError("out must be on the side of the frames")
+        if on_dev:
+            import torch
+
+            ok = out.dtype == torch.uint8 and out.is_contiguous()
+        else:
+            ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
+        if not ok or tuple(out.shape) != shape:
+            raise ValueError(f"out must be a contiguous uint8 array of shape {shape}")
+    ctx = _resolve_ctx(ctx, keep, out)
+    opts = fd_equalize_opts(tiles_x, tiles_y, clip_milli)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_frames_equalize(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(out),
+                                        1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return out

@@ -768,6 +768,60 @@ int fd_frames_warp(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int
                    const fd_warp_opts *opts, const double *params, int params_on_device,
                    int out_rows, int out_cols, uint8_t *out, uint8_t *out_mask /* NULL to skip */, int out_on_device);
 
+/* ---- Contrast-limited adaptive histogram equalization (MI355X extension) ----------------------------- */
+typedef struct fd_equalize_opts {
+    int32_t tiles_x;    /* 1..32, <= cols */
+    int32_t tiles_y;    /* 1..32, <= rows */
+    int32_t clip_milli; /* clip limit x 1000 (OpenCV's clipLimit 3.0 -> 3000); 0: no clipping */
+} fd_equalize_opts;
+
+/*
+ * fd_frames_equalize -- CLAHE of every frame of frames [batch][rows][cols] uint8 into out of the same shape:
+ * the photometric pre-processing stage ahead of fd_points_detect (absolute response thresholds, FAST's fixed
+ * intensity threshold) and fd_flow_lk (brightness constancy). The reference has no such stage: the contract is
+ * this text. Every quantity is an integer; divisions are floor divisions of non-negative values. Frames are
+ * independent.
+ *
+ * Tiles. Column edges ex[i] = (i*cols)/tiles_x, i = 0..tiles_x; row edges ey[j] likewise with rows and tiles_y.
+ * Tile (j, i) covers rows ey[j] .. ey[j+1]-1 and columns ex[i] .. ex[i+1]-1; A is its area. Tiles may differ in
+ * size by one row or column; there is no padding and no reflection; tiles <= dimension gives A >= 1.
+ *
+ * LUT of a tile. h[v] = the number of its pixels equal to v. If clip_milli > 0:
+ *   lim = max(1, (clip_milli*A)/256000)   (a 64-bit product);   E = sum of max(h[v]-lim, 0)
+ *   h[v] = min(h[v], lim), then h[v] += E/256
+ *   r = E % 256; if r > 0: step = 256/r, and h[v] += 1 for every v with v % step == 0 and v/step < r
+ * (OpenCV's single redistribution pass: bins may end above lim, as intended). The sum of h is A always.
+ *   cdf[v] = h[0] + ... + h[v];   lut[v] = (cdf[v]*255 + A/2) / A
+ * so lut is non-decreasing and lut[255] = 255. A call in which any tile has A > 2^24 is refused, which keeps
+ * cdf*255 + A/2 below 2^32.
+ *
+ * Interpolation, separable, in fd_flow_lk's 1/1024 fixed point. Column x, from the edges only: c2[i] =
+ * ex[i]+ex[i+1] (twice tile i's centre), p = 2x+1.
+ *   p < c2[0]:            i0 = i1 = 0, fx = 0
+ *   p >= c2[tiles_x-1]:   i0 = i1 = tiles_x-1, fx = 0
+ *   otherwise:            i0 = the largest i with c2[i] <= p, i1 = i0+1,
+ *                         fx = ((p - c2[i0])*1024) / (c2[i1] - c2[i0]), so 0 <= fx < 1024
+ * Rows likewise: j0, j1, fy. For a pixel with value v:
+ *   top = lut[j0][i0][v]*(1024-fx) + lut[j0][i1][v]*fx
+ *   bot = lut[j1][i0][v]*(1024-fx) + lut[j1][i1][v]*fx
+ *   out = (top*(1024-fy) + bot*fy + 2^19) >> 20        (at most 255*2^20 + 2^19 < 2^32)
+ * Consequences: tiles_x = tiles_y = 1 with clip_milli = 0 is plain global histogram equalization; clip_milli = 0
+ * with more tiles is unclipped AHE; the output depends only on the frame and the three options, never on the
+ * launch shape.
+ *
+ * No alignment beyond a byte is asked of frames or out, and cols may be odd. out may be exactly frames (in
+ * place, host or device); any other overlap is the caller's error and is not detected. frames and out are
+ * device pointers when their *_on_device flag is set. Host frames are staged through the context as
+ * fd_pyr_build stages them, a host out through a context buffer; a call with a host array is complete on
+ * return. The tiles' LUTs (batch*tiles_y*tiles_x*256 bytes) and the axes' interpolation entries live in the
+ * context's workspace: with both pointers on the device, and once a call of no smaller footprint has run, the
+ * call is kernels on the context's stream only: asynchronous and graph-capturable.
+ * FD_ERR_INVALID: ctx, opts, frames or out NULL; batch, rows or cols < 1; tiles_x outside 1..min(32, cols);
+ * tiles_y outside 1..min(32, rows); clip_milli < 0; a tile area above 2^24.
+ */
+int fd_frames_equalize(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                       const fd_equalize_opts *opts, uint8_t *out, int out_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

@@ -23,6 +23,11 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      perspective (homography), then a barrel-distortion camera model, at 1920x1080 batch 64 (10
                      calls each) and at 640x480 batch 1 (200 calls each), destination shape = source shape
                      (--warp-size hd / vga: one of the two, so that a trace's statistics are one shape's)
+  --shape equalize   fd_frames_equalize on device tensors, tiles (8, 8), clip limit 3.0, out preallocated: k_eq_tab,
+                     k_eq_lut and k_eq_apply per call, on natural-statistics frames (blurred noise, darkened) at
+                     --eq-size vga1 (640x480 batch 1, 200 calls), vga64 (640x480 batch 64, 20 calls) or hd
+                     (1920x1080 batch 64, 10 calls); all: the three in turn (a trace per shape keeps its statistics
+                     one shape's)
   --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
                      128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
                      baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
@@ -45,7 +50,7 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "equalize", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
@@ -53,6 +58,7 @@ p.add_argument("--cross-check", action="store_true", help="fastmatch: match with
 p.add_argument("--fb", action="store_true", help="fastflow: track with the forward-backward check")
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
 p.add_argument("--warp-size", default="both", choices=["both", "hd", "vga"], help="warp: one of the two shapes (a trace per shape)")
+p.add_argument("--eq-size", default="all", choices=["all", "vga1", "vga64", "hd"], help="equalize: one of the three shapes (a trace per shape)")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
 g = torch.Generator(device="cuda")
@@ -229,6 +235,17 @@ elif a.shape == "warp":
             for _ in range(calls):
                 fd.warp_frames(frames, dp, model=model, return_mask=True, out=out)
             print(f"{model} {cols}x{rows}x{b}: pixels with a source {float(out[1].float().mean()):.4f}")
+elif a.shape == "equalize":
+    kind = "tiles 8x8, clip 3.0"
+    sizes = {"vga1": (1, 480, 640, a.calls or 200), "vga64": (64, 480, 640, a.calls or 20), "hd": (64, 1080, 1920, a.calls or 10)}
+    for b, rows, cols, calls in (sizes.values() if a.eq_size == "all" else (sizes[a.eq_size],)):
+        # blurred noise, darkened: neighbouring pixels are close (a camera frame's statistics; uniform noise has none)
+        frames = (torch.nn.functional.avg_pool2d(noise(b, rows + 4, cols + 4).float()[:, None], 5, 1)[:, 0] / 3.0).clamp(0, 255).to(torch.uint8).contiguous()
+        out = torch.empty_like(frames)
+        for _ in range(calls):
+            fd.equalize_frames(frames, (8, 8), 3.0, out=out)
+        print(f"equalize {cols}x{rows}x{b}: mean in {float(frames.float().mean()):.1f}, mean out {float(out.float().mean()):.1f}, "
+              f"levels in {int(frames.unique().numel())}, levels out {int(out.unique().numel())}")
 elif a.shape == "nnmatch":
     kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
     B, S = 64, 240
