@@ -461,7 +461,20 @@ struct EqualizeArgs {
     int lanes_log2, chunks, row_split;  // launch_equalize's: lanes per tile row, workgroup columns per row, workgroups per row cell
 };
 
+// Line band descriptor (fd_line_desc.hip; fd_lines_describe of include/fd_hip.h).
+struct LineDescArgs {
+    const uint8_t *frames;   // [batch][rows][cols]
+    const float *lines;      // [batch][stride][line_floats], floats 0..3 = (start.x, start.y, end.x, end.y)
+    const int32_t *counts;   // [batch] or null (= stride); bits 25..31 ignored
+    float *out_desc;         // [batch][stride][8 * bands]
+    float *out_xy;           // [batch][stride][2] midpoints, or null
+    uint8_t *out_valid;      // [batch][stride], or null
+    int batch, rows, cols, stride, line_floats, bands, band_width;
+};
+
 // Launchers (stream-ordered, no allocation, no synchronisation: graph-capturable).
+// k_line_desc, one workgroup per line slot
+hipError_t launch_line_desc(const LineDescArgs &a, hipStream_t s);
 // the three kernels of fd_frames_equalize, in order
 hipError_t launch_equalize(EqualizeArgs a, hipStream_t s);
 hipError_t launch_warp(WarpArgs a, hipStream_t s);

@@ -822,6 +822,78 @@ typedef struct fd_equalize_opts {
 int fd_frames_equalize(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
                        const fd_equalize_opts *opts, uint8_t *out, int out_on_device);
 
+/* ---- Line band descriptor (MI355X extension) ---------------------------------------------------------- */
+typedef struct fd_line_desc_opts {
+    int32_t bands;      /* 1..32 (default 9): bands across the line; the descriptor has dim = 8*bands floats */
+    int32_t band_width; /* 1..16 (default 7): rows of one band */
+} fd_line_desc_opts;
+
+/*
+ * fd_lines_describe -- an LBD-style band descriptor (after Zhang & Koch's line band descriptor) of every
+ * segment of lines [batch][stride][line_floats] over frames [batch][rows][cols] uint8, so that the segments of
+ * fd_lsd_lines can be matched by fd_nn_match / fd_nn_match_guided as they are (dim = 8*bands is a multiple of
+ * 4, at most 256). The reference has no such stage: the contract is this text. Per-pixel work is in integers;
+ * everything else is in double, IEEE round-to-nearest, no contraction, one rounding per written operation, in
+ * the order written. Lines and frames are independent.
+ *
+ * Floats 0..3 of a line are (sx, sy, ex, ey), each converted to double; line_floats is 4, or 12 so that an
+ * array of fd_lsd_rect passes as it is. w = band_width, H = bands*w.
+ *
+ * Per line.
+ *   dx = ex - sx;  dy = ey - sy;  L = sqrt(dx*dx + dy*dy)
+ *   c  = ((sx + ex)*0.5, (sy + ey)*0.5)
+ *   The line is invalid if one of the four floats is not finite or if L >= 1 is false. Otherwise
+ *   dL = (dx/L, dy/L);  n = (-dL.y, dL.x)
+ *   dLq = (rint(dL.x*16384), rint(dL.y*16384)) as integers (round half to even);  nq = (-dLq.y, dLq.x)
+ *   N = min(floor(L), 4096)   (>= 1) samples along the line, H rows across it.
+ *
+ * Sample (i, j), 0 <= i < N, 0 <= j < H.
+ *   a = i - (N - 1)*0.5;  b = j - (H - 1)*0.5                    (exact)
+ *   x = c.x + (a*dL.x + b*n.x);  y = c.y + (a*dL.y + b*n.y)
+ *   px = floor(x + 0.5);  py = floor(y + 0.5)
+ *   A sample with 1 <= px <= cols - 2 and 1 <= py <= rows - 2 false contributes nothing. Otherwise, with I the frame,
+ *   gx = I(py, px+1) - I(py, px-1);  gy = I(py+1, px) - I(py-1, px)
+ *   gp = gx*nq.x + gy*nq.y;  gl = gx*dLq.x + gy*dLq.y             (integers, |.| < 2^23)
+ * Row sums, exact integers (they pass 2^32): v[j][0] = sum_i max(gp, 0), v[j][1] = sum_i max(-gp, 0), v[j][2]
+ * and v[j][3] the same of gl. S = sum_j (v[j][0] - v[j][1]), the sum of every gp.
+ *
+ * Orientation. If S < 0 the row sums are replaced by those of the reversed segment, r[j][m] = v[H-1-j][m^1]
+ * (rows reversed, v0 <-> v1, v2 <-> v3); otherwise r = v. The sample grid is symmetric about c and (-a)*(-dL.x)
+ * has the bits of a*dL.x, so r is what the call computes for (ex, ey, sx, sy) whenever S != 0: the descriptor
+ * does not depend on the order of the endpoints, bit for bit. (Against the unreversed descriptor, the band
+ * order is reversed and the components of each group of four are swapped in pairs.)
+ *
+ * Bands. Row j has the global weight G[j] = H - |2j - (H - 1)|. Band k, 0 <= k < bands, is formed from the rows
+ * of bands k-1, k, k+1 that exist: local index t = 0 .. 3w-1 stands for row j = (k-1)*w + t, skipped unless
+ * 0 <= j < H; its local weight is l[t] = 3w - |2t - (3w - 1)|; n_rows = the rows not skipped. For component m
+ * of 0..3, over t ascending:
+ *   u[t] = (double)(G[j]*l[t]*r[j][m])                             (an exact integer below 2^53)
+ *   mean = (sum_t u[t]) / n_rows;   std = sqrt((sum_t (u[t] - mean)*(u[t] - mean)) / n_rows)
+ * (sums start at 0.0). The raw descriptor is D[8k + m] = mean, D[8k + 4 + m] = std.
+ *
+ * Normalisation. For the 4*bands means (indices 8k + m) and then for the 4*bands stds (8k + 4 + m), each group in
+ * ascending index order: s = sum of D[i]*D[i]; q = sqrt(s); if q > 0, D[i] = min(D[i] / q, 0.4); a group with
+ * q == 0 stays zero. Then over all 8*bands indices ascending: s = sum of D[i]*D[i]; q = sqrt(s); out_desc[i] =
+ * (float)(D[i] / q), one rounding. If both groups have q == 0 (a flat or empty support region) the line is invalid.
+ *
+ * Outputs, for slots < counts[b] only (all `stride` with counts NULL; bits 25..31 of a count are ignored and the
+ * count is clamped to stride); other slots are not written. out_desc [batch][stride][8*bands]: the descriptor,
+ * all zero for an invalid line. out_xy [batch][stride][2], NULL to skip: ((float)c.x, (float)c.y), the midpoint
+ * fd_nn_match_guided takes as q_xy / t_xy, or (0, 0) where an endpoint is not finite. out_valid [batch][stride],
+ * NULL to skip: 1, or 0 for an invalid line (it passes as fd_nn_match's q_valid / t_valid).
+ *
+ * frames are device memory when frames_on_device is set; lines, counts and the outputs are device pointers
+ * when io_on_device is set, else host arrays staged through the context, and a call with any host array is
+ * complete on return. With everything on the device the call is one kernel on the context's stream, allocates
+ * nothing, and is graph-capturable. stride == 0: FD_OK, no work.
+ * FD_ERR_INVALID: ctx, opts, frames, lines or out_desc NULL; bands outside 1..32; band_width outside 1..16;
+ * line_floats not 4 or 12; batch < 1; stride < 0; rows or cols < 3.
+ */
+int fd_lines_describe(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                      const fd_line_desc_opts *opts, const float *lines, int32_t line_floats, const int32_t *counts /* NULL: stride each */,
+                      int32_t stride, float *out_desc, float *out_xy /* NULL to skip */, uint8_t *out_valid /* NULL to skip */,
+                      int io_on_device);
+
 /* ---- SuperPoint post-processing (the network runs in PyTorch-ROCm) -------------------------------- */
 /* NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31) fields of the heatmap path. */
 typedef struct fd_nn_opts {

@@ -28,6 +28,10 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      --eq-size vga1 (640x480 batch 1, 200 calls), vga64 (640x480 batch 64, 20 calls) or hd
                      (1920x1080 batch 64, 10 calls); all: the three in turn (a trace per shape keeps its statistics
                      one shape's)
+  --shape linedesc   fd_lines_describe on device tensors, default options (9 bands of 7 rows, dim 72), 512 seeded
+                     segments per frame with lengths 20..300 px at any angle on 640x480 frames of blurred noise:
+                     batch 64 (20 calls), then batch 1 (200 calls); one k_line_desc per call, also timed here with
+                     events
   --shape nnmatch    fd_nn_match on 64 frames x 240 x 240 L2-normalised float descriptors (--dim 256 SuperPoint /
                      128 DISK; --cross-check: two k_nn_match launches per call), 20 calls; then a torch
                      baseline on the same tensors (q @ t.T, norms, topk(2)), 20 calls; both also timed here with
@@ -50,7 +54,7 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "equalize", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "equalize", "linedesc", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
@@ -246,6 +250,27 @@ elif a.shape == "equalize":
             fd.equalize_frames(frames, (8, 8), 3.0, out=out)
         print(f"equalize {cols}x{rows}x{b}: mean in {float(frames.float().mean()):.1f}, mean out {float(out.float().mean()):.1f}, "
               f"levels in {int(frames.unique().numel())}, levels out {int(out.unique().numel())}")
+elif a.shape == "linedesc":
+    kind = "9 bands x 7 rows"
+    rows, cols, S = 480, 640, 512
+    for b, calls in ((64, a.calls or 20), (1, a.calls or 200)):
+        frames = torch.nn.functional.avg_pool2d(noise(b, rows + 4, cols + 4).float()[:, None], 5, 1)[:, 0].clamp(0, 255).to(torch.uint8).contiguous()
+        u = torch.rand((b, S, 4), generator=g, device="cuda")
+        centre = u[..., :2] * torch.tensor([cols - 1.0, rows - 1.0], device="cuda")
+        half = 0.5 * (20.0 + 280.0 * u[..., 2:3]) * torch.stack([torch.cos(6.2831853 * u[..., 3]), torch.sin(6.2831853 * u[..., 3])], -1)
+        lines = torch.cat([centre - half, centre + half], -1).contiguous()
+        out = (torch.empty((b, S, 72), device="cuda"), torch.empty((b, S, 2), device="cuda"), torch.empty((b, S), dtype=torch.uint8, device="cuda"))
+        for _ in range(3):
+            fd.describe_lines(frames, lines, out=out)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+        ev[0].record()
+        for e in ev[1:]:
+            fd.describe_lines(frames, lines, out=out)
+            e.record()
+        torch.cuda.synchronize()
+        us = sorted(1e3 * x.elapsed_time(y) for x, y in zip(ev, ev[1:]))
+        print(f"fd.describe_lines {cols}x{rows}x{b}, {S} lines per frame, {kind}: median {us[len(us) // 2]:.1f} us per call "
+              f"(min {us[0]:.1f}, max {us[-1]:.1f}), {len(us)} calls; valid {float(out[2].float().mean()):.3f}")
 elif a.shape == "nnmatch":
     kind = f"dim {a.dim}" + (" cross-check" if a.cross_check else "")
     B, S = 64, 240
