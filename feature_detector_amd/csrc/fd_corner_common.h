@@ -1,6 +1,8 @@
-// Shared device pieces of the corner kernels (fd_points.hip: k_corner, k_fast; fd_corner_lp.hip:
-// k_corner_lp): workgroup -> tile decoding, frame loads and the exact response arithmetic (the candidate
-// lists they write: fd_emit.h). Each including translation unit gets its own copy (anonymous namespace).
+// Shared device pieces of the corner kernels (fd_points.hip: k_corner, k_corner_short, k_fast;
+// fd_corner_lp.hip: k_corner_lp): workgroup -> tile decoding, frame loads, the prior mask's bits, the exact
+// response arithmetic, and the integer kernels' row step -- gradient row sums, stored responses, NMS --
+// written once for k_corner's ring walk and k_corner_short's straight-line walk (the candidate lists they
+// write: fd_emit.h). Each including translation unit gets its own copy (anonymous namespace).
 #pragma once
 
 #include "fd_emit.h"
@@ -42,6 +44,20 @@ __device__ __forceinline__ uint32_t load_px4(__amdgpu_buffer_rsrc_t r, int32_t o
     if constexpr (ALIGNED) return buf_load_u32(r, off);
     return buf_load_u8(r, off) | (buf_load_u8(r, off + 1) << 8) | (buf_load_u8(r, off + 2) << 16) |
            (buf_load_u8(r, off + 3) << 24);
+}
+// Two pixels [off, off+2) as the low bytes of a dword (aligned: off is even, cols % 4 == 0 and c0 even).
+template <bool ALIGNED>
+__device__ __forceinline__ uint32_t load_px2(__amdgpu_buffer_rsrc_t r, int32_t off) {
+    if constexpr (ALIGNED) return buf_load_u16(r, off);
+    return buf_load_u8(r, off) | (buf_load_u8(r, off + 1) << 8);
+}
+
+// Prior-mask bits of the NC columns from c0 (a multiple of NC: they share a word) of one row.
+template <int NC>
+__device__ __forceinline__ uint32_t mask_bits(const PointsArgs &a, int f, int row, int c0) {
+    if (c0 < 0 || c0 >= a.cols) return 0u;
+    const uint32_t w = a.mask[(static_cast<int64_t>(f) * a.rows + row) * a.mask_wpr + (c0 >> 5)];
+    return (w >> (c0 & 31)) & ((1u << NC) - 1u);
 }
 
 // Two pixels' float math at a time: <2 x float> arithmetic compiles to v_pk_mul_f32 / v_pk_add_f32 /
@@ -98,6 +114,132 @@ __device__ __forceinline__ f2 corner_response2(uint32_t sxx0, uint32_t sxx1, uin
         res.y = (gate.y > thr && r.y > thr) ? r.y : 0.0f;
     }
     return res;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The integer kernels' row step (k_corner, k_corner_short), for a lane of NC columns c0 .. c0+NC-1 in a
+// wave whose lanes 0 and 63 only supply halo (tile width 62 NC). Each piece takes its rows as arguments
+// and is indifferent to how the caller keeps them (a 3-slot ring, or one slot per row).
+// ---------------------------------------------------------------------------------------------------
+// Which of the lane's columns count, fixed for the tile.
+template <int NC>
+struct TileCols {
+    int c0;               // the lane's first column: tx * 62 NC + NC (lane - 1)
+    bool interior;        // every lane's columns inside [2, cols-3]: only the frame's first/last rows need masking
+    bool cval[NC];        // column inside [2, cols-3]
+    bool colv[NC];        // ... and owned by an interior lane (emitted)
+    uint64_t colv_b[NC];  // ballot of colv
+};
+template <int NC>
+__device__ __forceinline__ TileCols<NC> tile_columns(int tx, int cols) {
+    constexpr int TW = 62 * NC;
+    const int lane = lane_id();
+    const int c0 = tx * TW + NC * (lane - 1);
+    TileCols<NC> tc;
+    tc.c0 = c0;
+    tc.interior = tx * TW - NC >= 2 && tx * TW + NC * 62 + NC - 1 <= cols - 3;
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        tc.cval[m] = c0 + m >= 2 && c0 + m <= cols - 3;
+        tc.colv[m] = tc.cval[m] && lane >= 1 && lane <= 62;
+        tc.colv_b[m] = ballot(tc.colv[m]);
+    }
+    return tc;
+}
+
+// Biased horizontal 3-tap sums of one row's gradient products (3 products, 3*beta).
+template <int NC>
+struct HSums {
+    uint32_t xx[NC], yy[NC], xy[NC];
+};
+
+// Gradients of a centre row at the lane's NC columns (feature_point_harris_detector.cpp:35-62) and their
+// horizontal sums. Pc / P_below / P_above: the lane's pixels of the centre row and of the rows below and
+// above it; Lc / Rc: the neighbour lanes' pixels of the centre row (its two halo bytes come from them).
+// Products carry the float-conversion bias (v_mad_i32_i24 with a constant addend: free).
+template <int NC>
+__device__ __forceinline__ void grad_row_sums(uint32_t Lc, uint32_t Pc, uint32_t Rc, uint32_t P_below, uint32_t P_above,
+                                              HSums<NC> &h) {
+    uint32_t qxx[NC + 2], qyy[NC + 2], qxy[NC + 2];  // products at columns c0-1 .. c0+NC (k = m + 1)
+    uint32_t bsq = kBiasSq, bxy = kBiasXy;
+    asm volatile("" : "+s"(bsq), "+s"(bxy));  // opaque: keeps v_mad (else mul + or)
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        const int ix = win_byte<NC>(Lc, Pc, Rc, m + 1) - win_byte<NC>(Lc, Pc, Rc, m - 1);
+        const int iy = win_byte<NC>(0, P_below, 0, m) - win_byte<NC>(0, P_above, 0, m);
+        qxx[m + 1] = static_cast<uint32_t>(ix * ix) + bsq;
+        qyy[m + 1] = static_cast<uint32_t>(iy * iy) + bsq;
+        qxy[m + 1] = static_cast<uint32_t>(ix * iy) + bxy;
+    }
+    // Halo products from the neighbour lanes' edge columns (exact for lanes 0 / 63's inner columns,
+    // whose neighbours are lanes 1 / 62).
+    qxx[0] = from_left(qxx[NC]);
+    qyy[0] = from_left(qyy[NC]);
+    qxy[0] = from_left(qxy[NC]);
+    qxx[NC + 1] = from_right(qxx[1]);
+    qyy[NC + 1] = from_right(qyy[1]);
+    qxy[NC + 1] = from_right(qxy[1]);
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        h.xx[m] = add3u(qxx[m], qxx[m + 1], qxx[m + 2]);
+        h.yy[m] = add3u(qyy[m], qyy[m + 1], qyy[m + 2]);
+        h.xy[m] = add3u(qxy[m], qxy[m + 1], qxy[m + 2]);
+    }
+}
+
+// Stored responses of row rr from the horizontal sums of rows rr-1, rr, rr+1 (in any order): the vertical
+// 3-row sums are exact integers (< 2^23).
+template <int KIND, bool G1, bool MASKED, int NC>
+__device__ __forceinline__ void response_row(const PointsArgs &a, int f, int rr, const TileCols<NC> &tc,
+                                             const HSums<NC> &h0, const HSums<NC> &h1, const HSums<NC> &h2,
+                                             float (&rsp)[NC]) {
+    const bool rowv = rr >= 2 && rr <= a.rows - 3;
+    uint32_t sxx[NC], syy[NC], sxy[NC];
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        sxx[m] = add3u(h0.xx[m], h1.xx[m], h2.xx[m]);
+        syy[m] = add3u(h0.yy[m], h1.yy[m], h2.yy[m]);
+        sxy[m] = add3u(h0.xy[m], h1.xy[m], h2.xy[m]);
+    }
+    float r[NC];
+#pragma unroll
+    for (int m = 0; m < NC; m += 2) {
+        const f2 rp = corner_response2<KIND, G1>(sxx[m], sxx[m + 1], syy[m], syy[m + 1], sxy[m], sxy[m + 1], a.thr);
+        r[m] = rp.x;
+        r[m + 1] = rp.y;
+    }
+    if (!MASKED && rowv && tc.interior) {  // wave-uniform: no per-pixel masking needed
+#pragma unroll
+        for (int m = 0; m < NC; ++m) rsp[m] = r[m];
+    } else {
+        uint32_t mb = (1u << NC) - 1u;
+        if constexpr (MASKED) mb = rowv ? mask_bits<NC>(a, f, rr, tc.c0) : 0u;
+        // The halo lanes' inner columns (lane 0's last, lane 63's first) are exact and serve as the NMS
+        // neighbours of the tile's edge columns.
+#pragma unroll
+        for (int m = 0; m < NC; ++m) rsp[m] = (rowv && tc.cval[m] && ((mb >> m) & 1u)) ? r[m] : 0.0f;
+    }
+}
+
+// NMS of one row (feature_point_harris_detector.cpp:120-137): strict, 4-neighbour. x: the row's stored
+// responses, up / dn: those of its two vertical neighbours (in either order).
+// x > thr and x > each neighbour  <=>  x > max(thr, neighbours)  (no NaNs; +-0 compare equal): two v_max3.
+// b[m] is the wave ballot of fl[m], v[m] the candidate's response (emit_row's arguments).
+template <int NC>
+__device__ __forceinline__ void nms_row(const float (&x)[NC], const float (&up)[NC], const float (&dn)[NC], float thr,
+                                        const TileCols<NC> &tc, uint64_t (&b)[NC], bool (&fl)[NC], float (&v)[NC]) {
+    const float lft = from_left_f(x[NC - 1]);
+    const float rgt = from_right_f(x[0]);
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+        const float xl = m == 0 ? lft : x[m - 1];
+        const float xr = m == NC - 1 ? rgt : x[m + 1];
+        const float nb = max3f(max3f(xl, xr, thr), up[m], dn[m]);
+        const bool hit = x[m] > nb;
+        v[m] = x[m];
+        fl[m] = tc.colv[m] && hit;
+        b[m] = ballot(hit) & tc.colv_b[m];  // the compare's lane mask, no bool round trip
+    }
 }
 
 }  // namespace

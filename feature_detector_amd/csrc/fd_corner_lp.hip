@@ -124,19 +124,11 @@ struct alignas(16) LpLds<false> {
 template <int PX, bool ALIGNED>
 __device__ __forceinline__ void lp_load_row(uint32_t (&w)[LpGeom<PX>::NW], __amdgpu_buffer_rsrc_t r, int32_t off) {
     if constexpr (PX == 2) {
-        if constexpr (ALIGNED) w[0] = static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0));
-        else w[0] = buf_load_u8(r, off) | (buf_load_u8(r, off + 1) << 8);
+        w[0] = load_px2<ALIGNED>(r, off);
     } else {
 #pragma unroll
         for (int q = 0; q < LpGeom<PX>::NW; ++q) w[q] = load_px4<ALIGNED>(r, off + 4 * q);
     }
-}
-
-template <int PX>
-__device__ __forceinline__ uint32_t lp_mask_bits(const PointsArgs &a, int f, int row, int c0) {
-    if (c0 < 0 || c0 >= a.cols) return 0u;
-    const uint32_t w = a.mask[(static_cast<int64_t>(f) * a.rows + row) * a.mask_wpr + (c0 >> 5)];
-    return (w >> (c0 & 31)) & ((1u << PX) - 1u);  // c0 is a multiple of PX: the PX bits share a word
 }
 
 // Entry (j, lane) of the wave's slots as (response, raster index). Shi-Tomasi slots hold 2r.
@@ -365,7 +357,7 @@ FD_LP_WAVES(PX, HIST, ALIGNED) __global__ __launch_bounds__(256) void k_corner_l
                     for (int m = 0; m < PX; ++m) rsp[su][m] = r[m];
                 } else {
                     uint32_t mb = (1u << PX) - 1u;
-                    if constexpr (MASKED) mb = rowv ? lp_mask_bits<PX>(a, f, rr, c0) : 0u;
+                    if constexpr (MASKED) mb = rowv ? mask_bits<PX>(a, f, rr, c0) : 0u;
 #pragma unroll
                     for (int m = 0; m < PX; ++m) rsp[su][m] = (rowv && cval[m] && ((mb >> m) & 1u)) ? r[m] : 0.0f;
                 }

@@ -37,10 +37,12 @@ __device__ __forceinline__ uint32_t buf_load_u8(__amdgpu_buffer_rsrc_t r, int32_
     return static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b8(r, byte_off, 0, 0));
 }
 
-// Byte J (compile-time after unrolling) of the 12-byte window [L | M | R] = columns c0-4 .. c0+7.
+// Byte j in [-1, NC] (compile-time after unrolling) of the window [left lane | own NC bytes | right lane],
+// each lane holding its NC pixels as the low bytes of a dword: columns c0-1 .. c0+NC.
+template <int NC>
 __device__ __forceinline__ int win_byte(uint32_t L, uint32_t M, uint32_t R, int j) {
-    const uint32_t w = j < 0 ? L : (j < 4 ? M : R);
-    const int sh = 8 * (j < 0 ? j + 4 : (j < 4 ? j : j - 4));
+    const uint32_t w = j < 0 ? L : (j < NC ? M : R);
+    const int sh = 8 * (j < 0 ? NC - 1 : (j < NC ? j : 0));
     return static_cast<int>((w >> sh) & 0xFFu);
 }
 

@@ -14,6 +14,8 @@
 // rounded f32 sqrt/div (hipcc default; never -ffast-math).
 #include "fd_corner_common.h"
 
+#include <type_traits>
+
 namespace fdk {
 
 namespace {
@@ -64,22 +66,25 @@ struct SinkSource {
     __device__ __forceinline__ void flush(const PointsArgs &a, int f) { sink_flush(sk, a, f); }
 };
 
-// Emit up to 4 candidates of this lane (columns c0..c0+3 of row `row`), preserving column order.
+// Emit up to NC candidates of this lane (columns c0..c0+NC-1 of row `row`), preserving column order.
 // The lane's slot is the count of candidates in lower lanes: one v_mbcnt pair per column ballot.
 // b[m] is the wave ballot of fl[m] (callers that hold it as a compare mask pass it directly).
-template <bool RASTER, int SEGCAP>
+template <bool RASTER, int SEGCAP, int NC>
 __device__ __forceinline__ void emit_row(Sink &sk, const PointsArgs &a, int f, int tx, int row, int c0,
-                                         const uint64_t (&b)[4], const bool (&fl)[4], const float (&v)[4]) {
-    const uint64_t b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-    const int tot = popc64(b0) + popc64(b1) + popc64(b2) + popc64(b3);  // scalar unit
+                                         const uint64_t (&b)[NC], const bool (&fl)[NC], const float (&v)[NC]) {
+    int tot = 0;
+#pragma unroll
+    for (int m = 0; m < NC; ++m) tot += popc64(b[m]);  // scalar unit
     const uint32_t id0 = static_cast<uint32_t>(row) * static_cast<uint32_t>(a.cols) + static_cast<uint32_t>(c0);
     if constexpr (RASTER) {
-        int pos = mbcnt64(b3, mbcnt64(b2, mbcnt64(b1, mbcnt64(b0, 0))));
+        int pos = 0;
+#pragma unroll
+        for (int m = 0; m < NC; ++m) pos = mbcnt64(b[m], pos);
         const int64_t seg = (static_cast<int64_t>(f) * a.rows + row) * a.tiles_x + tx;
         if (lane_id() == 0) a.seg_cnt[seg] = tot;
         Cand *dst = a.seg + seg * SEGCAP;
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < NC; ++m)
             if (fl[m]) dst[pos++] = Cand{v[m], id0 + m};
     } else {
         if (tot == 0) return;
@@ -91,9 +96,11 @@ __device__ __forceinline__ void emit_row(Sink &sk, const PointsArgs &a, int f, i
             }
             sink_flush(sk, a, f);
         }
-        int pos = mbcnt64(b3, mbcnt64(b2, mbcnt64(b1, mbcnt64(b0, sk.n))));
+        int pos = sk.n;
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < NC; ++m) pos = mbcnt64(b[m], pos);
+#pragma unroll
+        for (int m = 0; m < NC; ++m)
             if (fl[m]) {
                 if (sk.ehist) atomicAdd(&sk.ehist[level0_bin(v[m], a.list.key_base, a.list.key_lz)], 1u);
                 sk.resp[pos] = v[m];
@@ -102,19 +109,6 @@ __device__ __forceinline__ void emit_row(Sink &sk, const PointsArgs &a, int f, i
             }
         sk.n += tot;
     }
-}
-
-__device__ __forceinline__ uint32_t mask_bits4(const PointsArgs &a, int f, int row, int c0) {
-    if (c0 < 0 || c0 >= a.cols) return 0u;
-    const uint32_t w = a.mask[(static_cast<int64_t>(f) * a.rows + row) * a.mask_wpr + (c0 >> 5)];
-    return (w >> (c0 & 31)) & 0xFu;
-}
-// (NC columns from c0, a multiple of NC: they share a word)
-template <int NC>
-__device__ __forceinline__ uint32_t mask_bits(const PointsArgs &a, int f, int row, int c0) {
-    if (c0 < 0 || c0 >= a.cols) return 0u;
-    const uint32_t w = a.mask[(static_cast<int64_t>(f) * a.rows + row) * a.mask_wpr + (c0 >> 5)];
-    return (w >> (c0 & 31)) & ((1u << NC) - 1u);
 }
 
 // Workgroup-shared staging + level-0 histogram (detect mode).
@@ -133,7 +127,8 @@ __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, 
 // ---------------------------------------------------------------------------------------------------
 // K1: corner response + NMS. One wave per tile of kTileW columns x tile_h rows; lane l covers columns
 // c0 = tx*kTileW + 4(l-1) .. c0+3 and walks the rows keeping 3-row sliding windows in registers:
-// pixels (+ DPP halo dwords), horizontal tensor sums, responses.
+// pixels (+ DPP halo dwords), horizontal tensor sums, responses. The row step's arithmetic (gradient row
+// sums, stored responses, NMS) is fd_corner_common.h's; this walk owns the load ring and its pipeline.
 // ---------------------------------------------------------------------------------------------------
 template <int KIND, bool RASTER, bool MASKED, bool ALIGNED, bool G1>
 __global__ __launch_bounds__(256) void k_corner(PointsArgs a) {
@@ -164,30 +159,18 @@ __global__ __launch_bounds__(256) void k_corner(PointsArgs a) {
 
 template <int KIND, bool RASTER, bool MASKED, bool ALIGNED, bool G1>
 __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, int tx, Sink &sk) {
-    const int lane = lane_id();
+    constexpr int NC = 4;
+    static_assert(kTileW == 62 * NC, "tile width of the shared row step");
     const int rows = a.rows, cols = a.cols;
-    const int c0 = tx * kTileW + 4 * (lane - 1);
     const int y0 = 2 + ty * a.tile_h;
     const int y1 = min(y0 + a.tile_h, rows - 2);  // output rows [y0, y1) within [2, rows-3]
     const auto rs = make_rsrc(a.frames + static_cast<int64_t>(f) * rows * cols, static_cast<uint32_t>(rows * cols));
-    // Every lane's 4 columns inside [2, cols-3]: then only the frame's first/last rows need masking.
-    const bool tile_interior = tx * kTileW - 4 >= 2 && tx * kTileW + 4 * 62 + 3 <= cols - 3;
+    const TileCols<NC> tc = tile_columns<NC>(tx, cols);
+    const int c0 = tc.c0;
 
-    bool cval[4], colv[4];  // column inside [2, cols-3]; and owned by an interior lane (emitted)
-    uint64_t colv_b[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        cval[m] = c0 + m >= 2 && c0 + m <= cols - 3;
-        colv[m] = cval[m] && lane >= 1 && lane <= 62;
-        colv_b[m] = ballot(colv[m]);
-    }
-
-    uint32_t hxx[3][4], hyy[3][4], hxy[3][4];  // biased horizontal sums (3 products, 3*beta)
-    float rsp[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) hxx[s][m] = hyy[s][m] = hxy[s][m] = 0, rsp[s][m] = 0.0f;
+    // 3-slot windows of the gradient rows' horizontal sums and of the stored responses
+    HSums<NC> h[3] = {};
+    float rsp[3][NC] = {};
 
     // Row ring of 6 dwords: rows ri-2 .. ri are in use while rows ri+1 .. ri+3 are in flight (a row
     // step is about one HBM latency of wall time at full occupancy). The loop is unrolled by the ring
@@ -216,89 +199,25 @@ __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, 
             // evaluations. Skipped slots keep their zero initialisation and are never read.
             if (!(t >= 2 || i0 > 0)) continue;
 
-            // Gradients of centre row ri-1 at the lane's 4 columns (feature_point_harris_detector.cpp:
-            // 35-62); the two halo bytes of row ri-1 come from the neighbour lanes. Products carry the
-            // float-conversion bias (v_mad_i32_i24 with a constant addend: free).
-            const uint32_t Lc = from_left(P_sc), Rc = from_right(P_sc);
-            uint32_t qxx[6], qyy[6], qxy[6];
-            uint32_t bsq = kBiasSq, bxy = kBiasXy;
-            asm volatile("" : "+s"(bsq), "+s"(bxy));  // opaque: keeps v_mad (else mul + or)  // products at columns c0-1 .. c0+4 (k = m + 1)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int ix = win_byte(Lc, P_sc, Rc, m + 1) - win_byte(Lc, P_sc, Rc, m - 1);
-                const int iy = win_byte(0, P_s, 0, m) - win_byte(0, P_su, 0, m);
-                qxx[m + 1] = static_cast<uint32_t>(ix * ix) + bsq;
-                qyy[m + 1] = static_cast<uint32_t>(iy * iy) + bsq;
-                qxy[m + 1] = static_cast<uint32_t>(ix * iy) + bxy;
-            }
-            // Halo products from the neighbour lanes' edge columns (exact for lanes 0 / 63's inner
-            // columns, whose neighbours are lanes 1 / 62).
-            qxx[0] = from_left(qxx[4]);
-            qyy[0] = from_left(qyy[4]);
-            qxy[0] = from_left(qxy[4]);
-            qxx[5] = from_right(qxx[1]);
-            qyy[5] = from_right(qyy[1]);
-            qxy[5] = from_right(qxy[1]);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                hxx[sc][m] = add3u(qxx[m], qxx[m + 1], qxx[m + 2]);
-                hyy[sc][m] = add3u(qyy[m], qyy[m + 1], qyy[m + 2]);
-                hxy[sc][m] = add3u(qxy[m], qxy[m + 1], qxy[m + 2]);
-            }
+            // Gradients of centre row ri-1; its two halo bytes come from the neighbour lanes.
+            grad_row_sums<NC>(from_left(P_sc), P_sc, from_right(P_sc), P_s, P_su, h[sc]);
 
             if (!(t >= 4 || i0 > 0)) continue;
-            // Response of row rr = ri-2: vertical 3-row sums are exact integers (< 2^23).
-            const int rr = ri - 2;
-            const bool rowv = rr >= 2 && rr <= rows - 3;
-            uint32_t sxx[4], syy[4], sxy[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                sxx[m] = add3u(hxx[s][m], hxx[su][m], hxx[sc][m]);
-                syy[m] = add3u(hyy[s][m], hyy[su][m], hyy[sc][m]);
-                sxy[m] = add3u(hxy[s][m], hxy[su][m], hxy[sc][m]);
-            }
-            const f2 r01 = corner_response2<KIND, G1>(sxx[0], sxx[1], syy[0], syy[1], sxy[0], sxy[1], a.thr);
-            const f2 r23 = corner_response2<KIND, G1>(sxx[2], sxx[3], syy[2], syy[3], sxy[2], sxy[3], a.thr);
-            const float r[4] = {r01.x, r01.y, r23.x, r23.y};
-            if (!MASKED && rowv && tile_interior) {  // wave-uniform: no per-pixel masking needed
-#pragma unroll
-                for (int m = 0; m < 4; ++m) rsp[su][m] = r[m];
-            } else {
-                uint32_t mb = 0xFu;
-                if constexpr (MASKED) mb = rowv ? mask_bits4(a, f, rr, c0) : 0u;
-                // Lane 0's columns 2-3 and lane 63's columns 0-1 are exact and serve as the NMS
-                // neighbours of the tile's edge columns.
-#pragma unroll
-                for (int m = 0; m < 4; ++m) rsp[su][m] = (rowv && cval[m] && ((mb >> m) & 1u)) ? r[m] : 0.0f;
-            }
+            response_row<KIND, G1, MASKED, NC>(a, f, ri - 2, tc, h[s], h[su], h[sc], rsp[su]);
 
-            // NMS of row nr = ri-3 (feature_point_harris_detector.cpp:120-137): strict, 4-neighbour.
-            // x > thr and x > each neighbour  <=>  x > max(thr, neighbours)  (no NaNs; +-0 compare equal).
-            const int nr = ri - 3;
+            const int nr = ri - 3;  // the row whose four neighbours are now known
             if (nr >= y0 && nr < y1) {  // wave-uniform
-                const float lft = from_left_f(rsp[s][3]);
-                const float rgt = from_right_f(rsp[s][0]);
-                bool fl[4];
-                float v[4];
-                uint64_t b[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float x = rsp[s][m];
-                    const float xl = m == 0 ? lft : rsp[s][m - 1];
-                    const float xr = m == 3 ? rgt : rsp[s][m + 1];
-                    const float nb = max3f(max3f(xl, xr, a.thr), rsp[sc][m], rsp[su][m]);
-                    const bool hit = x > nb;
-                    v[m] = x;
-                    fl[m] = colv[m] && hit;
-                    b[m] = ballot(hit) & colv_b[m];  // the compare's lane mask, no bool round trip
-                }
+                bool fl[NC];
+                float v[NC];
+                uint64_t b[NC];
+                nms_row<NC>(rsp[s], rsp[sc], rsp[su], a.thr, tc, b, fl, v);
                 emit_row<RASTER, kSegCorner>(sk, a, f, tx, nr, c0, b, fl, v);
                 if constexpr (RASTER) {
                     if (a.resp_map != nullptr) {
                         float *mrow = a.resp_map + (static_cast<int64_t>(f) * rows + nr) * cols;
 #pragma unroll
-                        for (int m = 0; m < 4; ++m)
-                            if (colv[m]) mrow[c0 + m] = v[m];
+                        for (int m = 0; m < NC; ++m)
+                            if (tc.colv[m]) mrow[c0 + m] = v[m];
                     }
                 }
             }
@@ -311,81 +230,34 @@ __device__ __forceinline__ void corner_tile(const PointsArgs &a, int f, int ty, 
 // the row ring. A lone wave per SIMD pays one memory latency per dependent load and the issue latency of
 // every dependent VALU operation, so the tile's kShortTileH + 6 rows are all requested before the first
 // is used (one exposed round trip instead of two) and the 9 row steps are straight-line code. A lane
-// covers NC columns, c0 = tx * 62 NC + NC (l - 1); lanes 0 and 63 are halo lanes. With NC == 2 a workgroup
-// is 8 waves over the 4 tiles' columns of k_corner's workgroup (tile t = tiles 2t, 2t + 1 here), so the
-// segments, their descriptors and the selection see the same candidate sets per workgroup.
+// covers two columns, c0 = tx * 124 + 2 (l - 1); lanes 0 and 63 are halo lanes. A workgroup is 8 waves over
+// the 4 tiles' columns of k_corner's workgroup (tile t = tiles 2t, 2t + 1 here), so the segments, their
+// descriptors and the selection see the same candidate sets per workgroup. The row step itself is
+// k_corner's (fd_corner_common.h).
 // ---------------------------------------------------------------------------------------------------
 constexpr int kShortTileH = 3;
 // columns per lane: 2 measured 0.38 us per headline step faster than 4 (k_corner's geometry, same code),
 // which was itself 0.96 us faster than k_corner (profiles/r08_k1_short_tile_ab.txt)
 constexpr int kShortCols = 2;
-static_assert(kShortCols == 2 || kShortCols == 4, "columns per lane of the short-tile kernel");
-constexpr int kShortWg = kWave * 4 * (4 / kShortCols);
+constexpr int kShortTileW = 62 * kShortCols;
+constexpr int kShortWg = kWave * 4 * (kTileW / kShortTileW);
 // Per-wave staging. It never overflows: strict 4-neighbour NMS admits at most every other pixel, so a
-// wave stages at most 62 NC * kShortTileH / 2 entries (186 at NC == 2, 372 at 4). The overflow path stays
-// compiled all the same (emit_short).
-constexpr int kShortStage = kShortCols == 2 ? 252 : kStage;
+// wave stages at most 62 * kShortCols * kShortTileH / 2 = 186 entries. The overflow path stays compiled all the same
+// (emit_row).
+constexpr int kShortStage = 252;
 static_assert(kShortStage >= 62 * kShortCols * kShortTileH / 2, "a short tile's candidates fit the staging");
 using ShortLds = DetectLdsT<kShortStage, kShortWg / kWave>;
 static_assert(sizeof(ShortLds) + 4 * (kShortWg / kWave + 2) <= 32768, "32 KiB of LDS per workgroup");
 static_assert(sizeof(ShortLds) % 16 == 0 && offsetof(ShortLds, hist) % 16 == 0, "uint4 histogram access");
 
-// The lane's NC pixels of one row as the low bytes of a dword.
-template <int NC, bool ALIGNED>
-__device__ __forceinline__ uint32_t load_pxn(__amdgpu_buffer_rsrc_t r, int32_t off) {
-    if constexpr (NC == 4) return load_px4<ALIGNED>(r, off);
-    else if constexpr (ALIGNED) return buf_load_u16(r, off);  // (off is even: cols % 4 == 0, c0 even)
-    else return buf_load_u8(r, off) | (buf_load_u8(r, off + 1) << 8);
-}
-// Byte j in [-1, NC] of the window [left lane | own NC bytes | right lane] (compile-time j).
-template <int NC>
-__device__ __forceinline__ int px_byte(uint32_t L, uint32_t M, uint32_t R, int j) {
-    const uint32_t w = j < 0 ? L : (j < NC ? M : R);
-    const int sh = 8 * (j < 0 ? NC - 1 : (j < NC ? j : 0));
-    return static_cast<int>((w >> sh) & 0xFFu);
-}
-
-// emit_row's detect mode for NC columns per lane.
-template <int NC>
-__device__ __forceinline__ void emit_short(Sink &sk, const PointsArgs &a, int f, int row, int c0,
-                                           const uint64_t (&b)[NC], const bool (&fl)[NC], const float (&v)[NC]) {
-    int tot = 0;
-#pragma unroll
-    for (int m = 0; m < NC; ++m) tot += popc64(b[m]);  // scalar unit
-    if (tot == 0) return;
-    if (sk.n + tot > sk.cap) {  // (not reached, see kShortStage: the frame's list would no longer be sorted segments)
-        if (lane_id() == 0) {
-            atomicOr(&a.seg_bad[f], 1u);
-            *sk.ovf = 1u;
-        }
-        sink_flush(sk, a, f);
-    }
-    int pos = sk.n;
-#pragma unroll
-    for (int m = 0; m < NC; ++m) pos = mbcnt64(b[m], pos);
-    const uint32_t id0 = static_cast<uint32_t>(row) * static_cast<uint32_t>(a.cols) + static_cast<uint32_t>(c0);
-#pragma unroll
-    for (int m = 0; m < NC; ++m)
-        if (fl[m]) {
-            sk.resp[pos] = v[m];
-            sk.idx[pos] = id0 + m;
-            ++pos;
-        }
-    sk.n += tot;
-}
-
-template <int T>
-struct StepC {
-    static constexpr int value = T;
-};
-
-template <int KIND, bool MASKED, bool ALIGNED, int NC>
+template <int KIND, bool MASKED, bool ALIGNED>
 __device__ __forceinline__ void corner_tile_short(const PointsArgs &a, int f, int ty, int tx, Sink &sk) {
-    constexpr int TW = 62 * NC;
+    constexpr int NC = kShortCols;
     constexpr int kRows = kShortTileH + 6;
     const int lane = lane_id();
     const int rows = a.rows, cols = a.cols;
-    const int c0 = tx * TW + NC * (lane - 1);
+    const TileCols<NC> tc = tile_columns<NC>(tx, cols);
+    const int c0 = tc.c0;
     const int y0 = 2 + ty * kShortTileH;
     const int y1 = min(y0 + kShortTileH, rows - 2);  // output rows [y0, y1) within [2, rows-3]
     const int n_in = (y1 - y0) + 6;
@@ -394,136 +266,59 @@ __device__ __forceinline__ void corner_tile_short(const PointsArgs &a, int f, in
     // outside the buffer resource's range and read as 0, rows past a short last tile are not used).
     uint32_t P[kRows];
 #pragma unroll
-    for (int t = 0; t < kRows; ++t) P[t] = load_pxn<NC, ALIGNED>(rs, (y0 - 3 + t) * cols + c0);
-    // NC == 2: the halo lanes' inner column (the NMS neighbour of the tile's edge column) needs the pixel two
-    // columns further out, which no lane holds: lanes 0 and 63 load their outer neighbour's pair themselves.
+    for (int t = 0; t < kRows; ++t) P[t] = load_px2<ALIGNED>(rs, (y0 - 3 + t) * cols + c0);
+    // The halo lanes' inner column (the NMS neighbour of the tile's edge column) needs the pixel two columns
+    // further out, which no lane holds: lanes 0 and 63 load their outer neighbour's pair themselves.
     uint32_t E[kRows];
 #pragma unroll
     for (int t = 0; t < kRows; ++t) E[t] = 0u;
-    if constexpr (NC == 2) {
-        if (lane == 0 || lane == 63) {
-            const int eoff = lane == 0 ? -NC : NC;
+    if (lane == 0 || lane == 63) {
+        const int eoff = lane == 0 ? -NC : NC;
 #pragma unroll
-            for (int t = 0; t < kRows; ++t) E[t] = load_pxn<NC, ALIGNED>(rs, (y0 - 3 + t) * cols + c0 + eoff);
-        }
-    }
-
-    const bool tile_interior = tx * TW - NC >= 2 && tx * TW + NC * 62 + NC - 1 <= cols - 3;
-    bool cval[NC], colv[NC];  // column inside [2, cols-3]; and owned by an interior lane (emitted)
-    uint64_t colv_b[NC];
-#pragma unroll
-    for (int m = 0; m < NC; ++m) {
-        cval[m] = c0 + m >= 2 && c0 + m <= cols - 3;
-        colv[m] = cval[m] && lane >= 1 && lane <= 62;
-        colv_b[m] = ballot(colv[m]);
+        for (int t = 0; t < kRows; ++t) E[t] = load_px2<ALIGNED>(rs, (y0 - 3 + t) * cols + c0 + eoff);
     }
 
     // Step t has row y0-3+t: it computes the gradients of row y0-4+t (t >= 2), the responses of row y0-5+t
     // (t >= 4) and the NMS of row y0-6+t (t >= 6), as k_corner's steps do; every row keeps its registers.
-    uint32_t hxx[kRows][NC], hyy[kRows][NC], hxy[kRows][NC];  // [t]: biased horizontal sums of row y0-4+t
-    float rsp[kRows][NC];                                     // [t]: stored responses of row y0-5+t
-    auto step = [&](auto tc) {
-        constexpr int t = decltype(tc)::value;
-        const uint32_t P_s = P[t], P_sc = P[t - 1], P_su = P[t - 2];
+    HSums<NC> h[kRows];    // [t]: horizontal sums of row y0-4+t
+    float rsp[kRows][NC];  // [t]: stored responses of row y0-5+t
+    auto step = [&](auto index) {
+        constexpr int t = decltype(index)::value;
         // (the lane without a source lane keeps the DPP move's old value: its own outer pair, or 0)
-        const uint32_t Lc = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(E[t - 1]), static_cast<int>(P_sc), 0x138, 0xF, 0xF, false));
-        const uint32_t Rc = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(E[t - 1]), static_cast<int>(P_sc), 0x130, 0xF, 0xF, false));
-        uint32_t qxx[NC + 2], qyy[NC + 2], qxy[NC + 2];  // products at columns c0-1 .. c0+NC (k = m + 1)
-        uint32_t bsq = kBiasSq, bxy = kBiasXy;
-        asm volatile("" : "+s"(bsq), "+s"(bxy));  // opaque: keeps v_mad (else mul + or)
-#pragma unroll
-        for (int m = 0; m < NC; ++m) {
-            const int ix = px_byte<NC>(Lc, P_sc, Rc, m + 1) - px_byte<NC>(Lc, P_sc, Rc, m - 1);
-            const int iy = px_byte<NC>(0, P_s, 0, m) - px_byte<NC>(0, P_su, 0, m);
-            qxx[m + 1] = static_cast<uint32_t>(ix * ix) + bsq;
-            qyy[m + 1] = static_cast<uint32_t>(iy * iy) + bsq;
-            qxy[m + 1] = static_cast<uint32_t>(ix * iy) + bxy;
-        }
-        // Halo products from the neighbour lanes' edge columns (exact for lanes 0 / 63's inner columns).
-        qxx[0] = from_left(qxx[NC]);
-        qyy[0] = from_left(qyy[NC]);
-        qxy[0] = from_left(qxy[NC]);
-        qxx[NC + 1] = from_right(qxx[1]);
-        qyy[NC + 1] = from_right(qyy[1]);
-        qxy[NC + 1] = from_right(qxy[1]);
-#pragma unroll
-        for (int m = 0; m < NC; ++m) {
-            hxx[t][m] = add3u(qxx[m], qxx[m + 1], qxx[m + 2]);
-            hyy[t][m] = add3u(qyy[m], qyy[m + 1], qyy[m + 2]);
-            hxy[t][m] = add3u(qxy[m], qxy[m + 1], qxy[m + 2]);
-        }
-
+        const uint32_t Lc = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(E[t - 1]), static_cast<int>(P[t - 1]), 0x138, 0xF, 0xF, false));
+        const uint32_t Rc = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(E[t - 1]), static_cast<int>(P[t - 1]), 0x130, 0xF, 0xF, false));
+        grad_row_sums<NC>(Lc, P[t - 1], Rc, P[t], P[t - 2], h[t]);
         if constexpr (t >= 4) {
-            // Response of row rr (vertical 3-row sums are exact integers below 2^23).
-            const int rr = y0 - 5 + t;
-            const bool rowv = rr >= 2 && rr <= rows - 3;
-            float r[NC];
-#pragma unroll
-            for (int m = 0; m < NC; m += 2) {
-                uint32_t sxx[2], syy[2], sxy[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    sxx[k] = add3u(hxx[t][m + k], hxx[t - 2][m + k], hxx[t - 1][m + k]);
-                    syy[k] = add3u(hyy[t][m + k], hyy[t - 2][m + k], hyy[t - 1][m + k]);
-                    sxy[k] = add3u(hxy[t][m + k], hxy[t - 2][m + k], hxy[t - 1][m + k]);
-                }
-                const f2 rp = corner_response2<KIND, true>(sxx[0], sxx[1], syy[0], syy[1], sxy[0], sxy[1], a.thr);
-                r[m] = rp.x;
-                r[m + 1] = rp.y;
-            }
-            if (!MASKED && rowv && tile_interior) {  // wave-uniform: no per-pixel masking needed
-#pragma unroll
-                for (int m = 0; m < NC; ++m) rsp[t][m] = r[m];
-            } else {
-                uint32_t mb = (1u << NC) - 1u;
-                if constexpr (MASKED) mb = rowv ? mask_bits<NC>(a, f, rr, c0) : 0u;
-#pragma unroll
-                for (int m = 0; m < NC; ++m) rsp[t][m] = (rowv && cval[m] && ((mb >> m) & 1u)) ? r[m] : 0.0f;
-            }
-
+            response_row<KIND, true, MASKED, NC>(a, f, y0 - 5 + t, tc, h[t], h[t - 2], h[t - 1], rsp[t]);
             if constexpr (t >= 6) {
-                // NMS of row nr (feature_point_harris_detector.cpp:120-137): strict, 4-neighbour, as in k_corner.
-                const int nr = y0 - 6 + t;
-                const float lft = from_left_f(rsp[t - 1][NC - 1]);
-                const float rgt = from_right_f(rsp[t - 1][0]);
                 bool fl[NC];
                 float v[NC];
                 uint64_t b[NC];
-#pragma unroll
-                for (int m = 0; m < NC; ++m) {
-                    const float x = rsp[t - 1][m];
-                    const float xl = m == 0 ? lft : rsp[t - 1][m - 1];
-                    const float xr = m == NC - 1 ? rgt : rsp[t - 1][m + 1];
-                    const float nb = max3f(max3f(xl, xr, a.thr), rsp[t][m], rsp[t - 2][m]);
-                    const bool hit = x > nb;
-                    v[m] = x;
-                    fl[m] = colv[m] && hit;
-                    b[m] = ballot(hit) & colv_b[m];
-                }
-                emit_short<NC>(sk, a, f, nr, c0, b, fl, v);
+                nms_row<NC>(rsp[t - 1], rsp[t], rsp[t - 2], a.thr, tc, b, fl, v);
+                emit_row<false, kSegCorner>(sk, a, f, tx, y0 - 6 + t, c0, b, fl, v);
             }
         }
     };
     // (straight-line: no loop, every row and sum keeps its own registers; the frame's last tile row may
     // hold 1 or 2 rows, which end the walk early, wave-uniformly)
-    step(StepC<2>{});
-    step(StepC<3>{});
-    step(StepC<4>{});
-    step(StepC<5>{});
-    step(StepC<6>{});
-    if (n_in > 7) step(StepC<7>{});
-    if (n_in > 8) step(StepC<8>{});
+    step(std::integral_constant<int, 2>{});
+    step(std::integral_constant<int, 3>{});
+    step(std::integral_constant<int, 4>{});
+    step(std::integral_constant<int, 5>{});
+    step(std::integral_constant<int, 6>{});
+    if (n_in > 7) step(std::integral_constant<int, 7>{});
+    if (n_in > 8) step(std::integral_constant<int, 8>{});
 }
 
 template <int KIND, bool MASKED, bool ALIGNED>
 __global__ __launch_bounds__(kShortWg) void k_corner_short(PointsArgs a) {
-    constexpr int NC = kShortCols, W = kShortWg / kWave;
+    constexpr int W = kShortWg / kWave;
     __shared__ ShortLds lds;
     __shared__ uint32_t seg_ovf, seg_wtot[W], seg_base;
     const int lb = logical_block();
     const int f = lb / a.blocks_per_frame, g = lb % a.blocks_per_frame;
     const int wv = threadIdx.x >> 6;
-    const int tiles_x = a.tiles_x * (4 / NC);  // (a.tiles_x counts k_corner's tiles of kTileW columns)
+    const int tiles_x = a.tiles_x * (kTileW / kShortTileW);  // (a.tiles_x counts k_corner's tiles of kTileW columns)
     const int t = __builtin_amdgcn_readfirstlane(g * W + wv);
     const int tx = t % tiles_x, ty = t / tiles_x;
     const bool active = t < tiles_x * a.tiles_y;
@@ -531,7 +326,7 @@ __global__ __launch_bounds__(kShortWg) void k_corner_short(PointsArgs a) {
     sk.cap = kShortStage;
     if (threadIdx.x == 0) seg_ovf = 0;
     hist_clear<kShortWg>(lds.hist);
-    if (active) corner_tile_short<KIND, MASKED, ALIGNED, NC>(a, f, ty, tx, sk);
+    if (active) corner_tile_short<KIND, MASKED, ALIGNED>(a, f, ty, tx, sk);
     SinkSource src{sk};
     seg_list_flush<kShortWg>(src, a, f, g, active, lds.hist, &seg_ovf, seg_wtot, seg_base);
 }
@@ -797,7 +592,7 @@ __device__ __forceinline__ void fast_tile(const PointsArgs &a, const FastOffsets
             };
             uint32_t live = colmask;
             if constexpr (MASKED) {
-                const uint32_t mb = mask_bits4(a, f, orow, c0);
+                const uint32_t mb = mask_bits<4>(a, f, orow, c0);
                 live &= ((mb & 1u) ? 0x80u : 0u) | ((mb & 2u) ? 0x8000u : 0u) | ((mb & 4u) ? 0x800000u : 0u) |
                         ((mb & 8u) ? 0x80000000u : 0u);
             }

@@ -170,6 +170,28 @@ def test_priors_out_of_image_and_fractional(fd, oracle):
         check_detect(fd, oracle, name, img, 12, THR[name], 80, prior)
 
 
+@pytest.mark.parametrize("cols", [247, 248, 249, 250, 253])
+def test_ring_walk_masked_at_tile_seam(fd, oracle, monkeypatch, cols):
+    """k_corner's MASKED instances at the last lanes of its 248-column tile (253: a second tile), with aligned
+    and unaligned rows (cols % 4) and priors on the seam columns: the raster-ordered candidate stage, detect
+    with a negative threshold (the G1 = false form), and detect at thr >= 0 with the sorted-segment lists
+    switched off (a launch this small runs k_corner_short otherwise)."""
+    rows, dist = 11, 3
+    img = oracle.make_frame("noise", 800 + cols, rows, cols)
+    prior = np.array([(247.0, 4.0), (244.5, 8.0), (2.0, 2.0), (60.0, 5.0), (cols - 3.0, 6.0), (123.0, 3.0)], np.float32)
+    mask = build_mask(rows, cols, dist, prior)
+    for name in ("harris", "shi_tomasi"):
+        (got,) = fd.point_candidates(name, img, dist, THR[name], prior=[prior])
+        exp = oracle_candidates(oracle, name, img, THR[name], mask)
+        assert_same_candidates(got, exp)
+        assert 0 < len(exp[0]) < len(oracle_candidates(oracle, name, img, THR[name])[0])
+        check_detect(fd, oracle, name, img, dist, -1.0, 4096, prior)
+    monkeypatch.setenv("FD_DEBUG_AB", "1")  # (the library reads A/B switches only with it)
+    monkeypatch.setenv("FD_SEG_LISTS", "0")
+    for name in ("harris", "shi_tomasi"):
+        assert len(check_detect(fd, oracle, name, img, dist, THR[name], 4096, prior)) > 0
+
+
 def test_empty_candidates(fd, oracle):
     img = np.full((64, 64), 128, np.uint8)
     for name in ("harris", "shi_tomasi", "fast"):
