@@ -51,4 +51,35 @@ bool GeometricVerifier::Verify(const std::vector<Vec2> &query_uv, const std::vec
     return true;
 }
 
+bool GeometricVerifier::Refit(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, std::vector<uint8_t> &inlier,
+                              std::array<double, 9> &model, int32_t rounds, const std::vector<int32_t> *train_index,
+                              const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
+    const size_t n = query_uv.size();
+    if (accepted_rounds) *accepted_rounds = 0;
+    if (n == 0) return context_.Fail("Refit: no query points");
+    if (inlier.size() != n) return context_.Fail("Refit: one inlier flag per query point is needed");
+    if (train_index && train_index->size() != n) return context_.Fail("Refit: one train index per query point is needed");
+    if (valid && valid->size() != n) return context_.Fail("Refit: one valid flag per query point is needed");
+    if (!train_index && train_uv.size() < n)
+        return context_.Fail("Refit: without train_index every query point needs its train point");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    const std::vector<float> q = Flatten(query_uv);
+    std::vector<float> t = Flatten(train_uv);
+    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const fd_refit_opts o{options_.kModel, rounds, options_.kThreshold, options_.kCenterX, options_.kCenterY, options_.kScale};
+    std::vector<uint8_t> out_inlier(n);
+    double m[9];
+    int32_t accepted = 0;
+    const int rc = fd_ransac_refit(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
+                                   static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
+                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), m, out_inlier.data(), nullptr,
+                                   &accepted, 0);
+    if (rc != FD_OK) return context_.FailCall("fd_ransac_refit");
+    inlier.swap(out_inlier);
+    std::copy(m, m + 9, model.begin());
+    if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
 }  // namespace feature_detector

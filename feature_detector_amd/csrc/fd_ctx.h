@@ -63,7 +63,7 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest call is a guided match: 8 inputs, 3 outputs
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a guided match (8 inputs, 3 outputs) and fd_ransac_refit (7 and 4)
     static constexpr int kStaging = 11;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
@@ -73,8 +73,8 @@ struct fd_ctx {
     fdrt::DevBuf f_bxy, f_bst;
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
-    // per-frame best-hypothesis words
-    fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best;
+    // per-frame best-hypothesis words; fd_ransac_refit: the support sets by list position ([batch][2][q_stride] bytes)
+    fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best, g_member;
     // fd_frames_equalize: the tiles' LUTs ([batch][tiles_y][tiles_x][256] bytes), then the columns' and rows'
     // interpolation entries ([cols + rows] words)
     fdrt::DevBuf e_ws;

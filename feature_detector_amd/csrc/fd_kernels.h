@@ -440,6 +440,18 @@ struct RansacArgs {
     int32_t *out_counts, *out_best;  // [batch] or null
 };
 
+// Least-squares refit of a RANSAC model on its inliers (fd_ransac.hip; fd_ransac_refit of include/fd_hip.h).
+// k_ransac_compact runs on `r` as it does for fd_ransac (hypotheses, seed, models, out_best unused; r.best is
+// zeroed); k_ransac_refit reads r's lists and writes r.out_model, r.out_inlier, r.out_counts.
+struct RefitArgs {
+    RansacArgs r;
+    const double *in_model;      // [batch][9]; may be r.out_model
+    const uint8_t *in_inlier;    // [batch][q_stride]; only a byte equal to 1 is a member; may be r.out_inlier
+    uint8_t *member;             // [batch][2][q_stride] workspace: membership by list position, current and candidate
+    int rounds;                  // 1..4
+    int32_t *out_rounds;         // [batch] or null
+};
+
 // Image warp (fd_warp.hip): every destination pixel of out [batch][out_rows][out_cols] sampled from the frames
 // [batch][rows][cols] at the position a per-frame model gives (fd_frames_warp of include/fd_hip.h).
 struct WarpArgs {
@@ -480,6 +492,8 @@ hipError_t launch_equalize(EqualizeArgs a, hipStream_t s);
 hipError_t launch_warp(WarpArgs a, hipStream_t s);
 // the three kernels of fd_ransac, in order
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);
+// k_ransac_compact, then k_ransac_refit (all rounds in one launch)
+hipError_t launch_ransac_refit(const RefitArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);

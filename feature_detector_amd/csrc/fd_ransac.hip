@@ -13,7 +13,14 @@
 // counting its own model's inliers. The wave's best (count, lowest index) goes to the frame's 64-bit slot
 // in one atomicMax. k_ransac_finish, one workgroup per frame: classifies every slot with the winner by the
 // same device function and writes the outputs.
-#include "fd_match_common.h"
+//
+// k_ransac_refit (fd_ransac_refit), one workgroup per frame after k_ransac_compact: every round of the
+// least-squares refit on the support set inside one launch. The 9 x 9 normal matrix is summed in the
+// contract's order (256 partials in registers, an LDS tree in slices of 9 entries), its smallest eigenvector
+// comes from a fixed number of cyclic Jacobi sweeps on one wave with the matrix and V in LDS, F is projected
+// to rank 2 by the same routine on F^T F, and every correspondence is classified again.
+#include "fd_hip.h"
+#include "fd_window.h"
 
 namespace fdk {
 namespace {
@@ -266,6 +273,36 @@ __device__ __forceinline__ void matmul3(const double (&a)[9], const double (&b)[
         }
 }
 
+// The pixel-coordinate model of the conditioned one x, divided by its entry of largest magnitude, into om[9]
+// (the "Outputs" paragraph of fd_ransac; fd_ransac_refit writes its accepted model the same way).
+template <int MODEL>
+__device__ __forceinline__ void write_model(const double (&x)[9], double cx, double cy, double s, double *om) {
+    const double T[9] = {s, 0.0, -(s * cx), 0.0, s, -(s * cy), 0.0, 0.0, 1.0};
+    double L[9], mt[9], p[9];
+    if (MODEL == kFundamental) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) L[3 * i + j] = T[3 * j + i];
+    } else {
+        const double inv = 1.0 / s;
+        const double Ti[9] = {inv, 0.0, cx, 0.0, inv, cy, 0.0, 0.0, 1.0};
+#pragma unroll
+        for (int c = 0; c < 9; ++c) L[c] = Ti[c];
+    }
+    matmul3(x, T, mt);
+    matmul3(L, mt, p);
+    double best = -1.0, pv = p[0];
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+        if (fabs(p[c]) > best) {
+            best = fabs(p[c]);
+            pv = p[c];
+        }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) om[c] = p[c] / pv;
+}
+
 template <int MODEL>
 __global__ __launch_bounds__(kRansacThreads) void k_ransac_finish(RansacArgs a) {
     __shared__ int total;
@@ -303,34 +340,278 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_finish(RansacArgs a) 
         for (int c = 0; c < 9; ++c) om[c] = 0.0;
         return;
     }
-    const double s = a.scale;
-    const double T[9] = {s, 0.0, -(s * a.cx), 0.0, s, -(s * a.cy), 0.0, 0.0, 1.0};
-    double L[9], mt[9], p[9];
-    if (MODEL == kFundamental) {
+    write_model<MODEL>(x, a.cx, a.cy, a.scale, om);
+}
+
+// ---- fd_ransac_refit: the least-squares refit of a model on its inliers ------------------------------------
+constexpr int kSweeps = FD_REFIT_SWEEPS;
+constexpr int kNormal = 45;  // entries (a, b), a <= b, of the 9 x 9 normal matrix, row-major
+constexpr int kSlice = 9;    // of them through the LDS tree at a time: 9 * 256 * 8 B = 18 KiB (45 at once: 90 KiB)
+
+// acc += row^T row, the 45 entries in order, each one product and one sum.
+__device__ __forceinline__ void add_row(double (&acc)[kNormal], const double (&r)[9]) {
+    int e = 0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < 9; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) L[3 * i + j] = T[3 * j + i];
-    } else {
-        const double inv = 1.0 / s;
-        const double Ti[9] = {inv, 0.0, a.cx, 0.0, inv, a.cy, 0.0, 0.0, 1.0};
+        for (int j = i; j < 9; ++j, ++e) acc[e] = acc[e] + r[i] * r[j];
+}
+
+// The workgroup's sum of one count per thread.
+__device__ __forceinline__ int wg_count(uint32_t mine, int *total) {
+    __syncthreads();
+    if (threadIdx.x == 0) *total = 0;
+    __syncthreads();
+    const uint32_t wave_n = wave_total_add(mine);
+    if (lane_id() == 0 && wave_n) atomicAdd(total, static_cast<int>(wave_n));
+    __syncthreads();
+    return *total;
+}
+
+// Cyclic Jacobi of the contract on one wave. m holds 2 N rows of N doubles in LDS: the symmetric matrix, then
+// V. Lane r < 2 N owns row r: every element update of a rotation is an expression of the values before it,
+// so the lanes read their two elements, then write them (the matrix rows mirrored into the columns), and the
+// result is the serial restatement's bit for bit. The dependent chain of a rotation (two divisions, two square
+// roots) is computed by every lane alike; p, q and the skip are wave-uniform.
+template <int N>
+__device__ __forceinline__ void jacobi(double *m, int lane) {
+    const bool live = lane < 2 * N, sym = lane < N;
+    const int r = live ? lane : 0;
+    for (int sweep = 0; sweep < kSweeps; ++sweep)
+        for (int p = 0; p < N - 1; ++p)
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = m[p * N + q];
+                if (apq == 0.0) continue;
+                const double app = m[p * N + p], aqq = m[q * N + q];
+                const double xp = m[r * N + p], xq = m[r * N + q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0);
+                const double s = t * c;
+                double np = c * xp - s * xq, nq = s * xp + c * xq;
+                if (sym && r == p) {
+                    np = app - t * apq;
+                    nq = 0.0;
+                }
+                if (sym && r == q) {
+                    np = 0.0;
+                    nq = aqq + t * apq;
+                }
+                wave_lds_sync();
+                if (live) {
+                    m[r * N + p] = np;
+                    m[r * N + q] = nq;
+                }
+                if (sym) {
+                    m[p * N + r] = np;
+                    m[q * N + r] = nq;
+                }
+                wave_lds_sync();
+            }
+}
+
+// Index of the smallest of d: a strict < from entry 0.
+template <int N>
+__device__ __forceinline__ int smallest(const double (&d)[N]) {
+    int at = 0;
+    double best = d[0];
 #pragma unroll
-        for (int c = 0; c < 9; ++c) L[c] = Ti[c];
+    for (int i = 1; i < N; ++i)
+        if (d[i] < best) {
+            best = d[i];
+            at = i;
+        }
+    return at;
+}
+
+// One workgroup per frame, all rounds. The support set lives in global memory by list position, the current
+// one and the round's candidate; thread t reads and writes the positions i = t (mod 256) only, which is also
+// the contract's partial t of the normal matrix, so its 45 sums stay in registers over the frame.
+template <int MODEL>
+__global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
+    constexpr int M = MODEL == kFundamental ? 8 : 4;
+    __shared__ double red[kSlice * kRansacThreads];
+    __shared__ double mat[18 * 9];
+    __shared__ double mat3[6 * 3];
+    __shared__ double accepted[9];
+    __shared__ int total;
+    const RansacArgs &a = g.r;
+    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x), lane = lane_id();
+    const int nf = frame_count(a.q_counts, f, a.q_stride);
+    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
+    const int n = a.n[f];
+    const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + s0;
+    uint8_t *mem = g.member + 2 * s0;
+    for (int s = tid; s < nf; s += kRansacThreads) {
+        const int ci = a.cidx[s0 + s];
+        if (ci >= 0) mem[ci] = g.in_inlier[s0 + s] == 1 ? 1 : 0;  // ci < n <= q_stride
     }
-    matmul3(x, T, mt);
-    matmul3(L, mt, p);
-    double best = -1.0, pv = p[0];
+    __syncthreads();
+    uint32_t mine = 0;
+    for (int i = tid; i < n; i += kRansacThreads) mine += mem[i];
+    int count = wg_count(mine, &total);
+    int cur = 0, done = 0;
+
+    for (int round = 0; round < g.rounds && count >= M; ++round) {  // every exit is uniform over the workgroup
+        const uint8_t *S = mem + cur * a.q_stride;
+        uint8_t *S2 = mem + (cur ^ 1) * a.q_stride;
+        double acc[kNormal];
 #pragma unroll
-    for (int c = 0; c < 9; ++c)
-        if (fabs(p[c]) > best) {
-            best = fabs(p[c]);
-            pv = p[c];
+        for (int e = 0; e < kNormal; ++e) acc[e] = 0.0;
+        for (int i = tid; i < n; i += kRansacThreads) {
+            if (!S[i]) continue;
+            const d4 p = corr[i];
+            const double x = p.x, y = p.y, u = p.z, v = p.w;
+            if (MODEL == kFundamental) {
+                const double r0[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+                add_row(acc, r0);
+            } else {
+                const double r0[9] = {x, y, 1.0, 0.0, 0.0, 0.0, -(u * x), -(u * y), -u};
+                const double r1[9] = {0.0, 0.0, 0.0, x, y, 1.0, -(v * x), -(v * y), -v};
+                add_row(acc, r0);
+                add_row(acc, r1);
+            }
         }
 #pragma unroll
-    for (int c = 0; c < 9; ++c) om[c] = p[c] / pv;
+        for (int sl = 0; sl < kNormal / kSlice; ++sl) {
+#pragma unroll
+            for (int j = 0; j < kSlice; ++j) red[j * kRansacThreads + tid] = acc[sl * kSlice + j];
+            for (int step = kRansacThreads / 2; step >= 1; step >>= 1) {
+                __syncthreads();
+                if (tid < step) {
+#pragma unroll
+                    for (int j = 0; j < kSlice; ++j)
+                        red[j * kRansacThreads + tid] = red[j * kRansacThreads + tid] + red[j * kRansacThreads + tid + step];
+                }
+            }
+            __syncthreads();
+            if (tid < kSlice) {
+                int i = 0, rem = sl * kSlice + tid;  // entry (i, j) of the row-major upper triangle
+                while (rem >= 9 - i) {
+                    rem -= 9 - i;
+                    ++i;
+                }
+                const int j = i + rem;
+                const double v = red[tid * kRansacThreads];
+                mat[i * 9 + j] = v;
+                mat[j * 9 + i] = v;
+            }
+            __syncthreads();
+        }
+        if (tid < 81) mat[81 + tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
+        __syncthreads();
+        if (tid < kWave) jacobi<9>(mat, lane);
+        __syncthreads();
+        double d[9], x[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) d[k] = mat[k * 9 + k];
+        const int at = smallest<9>(d);
+        double d2 = __builtin_inf(), dmax = d[0];
+        bool valid = true;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            if (k != at && d[k] < d2) d2 = d[k];
+            if (d[k] > dmax) dmax = d[k];
+            x[k] = mat[(9 + k) * 9 + at];
+            valid = valid && isfinite(x[k]);
+        }
+        valid = valid && d2 > 1e-12 * dmax;
+        if (MODEL == kFundamental) {
+            if (tid == 0) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) s = s + x[3 * k + i] * x[3 * k + j];
+                        mat3[3 * i + j] = s;
+                        mat3[9 + 3 * i + j] = i == j ? 1.0 : 0.0;
+                    }
+            }
+            __syncthreads();
+            if (tid < kWave) jacobi<3>(mat3, lane);
+            __syncthreads();
+            double d3[3], v[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d3[k] = mat3[3 * k + k];
+            const int at3 = smallest<3>(d3);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = mat3[(3 + k) * 3 + at3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                double w = 0.0;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) w = w + x[3 * i + j] * v[j];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    x[3 * i + j] = x[3 * i + j] - w * v[j];
+                    valid = valid && isfinite(x[3 * i + j]);
+                }
+            }
+        }
+        if (!valid) break;
+        mine = 0;
+        for (int i = tid; i < n; i += kRansacThreads) {
+            const bool in = inlier<MODEL>(x, corr[i], a.tt);
+            S2[i] = in ? 1 : 0;
+            mine += in ? 1u : 0u;
+        }
+        const int c = wg_count(mine, &total);
+        if (c < count) break;
+        count = c;
+        cur ^= 1;
+        ++done;
+        if (tid == 0) {  // the accepted model: thread 0 writes it out at the end
+#pragma unroll
+            for (int k = 0; k < 9; ++k) accepted[k] = x[k];
+        }
+    }
+
+    __syncthreads();  // the members other threads wrote
+    const uint8_t *S = mem + cur * a.q_stride;
+    if (a.out_inlier)
+        for (int s = tid; s < nf; s += kRansacThreads) {
+            const int ci = a.cidx[s0 + s];
+            a.out_inlier[s0 + s] = ci >= 0 ? S[ci] : 0;
+        }
+    if (tid != 0) return;
+    // What only this epilogue needs is read from the kernel argument segment here (the argument block is the
+    // kernel's one parameter): named through `g`, the loads sit at the kernel's entry and their scalar
+    // registers stay occupied over the rounds, two of them spilled.
+    typedef const __attribute__((address_space(4))) RefitArgs *late_args;
+    const late_args e = (late_args)__builtin_amdgcn_kernarg_segment_ptr();
+    int32_t *const out_counts = e->r.out_counts, *const out_rounds = e->out_rounds;
+    if (out_counts) out_counts[f] = count;
+    if (out_rounds) out_rounds[f] = done;
+    double *om = e->r.out_model + static_cast<int64_t>(f) * 9;
+    if (done == 0) {  // in_model's bits as they are
+        const unsigned long long *im = reinterpret_cast<const unsigned long long *>(e->in_model) + static_cast<int64_t>(f) * 9;
+        unsigned long long w[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) w[c] = im[c];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) reinterpret_cast<unsigned long long *>(om)[c] = w[c];
+        return;
+    }
+    double xa[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) xa[k] = accepted[k];
+    write_model<MODEL>(xa, e->r.cx, e->r.cy, e->r.scale, om);
 }
 
 }  // namespace
+
+hipError_t launch_ransac_refit(const RefitArgs &a, hipStream_t s) {
+    if (a.r.batch < 1) return hipErrorInvalidValue;
+    const dim3 frames(static_cast<unsigned>(a.r.batch));
+    hipLaunchKernelGGL(k_ransac_compact, frames, dim3(kRansacThreads), 0, s, a.r);
+    if (a.r.model == kFundamental)
+        hipLaunchKernelGGL((k_ransac_refit<0>), frames, dim3(kRansacThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_ransac_refit<1>), frames, dim3(kRansacThreads), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s) {
     const int64_t blocks = static_cast<int64_t>(a.batch) * ((a.hypotheses + kWave - 1) / kWave);

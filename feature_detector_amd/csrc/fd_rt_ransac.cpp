@@ -1,11 +1,51 @@
-// Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac) over the kernels of
-// fd_ransac.hip.
+// Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac) and the least-squares
+// refit of its model (fd_ransac_refit) over the kernels of fd_ransac.hip.
 #include <algorithm>
 #include <cmath>
 
 #include "fd_ctx.h"
 
 using namespace fdrt;
+
+namespace {
+
+// What fd_ransac and fd_ransac_refit ask of the arguments they share.
+int check_pairs(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx, int32_t model,
+                float threshold, float center_x, float center_y, float scale) {
+    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
+    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
+    if (!match_idx && t_stride < q_stride)
+        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
+    if (model != FD_RANSAC_FUNDAMENTAL && model != FD_RANSAC_HOMOGRAPHY)
+        return fail(c, FD_ERR_INVALID, "model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
+    if (!std::isfinite(threshold) || !(threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    if (!std::isfinite(center_x) || !std::isfinite(center_y))
+        return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    return FD_OK;
+}
+
+// The fields both calls fill alike, and the workspace of k_ransac_compact.
+int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_t t_stride, int32_t model, float threshold,
+              float center_x, float center_y, float scale) {
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
+    a.batch = batch;
+    a.q_stride = q_stride;
+    a.t_stride = t_stride;
+    a.model = model;
+    a.cx = static_cast<double>(center_x);
+    a.cy = static_cast<double>(center_y);
+    a.scale = static_cast<double>(scale);
+    const double t = static_cast<double>(threshold) * a.scale;
+    a.tt = t * t;
+    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 4 * qs, a.corr));
+    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
+    FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
+    FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
+    return FD_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -14,21 +54,13 @@ int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_x
               double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xy || !t_xy || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
-    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
-    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
-    if (!match_idx && t_stride < q_stride)
-        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    if (opts->model != FD_RANSAC_FUNDAMENTAL && opts->model != FD_RANSAC_HOMOGRAPHY)
-        return fail(c, FD_ERR_INVALID, "model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
+    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, opts->model, opts->threshold, opts->center_x,
+                         opts->center_y, opts->scale);
+    if (rc) return rc;
     if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
         return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
-    if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0f))
-        return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
-    if (!std::isfinite(opts->center_x) || !std::isfinite(opts->center_y))
-        return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
-    if (!std::isfinite(opts->scale) || !(opts->scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
     FD_HIP_TRY(c, hipSetDevice(c->device));
-    int rc = refuse_sync_under_capture(c, io_on_device);
+    rc = refuse_sync_under_capture(c, io_on_device);
     if (rc) return rc;
     if (q_stride == 0) {  // no slots: no frame has a model
         if (io_on_device) {
@@ -44,22 +76,11 @@ int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_x
     }
     const size_t qs = static_cast<size_t>(batch) * q_stride, ts = static_cast<size_t>(batch) * t_stride;
     fdk::RansacArgs a{};
-    a.batch = batch;
-    a.q_stride = q_stride;
-    a.t_stride = t_stride;
-    a.model = opts->model;
+    rc = pair_args(c, a, batch, q_stride, t_stride, opts->model, opts->threshold, opts->center_x, opts->center_y, opts->scale);
+    if (rc) return rc;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
-    a.cx = static_cast<double>(opts->center_x);
-    a.cy = static_cast<double>(opts->center_y);
-    a.scale = static_cast<double>(opts->scale);
-    const double t = static_cast<double>(opts->threshold) * a.scale;
-    a.tt = t * t;
-    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 4 * qs, a.corr));
-    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
-    FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
     FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 9, a.models));
-    FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
     HostIo io(c, io_on_device);
     FD_HIP_TRY(c, io.in(q_xy, 2 * qs, a.q_xy));
     FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
@@ -71,6 +92,55 @@ int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_x
     FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
     FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
     FD_HIP_TRY(c, fdk::launch_ransac(a, c->stream));
+    return io.finish(q_counts, batch, q_stride);
+}
+
+int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float *q_xy, const int32_t *q_counts,
+                    int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx,
+                    const uint8_t *pair_valid, const double *in_model, const uint8_t *in_inlier, double *out_model,
+                    uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_xy || !t_xy || !in_model || !in_inlier || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
+    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, opts->model, opts->threshold, opts->center_x,
+                         opts->center_y, opts->scale);
+    if (rc) return rc;
+    if (opts->rounds < 1 || opts->rounds > FD_REFIT_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 4]");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    const size_t models = static_cast<size_t>(9) * batch;
+    if (q_stride == 0) {  // no slots: no round is accepted
+        if (io_on_device) {
+            if (out_model != in_model)
+                FD_HIP_TRY(c, hipMemcpyAsync(out_model, in_model, sizeof(double) * models, hipMemcpyDeviceToDevice, c->stream));
+            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+            if (out_rounds) FD_HIP_TRY(c, hipMemsetAsync(out_rounds, 0, sizeof(int32_t) * batch, c->stream));
+        } else {
+            if (out_model != in_model) std::copy(in_model, in_model + models, out_model);
+            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
+            if (out_rounds) std::fill(out_rounds, out_rounds + batch, 0);
+        }
+        return FD_OK;
+    }
+    const size_t qs = static_cast<size_t>(batch) * q_stride, ts = static_cast<size_t>(batch) * t_stride;
+    fdk::RefitArgs g{};
+    rc = pair_args(c, g.r, batch, q_stride, t_stride, opts->model, opts->threshold, opts->center_x, opts->center_y, opts->scale);
+    if (rc) return rc;
+    g.rounds = opts->rounds;
+    FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
+    HostIo io(c, io_on_device);  // 7 inputs and 4 outputs: the whole staging pool
+    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, g.r.q_xy));
+    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, g.r.t_xy));
+    FD_HIP_TRY(c, io.in(q_counts, batch, g.r.q_counts));
+    FD_HIP_TRY(c, io.in(match_idx, qs, g.r.match_idx));
+    FD_HIP_TRY(c, io.in(pair_valid, qs, g.r.pair_valid));
+    FD_HIP_TRY(c, io.in(in_model, models, g.in_model));
+    FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
+    FD_HIP_TRY(c, io.out(out_model, models, g.r.out_model));
+    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, g.r.out_inlier));
+    FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
+    FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
+    FD_HIP_TRY(c, fdk::launch_ransac_refit(g, c->stream));
     return io.finish(q_counts, batch, q_stride);
 }
 

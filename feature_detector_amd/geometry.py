@@ -11,7 +11,7 @@ import ctypes
 from dataclasses import dataclass
 
 from . import _lib
-from ._lib import fd_ransac_opts
+from ._lib import fd_ransac_opts, fd_refit_opts
 from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
@@ -80,3 +80,52 @@ def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: st
                                ptr(om), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return GeometryResult(om, oi, oc, ob)
+
+
+@dataclass
+class RefitResult(GeometryResult):
+    rounds: object = None  # int32 [B]: accepted refit rounds; 0: model and inliers are the given ones
+
+
+def refit_geometry(q_xy, t_xy, result: GeometryResult, matches=None, valid=None, counts=None, model: str = "fundamental",
+                   rounds: int = 2, threshold: float = 1.0, image_size=None, out=None,
+                   ctx: Context | None = None) -> RefitResult:
+    """fd_ransac_refit: the least-squares refit of verify_geometry's model on its inliers, the inliers
+    classified again, up to `rounds` (1..4) times while their number does not fall; a fundamental matrix comes
+    back with rank 2. This is the model to hand to warp_frames.
+
+    q_xy, t_xy, matches, valid, counts, model, threshold and image_size are verify_geometry's: pass the same
+    ones. result: what verify_geometry returned (its model float64 [B, 9] and inliers uint8 [B, S], on the
+    side of q_xy). A frame whose first refit is rejected (too few inliers, a degenerate inlier set, fewer
+    inliers than before) keeps its model bit for bit and has rounds 0.
+
+    Returns a RefitResult: model, inliers, counts as verify_geometry's, best as given, and rounds int32 [B].
+    Host and device inputs and out= (model float64 [B, 9], inliers uint8 [B, S], counts int32 [B], rounds
+    int32 [B]) behave as in verify_geometry; out= may hold result's own model and inliers tensors.
+    """
+    if model not in MODELS:
+        raise ValueError(f"model must be one of {sorted(MODELS)}")
+    on_dev = _is_torch_device_tensor(q_xy)
+    if _is_torch_device_tensor(t_xy) != on_dev or _is_torch_device_tensor(result.model) != on_dev or \
+            _is_torch_device_tensor(result.inliers) != on_dev:
+        raise ValueError("t_xy and result must be on the side (host / device) of q_xy")
+    ctx = _resolve_ctx(ctx, q_xy, t_xy)
+
+    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
+    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
+    if int(pt.shape[0]) != b:
+        raise ValueError("q_xy and t_xy must have the same batch")
+    if matches is None and ts < s:
+        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
+    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
+    cn = slot_arg(counts, "int32", (b,), on_dev)
+    im, ii = slot_arg(result.model, "float64", (b, 9), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
+    om, oi, oc, orr = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
+                              on_dev, pq.device if on_dev else None)
+    (cx, cy), scale = conditioning(image_size)
+    opts = fd_refit_opts(MODELS[model], int(rounds), float(threshold), float(cx), float(cy), float(scale))
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_ransac_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
+                                     ptr(im), ptr(ii), ptr(om), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return RefitResult(om, oi, oc, result.best, orr)

@@ -645,7 +645,7 @@ typedef struct fd_ransac_opts {
  * fd_ransac -- geometric verification of the correspondences of every frame of a batch: the model (F or H)
  * of the minimal sample with the most inliers among a fixed number of hypotheses, and the inlier mask.
  * The stage is an outlier filter whose mask feeds the next call (fd_flow_lk's valid, the prior features of
- * fd_points_detect); the model is the best minimal-sample model, not a refit. The reference has no such
+ * fd_points_detect); the model is the best minimal-sample model (fd_ransac_refit refits it). The reference has no such
  * stage: the contract is this text, a definite sequence. All floating point is double, every operation
  * rounded once, no contraction, f64 division correctly rounded.
  *
@@ -704,6 +704,83 @@ int fd_ransac(fd_ctx *ctx, int batch, const fd_ransac_opts *opts,
               const int32_t *match_idx, const uint8_t *pair_valid,
               double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
               int io_on_device);
+
+#define FD_REFIT_MAX_ROUNDS 4
+/* Jacobi sweeps of fd_ransac_refit. Found on the CPU with the restatement (tests/refit_ref.py): over every
+ * scene of tests/test_refit_host.py and tests/test_gpu_refit.py the eigenvector of the 9 x 9 normal matrix and
+ * the one of F^T F change no bit after 6 sweeps (first-round matrices); the rule adds 2
+ * (tests/test_refit_host.py::test_sweep_count_rule). */
+#define FD_REFIT_SWEEPS 8
+
+typedef struct fd_refit_opts {
+    int32_t model;      /* FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY */
+    int32_t rounds;     /* 1..4 */
+    float threshold;    /* pixels, finite, > 0: fd_ransac's */
+    float center_x, center_y, scale; /* fd_ransac's conditioning transform: pass the same three */
+} fd_refit_opts;
+
+/*
+ * fd_ransac_refit -- the least-squares refit of fd_ransac's model on its inliers: per frame the model that
+ * minimises the algebraic error over the support set, the set classified again, up to `rounds` times while
+ * the inlier count does not fall; F is projected to rank 2. The model a consumer such as fd_frames_warp
+ * should take. A definite sequence like fd_ransac's, with its conventions: all floating point double, every
+ * operation rounded once, no contraction, f64 division and square root correctly rounded.
+ *
+ * q_xy, q_counts, q_stride, t_xy, t_stride, match_idx, pair_valid: fd_ransac's, and the correspondence list
+ * 0..n-1 with its conditioned coordinates (x, y, u, v) is fd_ransac's. in_model double [batch][9] and
+ * in_inlier uint8 [batch][q_stride]: fd_ransac's out_model and out_inlier.
+ *
+ * Support set. S_0 = the correspondences whose in_inlier byte is exactly 1; c_0 = |S_0|.
+ *
+ * Round r = 1..rounds:
+ * 1. Fit from S_(r-1). Invalid when |S| < 4 (H) or 8 (F). Normal matrix N (9 x 9) = sum over the support of
+ *    row^T row with fd_ransac's rows, one per correspondence for F, two for H. Only the 45 entries (a, b),
+ *    a <= b, are summed, each by acc = acc + row[a] * row[b], then mirrored. Order: partial L = 0..255 starts
+ *    from 0.0 and takes the list positions i = L, L + 256, ... in ascending i, skipping those not in S; for H
+ *    the first row's product is added, then the second's. The partials are combined by the tree
+ *    P[L] = P[L] + P[L + step] for all L < step, with step = 128, 64, ..., 1; N is P[0].
+ * 2. Eigenvector by cyclic Jacobi on A = N (n = 9) with V = identity, FD_REFIT_SWEEPS sweeps, each visiting
+ *    the pairs (p, q), p < q, in row-major order. A pair with A[p][q] == 0.0 is skipped. Otherwise, with
+ *    app, aqq, apq the entries before the rotation:
+ *      theta = (aqq - app) / (2.0 * apq);  t = (theta < 0 ? -1.0 : 1.0) / (|theta| + sqrt(theta*theta + 1.0))
+ *      c = 1.0 / sqrt(t*t + 1.0);  s = t * c
+ *    and every new element is an expression of the elements before the rotation:
+ *      for k != p, q:  A[k][p] = A[p][k] = c*A[k][p] - s*A[k][q];   A[k][q] = A[q][k] = s*A[k][p] + c*A[k][q]
+ *      A[p][p] = app - t*apq;  A[q][q] = aqq + t*apq;  A[p][q] = A[q][p] = 0.0
+ *      for every k:    V[k][p] = c*V[k][p] - s*V[k][q];             V[k][q] = s*V[k][p] + c*V[k][q]
+ *    (each product rounded, then the sum or difference). The solution is column j of V, j the index of the
+ *    smallest diagonal entry of A (strict < from entry 0: the lowest index among equals). The fit is invalid
+ *    for a non-finite entry of that column, and unless d2 > 1e-12 * dmax, d2 the smallest diagonal entry apart
+ *    from entry j and dmax the largest (a NaN fails): a support set that leaves more than one direction free
+ *    (collinear points for H, a pure translation for F) has no refit.
+ * 3. F only, rank 2. G = F^T F, G[i][j] = sum over k ascending from 0.0 of F[k][i] * F[k][j]; the same Jacobi
+ *    routine with n = 3 on G; v = the column of V at G's smallest diagonal entry; w[i] = sum over j ascending
+ *    from 0.0 of F[i][j] * v[j]; F[i][j] = F[i][j] - w[i] * v[j]. A non-finite entry makes the fit invalid.
+ * 4. Classify every correspondence of the list, not only the support, by fd_ransac's inlier test with the new
+ *    model and t = (double)threshold * (double)scale: S_r, c_r = |S_r|.
+ * 5. Guard: the round is accepted iff the fit is valid and c_r >= c_(r-1). Otherwise the loop stops and the
+ *    state of the last accepted round stands.
+ *
+ * Outputs. out_model double [batch][9]: the model of the last accepted round, denormalised and divided by
+ * its entry of largest magnitude exactly as fd_ransac's; with no accepted round the nine doubles of in_model,
+ * bit for bit. out_inlier uint8 [batch][q_stride] (NULL to skip): 1 for the members of the last accepted
+ * round's S (of S_0 with none: a member's byte becomes exactly 1), 0 for every other slot below q_counts[b];
+ * slots >= q_counts[b] are not written. out_counts [batch] (NULL to skip): |S|. out_rounds int32 [batch]
+ * (NULL to skip): the accepted rounds, 0..rounds. out_model may be in_model and out_inlier may be in_inlier.
+ * q_stride 0: out_model = in_model, out_counts = 0, out_rounds = 0.
+ *
+ * Device pointers when io_on_device: asynchronous on the context's stream (k_ransac_compact and one more
+ * kernel), graph-capturable once a first call of the shape has sized the workspace. Host pointers otherwise:
+ * staged through context buffers, complete on return.
+ * FD_ERR_INVALID: fd_ransac's conditions; rounds outside 1..4; in_model or in_inlier NULL.
+ */
+int fd_ransac_refit(fd_ctx *ctx, int batch, const fd_refit_opts *opts,
+                    const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+                    const float *t_xy, int32_t t_stride,
+                    const int32_t *match_idx, const uint8_t *pair_valid,
+                    const double *in_model, const uint8_t *in_inlier,
+                    double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
+                    int io_on_device);
 
 /* ---- Image warp by a homography or a camera model (MI355X extension) --------------------------------- */
 #define FD_WARP_HOMOGRAPHY 0 /* params: double[9], row-major 3 x 3, fd_ransac's out_model layout */

@@ -59,6 +59,19 @@ public:
                 const std::vector<int32_t> *train_index = nullptr, const std::vector<uint8_t> *valid = nullptr,
                 std::array<double, 9> *model = nullptr, int32_t *best_hypothesis = nullptr);
 
+    // Refits Verify's model on its inliers by least squares (fd_ransac_refit of include/fd_hip.h): up to
+    // `rounds` (1..4) times the model is fitted to the inliers and the inliers are classified again, while
+    // their number does not fall; a fundamental matrix comes back with rank 2. query_uv, train_uv,
+    // train_index and valid are what Verify took; inlier and model are what it returned and receive the
+    // result. accepted_rounds (optional): the rounds taken; with 0 (too few or degenerate inliers, or fewer
+    // inliers than before) model keeps its bits and inlier its members.
+    // False for no query points, an inlier, train_index or valid of the wrong size, fewer train than query
+    // points without train_index, options or rounds out of range, or a libfdhip failure (last_error()); inlier
+    // and model are then left as given.
+    bool Refit(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, std::vector<uint8_t> &inlier,
+               std::array<double, 9> &model, int32_t rounds = 2, const std::vector<int32_t> *train_index = nullptr,
+               const std::vector<uint8_t> *valid = nullptr, int32_t *accepted_rounds = nullptr);
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
