@@ -19,7 +19,7 @@ EXPORTS = (
     "fd_ctx_get_stream",
     "fd_ctx_synchronize", "fd_ctx_reserve", "fd_ctx_stage", "fd_ctx_set_tie_order", "fd_ctx_frame_status", "fd_points_detect", "fd_points_candidates", "fd_points_response",
     "fd_points_response_append", "fd_points_select",
-    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_frames_warp", "fd_frames_equalize", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
+    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_brief_match_model", "fd_nn_match_model", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_frames_warp", "fd_frames_equalize", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
     "fd_nn_bias_relu", "fd_nn_conv3x3_c1", "fd_nn_conv3x3_c64",
     "fd_nn_heat_softmax", "fd_nn_desc_normalize",
     "fd_build_info", "fd_abi_version", "fd_png_info", "fd_png_decode", "fd_png_frames",
@@ -70,6 +70,11 @@ class fd_nn_match_opts(ctypes.Structure):
 
 class fd_match_gate(ctypes.Structure):
     _fields_ = [("radius_x", ctypes.c_float), ("radius_y", ctypes.c_float)]
+
+
+class fd_match_model_gate(ctypes.Structure):
+    _fields_ = [("model", ctypes.c_int32), ("threshold", ctypes.c_float), ("radius_x", ctypes.c_float),
+                ("radius_y", ctypes.c_float)]
 
 
 class fd_flow_opts(ctypes.Structure):
@@ -162,6 +167,10 @@ def load() -> ctypes.CDLL:
                                         P, P, P, P, i32, P, P, P, P, i32]),
         "fd_nn_match_guided": (i32, [P, i32, ctypes.POINTER(fd_nn_match_opts), ctypes.POINTER(fd_match_gate), P, P, P, i32,
                                      P, P, P, P, i32, P, P, P, P, i32]),
+        "fd_brief_match_model": (i32, [P, i32, ctypes.POINTER(fd_match_opts), ctypes.POINTER(fd_match_model_gate), P, P, P, P,
+                                       i32, P, P, P, P, i32, P, P, P, P, i32]),
+        "fd_nn_match_model": (i32, [P, i32, ctypes.POINTER(fd_nn_match_opts), ctypes.POINTER(fd_match_model_gate), P, P, P, P,
+                                    i32, P, P, P, P, i32, P, P, P, P, i32]),
         "fd_pyr_layout": (i32, [i32, i32, i32, i32, ctypes.POINTER(i64)]),
         "fd_pyr_build": (i32, [P, P, i32, i32, i32, i32, i32, P, i32]),
         "fd_flow_lk": (i32, [P, i32, i32, i32, i32, ctypes.POINTER(fd_flow_opts), P, P, P, P, P, i32, P, P, P, P, P, i32]),

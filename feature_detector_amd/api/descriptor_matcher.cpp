@@ -2,6 +2,7 @@
 // One call matches every query descriptor against every train descriptor in one kernel launch (two with
 // the cross-check). NNDescriptorMatcher: the same over fd_nn_match for float descriptors (squared L2).
 // MatchGuided of both: the same call through the guided entry points, with the keypoint positions.
+// MatchModel of both: the same through the model-gated entry points, with the positions and a 3 x 3 model.
 #include "feature_detector/descriptor_matcher.h"
 
 #include <cmath>
@@ -26,6 +27,7 @@ bool Pack(const std::vector<BriefType> &descriptors, size_t length, std::vector<
 }
 
 bool BadRadius(float r) { return !std::isfinite(r) || r < 0.0f; }
+bool BadThreshold(float t) { return !std::isfinite(t) || t <= 0.0f; }
 
 }  // namespace
 
@@ -44,11 +46,26 @@ bool BriefMatcher::MatchGuided(const std::vector<BriefType> &query, const std::v
     return Run(query, train, &query_uv, &train_uv, radius_x, radius_y, train_index, distance, query_valid, train_valid);
 }
 
-// query_uv / train_uv null: Match; else MatchGuided
+bool BriefMatcher::MatchModel(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                              const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, const double model[9],
+                              MatchModelKind kind, float threshold, std::vector<int32_t> &train_index,
+                              std::vector<int32_t> *distance, const std::vector<uint8_t> *query_valid,
+                              const std::vector<uint8_t> *train_valid, float radius_x, float radius_y) {
+    if (!model || BadThreshold(threshold)) {
+        train_index.assign(query.size(), -1);
+        if (distance) distance->assign(query.size(), -1);
+        return context_.Fail("MatchModel: a model and a finite threshold > 0 are needed");
+    }
+    return Run(query, train, &query_uv, &train_uv, radius_x, radius_y, train_index, distance, query_valid, train_valid, model,
+               kind, threshold);
+}
+
+// query_uv / train_uv null: Match; else MatchGuided, or with a model MatchModel
 bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
                        const std::vector<Vec2> *query_uv, const std::vector<Vec2> *train_uv, float radius_x, float radius_y,
                        std::vector<int32_t> &train_index, std::vector<int32_t> *distance,
-                       const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+                       const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid, const double *model,
+                       MatchModelKind kind, float threshold) {
     train_index.assign(query.size(), -1);
     if (distance) distance->assign(query.size(), -1);
     if (query.empty() || train.empty()) return context_.Fail("Match: empty input");
@@ -71,8 +88,13 @@ bool BriefMatcher::Run(const std::vector<BriefType> &query, const std::vector<Br
     if (query_uv) {
         const std::vector<float> qxy = Flatten(*query_uv), txy = Flatten(*train_uv);
         const fd_match_gate gate{radius_x, radius_y};
-        rc = fd_brief_match_guided(ctx, 1, &o, &gate, q.data(), qv, nullptr, nq, qxy.data(), t.data(), tv, nullptr, nt,
-                                   txy.data(), train_index.data(), dist.data(), nullptr, 0);
+        const fd_match_model_gate mgate{static_cast<int32_t>(kind), threshold, radius_x, radius_y};
+        if (model)
+            rc = fd_brief_match_model(ctx, 1, &o, &mgate, model, q.data(), qv, nullptr, nq, qxy.data(), t.data(), tv, nullptr,
+                                      nt, txy.data(), train_index.data(), dist.data(), nullptr, 0);
+        else
+            rc = fd_brief_match_guided(ctx, 1, &o, &gate, q.data(), qv, nullptr, nq, qxy.data(), t.data(), tv, nullptr, nt,
+                                       txy.data(), train_index.data(), dist.data(), nullptr, 0);
     } else {
         rc = fd_brief_match(ctx, 1, &o, q.data(), qv, nullptr, nq, t.data(), tv, nullptr, nt, train_index.data(),
                             dist.data(), nullptr, 0);
@@ -103,10 +125,26 @@ bool NNDescriptorMatcher::MatchGuided(const float *query, int32_t n_query, const
                query_valid, train_valid);
 }
 
+bool NNDescriptorMatcher::MatchModel(const float *query, int32_t n_query, const float *query_xy, const float *train,
+                                     int32_t n_train, const float *train_xy, int32_t dim, const double model[9],
+                                     MatchModelKind kind, float threshold, std::vector<int32_t> &train_index,
+                                     std::vector<float> *distance, const std::vector<uint8_t> *query_valid,
+                                     const std::vector<uint8_t> *train_valid, float radius_x, float radius_y) {
+    if (!model || BadThreshold(threshold)) {
+        const size_t nq = n_query > 0 ? static_cast<size_t>(n_query) : 0;
+        train_index.assign(nq, -1);
+        if (distance) distance->assign(nq, -1.0f);
+        return context_.Fail("MatchModel: a model and a finite threshold > 0 are needed");
+    }
+    return Run(query, n_query, query_xy, train, n_train, train_xy, dim, true, radius_x, radius_y, train_index, distance,
+               query_valid, train_valid, model, kind, threshold);
+}
+
 bool NNDescriptorMatcher::Run(const float *query, int32_t n_query, const float *query_xy, const float *train,
                               int32_t n_train, const float *train_xy, int32_t dim, bool guided, float radius_x,
                               float radius_y, std::vector<int32_t> &train_index, std::vector<float> *distance,
-                              const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid) {
+                              const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid,
+                              const double *model, MatchModelKind kind, float threshold) {
     const size_t nq = n_query > 0 ? static_cast<size_t>(n_query) : 0;
     train_index.assign(nq, -1);
     if (distance) distance->assign(nq, -1.0f);
@@ -122,7 +160,11 @@ bool NNDescriptorMatcher::Run(const float *query, int32_t n_query, const float *
     std::vector<float> dist(2 * nq, -1.0f);
     const uint8_t *qv = query_valid ? query_valid->data() : nullptr, *tv = train_valid ? train_valid->data() : nullptr;
     int rc;
-    if (guided) {
+    if (guided && model) {
+        const fd_match_model_gate mgate{static_cast<int32_t>(kind), threshold, radius_x, radius_y};
+        rc = fd_nn_match_model(ctx, 1, &o, &mgate, model, query, qv, nullptr, n_query, query_xy, train, tv, nullptr, n_train,
+                               train_xy, train_index.data(), dist.data(), nullptr, 0);
+    } else if (guided) {
         const fd_match_gate gate{radius_x, radius_y};
         rc = fd_nn_match_guided(ctx, 1, &o, &gate, query, qv, nullptr, n_query, query_xy, train, tv, nullptr, n_train,
                                 train_xy, train_index.data(), dist.data(), nullptr, 0);

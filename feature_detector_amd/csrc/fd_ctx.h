@@ -63,12 +63,13 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a guided match (8 inputs, 3 outputs) and fd_ransac_refit (7 and 4)
-    static constexpr int kStaging = 11;
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest call is a model-gated match (9 inputs, 3 outputs)
+    static constexpr int kStaging = 12;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
-    // fd_nn_match's norms of both sets ([batch][q_stride], then [batch][t_stride])
-    fdrt::DevBuf m_rev, m_norm;
+    // fd_nn_match's norms of both sets ([batch][q_stride], then [batch][t_stride]); the model-gated matchers' gate
+    // vectors of both sets ([batch][q_stride][4] doubles, then [batch][t_stride][4])
+    fdrt::DevBuf m_rev, m_norm, m_gate;
     // fd_flow_lk: the backward pass's results ([batch][stride] positions and status)
     fdrt::DevBuf f_bxy, f_bst;
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every

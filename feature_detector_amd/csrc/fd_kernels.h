@@ -294,7 +294,9 @@ constexpr uint32_t kCountMask = 0x01FFFFFFu;
 // frame. Forward pass: a = query, b = train. Cross-check's reverse pass: a = train, b = query, out_idx =
 // the reverse table, no other output and no test. Guided matching (fd_*_match_guided): with a_xy / b_xy
 // set, a "b" entry is a candidate of an "a" entry only inside the window |dx| <= radius_x, |dy| <= radius_y
-// (the reverse pass swaps the two position arrays with the sets; the gate is symmetric).
+// (the reverse pass swaps the two position arrays with the sets; the gate is symmetric). Model-gated
+// matching (fd_*_match_model): with a_gate / b_gate set as well, a candidate must also pass the model test
+// of fd_match_gate.h on the two entries' gate vectors (the reverse pass swaps them and flips a_is_query).
 struct MatchCommon {
     const int32_t *a_counts;  // [batch] or null (= a_stride); bits 25..31 ignored
     const int32_t *b_counts;  // the same of the searched set
@@ -306,6 +308,22 @@ struct MatchCommon {
     const float *a_xy;    // [batch][a_stride][2] (x, y), or null (both null: no gate)
     const float *b_xy;    // [batch][b_stride][2]
     float radius_x, radius_y;  // the window's half-width / half-height (unused without a gate)
+    const double *a_gate;  // [batch][a_stride][4] gate vectors (k_match_gate_vectors), or null (both null: no model)
+    const double *b_gate;  // [batch][b_stride][4]
+    double gate_tt;        // the model gate's t*t
+    int gate_model;        // FD_RANSAC_FUNDAMENTAL (0) or FD_RANSAC_HOMOGRAPHY (1)
+    int a_is_query;        // the "a" set is the query set (forward pass)
+};
+
+// The model gate's pre-pass: the gate vector (fd_match_gate.h) of every slot of both sets, side 0 the query
+// set, side 1 the train set.
+struct MatchGateArgs {
+    const float *xy[2];   // [batch][stride[i]][2]
+    double *out[2];       // [batch][stride[i]][4]
+    int stride[2];
+    int batch, model;     // FD_RANSAC_FUNDAMENTAL (0) or FD_RANSAC_HOMOGRAPHY (1)
+    const double *m;      // [batch][9], row-major 3 x 3
+    double tt;            // t*t
 };
 
 // Hamming matcher (fd_match.hip).
@@ -525,6 +543,7 @@ hipError_t launch_lsd_count(const LsdArgs &a, hipStream_t s);    // compact mode
 hipError_t launch_lsd_scatter(const LsdArgs &a, hipStream_t s);  // compact mode: the lists
 hipError_t launch_brief(const BriefArgs &a, hipStream_t s);
 hipError_t launch_brief_match(const MatchArgs &a, hipStream_t s);
+hipError_t launch_match_gate_vectors(const MatchGateArgs &a, hipStream_t s);
 hipError_t launch_nn_norms(NnNormArgs a, hipStream_t s);
 hipError_t launch_nn_match(NnMatchArgs a, hipStream_t s);
 hipError_t launch_heat_candidates(const HeatArgs &a, hipStream_t s);

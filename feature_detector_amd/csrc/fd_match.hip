@@ -29,7 +29,14 @@
 // broadcast), and a pair outside the window takes the invalid entry's route: its popcount sum starts at
 // kInvalidPenalty. Per pair that is two subtractions, two compares and a select; the update and the merge
 // do not know of it. |b - a| has the same bits as |a - b|, so the reverse pass decides on the same pairs.
+//
+// The model instances (fd_brief_match_model; kGateF, kGateHFwd, kGateHRev of fd_match_gate.h) add the
+// epipolar band or the transfer disc to the window. k_match_gate_vectors (below) first writes four doubles
+// per entry of both sets; a lane keeps its own entry's four in registers, a tile's go to LDS beside the
+// positions (8 KiB, the same broadcast read), and a failing pair takes the same route as one outside the
+// window. Per pair that is 8 (F) or 7 (H) double operations and a compare.
 #include "fd_match_common.h"
+#include "fd_match_gate.h"
 
 namespace fdk {
 namespace {
@@ -41,12 +48,16 @@ constexpr int kInvalidPenalty = 1 << 20;
 constexpr int kAbsent = 0x7FFFFFFF;
 
 // NW: descriptor words held per lane and per LDS row (words above ceil(length / 32) are zero).
-// GATED: only "b" entries inside the lane's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y).
-template <int NW, bool GATED>
+// GATE (fd_match_gate.h): from kGateWindow on only "b" entries inside the lane's window are candidates
+// (a.a_xy, a.b_xy, a.radius_x / _y), from kGateF on only those that pass the model test as well (a.a_gate,
+// a.b_gate, a.gate_tt).
+template <int NW, int GATE>
 __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
+    constexpr bool GATED = GATE != kGateNone, MODEL = GATE >= kGateF;
     __shared__ __attribute__((aligned(16))) uint32_t tile[kMatchTile * NW];
     __shared__ uint32_t pen[kMatchTile];
     __shared__ float bxy[GATED ? 2 * kMatchTile : 1];
+    __shared__ __attribute__((aligned(16))) double bgv[MODEL ? 4 * kMatchTile : 2];
     __shared__ int32_t part[3][kMatchWaves - 1][kWave];
     const int tiles = (a.a_stride + kWave - 1) / kWave;
     const int f = static_cast<int>(blockIdx.x) / tiles;
@@ -76,6 +87,15 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
         }
         bp = a.b_xy + static_cast<int64_t>(f) * a.b_stride * 2;
     }
+    double ag[4] = {0.0, 0.0, 0.0, 0.0};
+    const double *bg = nullptr;
+    if constexpr (MODEL) {
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ag[k] = a.a_gate[4 * aslot + k];
+        }
+        bg = a.b_gate + static_cast<int64_t>(f) * a.b_stride * 4;
+    }
     const uint32_t *bb = a.b_bits + static_cast<int64_t>(f) * a.b_stride * nw;
     const uint8_t *bv = a.b_valid ? a.b_valid + static_cast<int64_t>(f) * a.b_stride : nullptr;
     int best = kAbsent, second = kAbsent, bidx = -1;
@@ -94,6 +114,10 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
             for (int i = static_cast<int>(threadIdx.x); i < 2 * n; i += kMatchThreads)
                 bxy[i] = bp[static_cast<int64_t>(t0) * 2 + i];
         }
+        if constexpr (MODEL) {
+            for (int i = static_cast<int>(threadIdx.x); i < 4 * n; i += kMatchThreads)
+                bgv[i] = bg[static_cast<int64_t>(t0) * 4 + i];
+        }
         __syncthreads();
 #pragma unroll 2
         for (int j = wave; j < n; j += kMatchWaves) {
@@ -102,6 +126,10 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
                 // one subtraction and one inclusive compare per axis; a NaN fails both
                 const bool in = fabsf(bxy[2 * j] - ax) <= a.radius_x && fabsf(bxy[2 * j + 1] - ay) <= a.radius_y;
                 d = in ? d : static_cast<uint32_t>(kInvalidPenalty);
+            }
+            if constexpr (MODEL) {
+                const double og[4] = {bgv[4 * j], bgv[4 * j + 1], bgv[4 * j + 2], bgv[4 * j + 3]};
+                d = model_pass<GATE>(ag, og, a.gate_tt) ? d : static_cast<uint32_t>(kInvalidPenalty);
             }
 #pragma unroll
             for (int w = 0; w < NW; ++w) d += static_cast<uint32_t>(__popc(qw[w] ^ tile[j * NW + w]));
@@ -137,10 +165,56 @@ __global__ __launch_bounds__(kMatchThreads) void k_brief_match(MatchArgs a) {
 
 template <int NW>
 void launch_nw(const MatchArgs &a, unsigned blocks, hipStream_t s) {
-    if (a.a_xy)
-        hipLaunchKernelGGL((k_brief_match<NW, true>), dim3(blocks), dim3(kMatchThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL((k_brief_match<NW, false>), dim3(blocks), dim3(kMatchThreads), 0, s, a);
+    switch (gate_of(a)) {
+        case kGateNone: hipLaunchKernelGGL((k_brief_match<NW, kGateNone>), dim3(blocks), dim3(kMatchThreads), 0, s, a); break;
+        case kGateWindow: hipLaunchKernelGGL((k_brief_match<NW, kGateWindow>), dim3(blocks), dim3(kMatchThreads), 0, s, a); break;
+        case kGateF: hipLaunchKernelGGL((k_brief_match<NW, kGateF>), dim3(blocks), dim3(kMatchThreads), 0, s, a); break;
+        case kGateHFwd: hipLaunchKernelGGL((k_brief_match<NW, kGateHFwd>), dim3(blocks), dim3(kMatchThreads), 0, s, a); break;
+        default: hipLaunchKernelGGL((k_brief_match<NW, kGateHRev>), dim3(blocks), dim3(kMatchThreads), 0, s, a); break;
+    }
+}
+
+// The gate vector of every slot of both sets (side 0: query, side 1: train), one lane per slot. Slots past a
+// frame's count get one too (their positions are read, whatever they hold): the matchers never read it.
+__global__ __launch_bounds__(256) void k_match_gate_vectors(MatchGateArgs a) {
+    const int64_t n0 = static_cast<int64_t>(a.batch) * a.stride[0], n1 = static_cast<int64_t>(a.batch) * a.stride[1];
+    int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n0 + n1) return;
+    const int side = i >= n0;
+    if (side) i -= n0;
+    const double *M = a.m + 9 * (i / a.stride[side]);
+    const double x = static_cast<double>(a.xy[side][2 * i]), y = static_cast<double>(a.xy[side][2 * i + 1]);
+    double v0, v1, v2, v3;
+    if (a.model == 0) {
+        if (side == 0) {
+            v0 = (M[0] * x + M[1] * y) + M[2];
+            v1 = (M[3] * x + M[4] * y) + M[5];
+            v2 = (M[6] * x + M[7] * y) + M[8];
+            v3 = v0 * v0 + v1 * v1;
+        } else {
+            const double m0 = (M[0] * x + M[3] * y) + M[6];
+            const double m1 = (M[1] * x + M[4] * y) + M[7];
+            v0 = x;
+            v1 = y;
+            v2 = 1.0;
+            v3 = m0 * m0 + m1 * m1;
+        }
+    } else if (side == 0) {
+        v0 = (M[0] * x + M[1] * y) + M[2];
+        v1 = (M[3] * x + M[4] * y) + M[5];
+        v2 = (M[6] * x + M[7] * y) + M[8];
+        v3 = a.tt * (v2 * v2);
+    } else {
+        v0 = x;
+        v1 = y;
+        v2 = 0.0;
+        v3 = 0.0;
+    }
+    double *o = a.out[side] + 4 * i;
+    o[0] = v0;
+    o[1] = v1;
+    o[2] = v2;
+    o[3] = v3;
 }
 
 }  // namespace
@@ -159,6 +233,15 @@ hipError_t launch_brief_match(const MatchArgs &a, hipStream_t s) {
         launch_nw<4>(a, g, s);
     else
         launch_nw<8>(a, g, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_gate_vectors(const MatchGateArgs &a, hipStream_t s) {
+    const int64_t total = static_cast<int64_t>(a.batch) * (static_cast<int64_t>(a.stride[0]) + a.stride[1]);
+    if (total == 0) return hipSuccess;
+    const int64_t blocks = (total + 255) / 256;
+    if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_match_gate_vectors, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -30,7 +30,16 @@
 // positions of its four rows (8 registers), a tile's TB "b" positions go to LDS beside bnorm, and a pair
 // outside the window gets d = +inf where an invalid column already does, after the MFMA chain, which the
 // gate does not touch.
+//
+// The model instances (fd_nn_match_model; kGateF, kGateHFwd, kGateHRev of fd_match_gate.h) add the model
+// test on the gate vectors of k_match_gate_vectors (fd_match.hip). Four rows of four doubles per lane do not
+// fit beside the A fragments (the K = 256 window instance already sits at the 128 registers of 4 waves per
+// SIMD), so the workgroup's 64 "a" vectors and positions go to LDS once (2.5 KiB) and a tile's TB "b" vectors
+// beside the positions (TB * 32 bytes); a pair reads both from there (lanes that share a row or a column read the same
+// address). The test runs per tile ahead of the MFMA chain, one bit per pair into a mask register, and a
+// failing pair gets d = +inf like one outside the window.
 #include "fd_match_common.h"
+#include "fd_match_gate.h"
 
 namespace fdk {
 namespace {
@@ -71,16 +80,22 @@ __global__ __launch_bounds__(256) void k_nn_norms(NnNormArgs a) {
 }
 
 // K: the instance's descriptor length (dim zero-padded up to it: fmaf(0, 0, acc) leaves acc unchanged);
-// TB: "b" rows per LDS tile (TB / 16 independent accumulators per wave); GATED: only "b" rows inside a
-// row's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y).
+// TB: "b" rows per LDS tile (TB / 16 independent accumulators per wave); GATE (fd_match_gate.h): from
+// kGateWindow on only "b" rows inside a row's window are candidates (a.a_xy, a.b_xy, a.radius_x / _y), from
+// kGateF on only those that pass the model test as well (a.a_gate, a.b_gate, a.gate_tt).
 // The gated instances ask for the ungated ones' 4 waves per SIMD (the LDS tile's limit): unasked, the
-// K = 256 one takes 132 registers and drops to 3.
-template <int K, int TB, bool GATED>
-__global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATED ? 4 : 1))) void k_nn_match(NnMatchArgs a) {
+// K = 256 one takes 132 registers and drops to 3. The model instances ask for 3: capped at the 128 registers
+// of 4 they spill a few loop-invariant addresses (4 to 14 registers too many), which they must not.
+template <int K, int TB, int GATE>
+__global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE >= kGateF ? 3 : GATE != kGateNone ? 4 : 1))) void k_nn_match(NnMatchArgs a) {
+    constexpr bool GATED = GATE != kGateNone, MODEL = GATE >= kGateF;
     constexpr int P = K + 4, NS = K / 4, NJ = TB / 16, C4 = K / 4;
     __shared__ __attribute__((aligned(16))) float tile[TB * P];
     __shared__ float bnorm[TB];
     __shared__ __attribute__((aligned(8))) float bxy[GATED ? 2 * TB : 2];
+    __shared__ __attribute__((aligned(16))) double agv[MODEL ? 4 * kNnRows : 2];
+    __shared__ __attribute__((aligned(8))) float axy[MODEL ? 2 * kNnRows : 2];
+    __shared__ __attribute__((aligned(16))) double bgv[MODEL ? 4 * TB : 2];
     const int tiles = (a.a_stride + kNnRows - 1) / kNnRows;
     const int f = static_cast<int>(blockIdx.x) / tiles;
     const int q0 = (static_cast<int>(blockIdx.x) - f * tiles) * kNnRows;
@@ -110,7 +125,7 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
     for (int r = 0; r < 4; ++r) {
         const int row = q0 + 16 * wave + 4 * g + r;
         an[r] = row < na ? a.a_norm[static_cast<int64_t>(f) * a.a_stride + row] : inf;
-        if constexpr (GATED) {
+        if constexpr (GATED && !MODEL) {
             const float *ap = a.a_xy + (static_cast<int64_t>(f) * a.a_stride + min(row, na - 1)) * 2;
             ax[r] = ap[0];
             ay[r] = ap[1];
@@ -123,6 +138,13 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
     const float *bf = a.b_desc + static_cast<int64_t>(f) * a.b_stride * a.dim;
     const float *bnf = a.b_norm + static_cast<int64_t>(f) * a.b_stride;
     const float *bpf = GATED ? a.b_xy + static_cast<int64_t>(f) * a.b_stride * 2 : nullptr;
+    const double *bgf = MODEL ? a.b_gate + static_cast<int64_t>(f) * a.b_stride * 4 : nullptr;
+    if constexpr (MODEL) {  // (the first tile's barriers order these stores before the first read; nb == 0 reads none)
+        const int64_t row0 = static_cast<int64_t>(f) * a.a_stride + q0;
+        const int rows = min(kNnRows, na - q0);
+        if (static_cast<int>(threadIdx.x) < 4 * rows) agv[threadIdx.x] = a.a_gate[4 * row0 + threadIdx.x];
+        if (static_cast<int>(threadIdx.x) < 2 * rows) axy[threadIdx.x] = a.a_xy[2 * row0 + threadIdx.x];
+    }
     for (int t0 = 0; t0 < nb; t0 += TB) {
         const int n = min(TB, nb - t0);
         __syncthreads();  // every wave is done with the previous tile
@@ -137,7 +159,28 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
         if constexpr (GATED) {  // (positions past the fill stay stale: their norm is +inf)
             if (static_cast<int>(threadIdx.x) < 2 * n) bxy[threadIdx.x] = bpf[static_cast<int64_t>(t0) * 2 + threadIdx.x];
         }
+        if constexpr (MODEL) {  // (likewise stale past the fill)
+            if (static_cast<int>(threadIdx.x) < 4 * n) bgv[threadIdx.x] = bgf[static_cast<int64_t>(t0) * 4 + threadIdx.x];
+        }
         __syncthreads();
+        // the window and the model test of the lane's 4 x NJ pairs, before the MFMA chain (while no accumulator
+        // is live): bit 4j + r for row r against column 16j + c. One row at a time keeps the doubles few.
+        uint32_t pass = 0u;
+        if constexpr (MODEL) {
+#pragma unroll 1
+            for (int r = 0; r < 4; ++r) {
+                const double *ap = agv + 4 * (16 * wave + 4 * g + r);
+                const double ag[4] = {ap[0], ap[1], ap[2], ap[3]};
+                const float rx = axy[2 * (16 * wave + 4 * g + r)], ry = axy[2 * (16 * wave + 4 * g + r) + 1];
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const double *bp = bgv + 4 * (16 * j + c);
+                    const double og[4] = {bp[0], bp[1], bp[2], bp[3]};
+                    const bool in = fabsf(bxy[2 * (16 * j + c)] - rx) <= a.radius_x && fabsf(bxy[2 * (16 * j + c) + 1] - ry) <= a.radius_y;
+                    pass |= (in && model_pass<GATE>(ag, og, a.gate_tt) ? 1u : 0u) << (4 * j + r);
+                }
+            }
+        }
         f4 acc[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[j] = f4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -155,7 +198,7 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
             const bool ok = bn < inf;
             const int col = t0 + 16 * j + c;
             float bx = 0.0f, by = 0.0f;
-            if constexpr (GATED) {
+            if constexpr (GATED && !MODEL) {
                 bx = bxy[2 * (16 * j + c)];
                 by = bxy[2 * (16 * j + c) + 1];
             }
@@ -163,11 +206,12 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
             for (int r = 0; r < 4; ++r) {
                 float d = fmaxf(0.0f, (an[r] + bn) - 2.0f * acc[j][r]);
                 d = ok ? d : inf;
-                if constexpr (GATED) {
+                if constexpr (GATED && !MODEL) {
                     // one subtraction and one inclusive compare per axis; a NaN fails both
                     const bool in = fabsf(bx - ax[r]) <= a.radius_x && fabsf(by - ay[r]) <= a.radius_y;
                     d = in ? d : inf;
                 }
+                if constexpr (MODEL) d = ((pass >> (4 * j + r)) & 1u) ? d : inf;
                 // the serial scan: a new best moves the old best to second, else d may lower second;
                 // a NaN compares false both times
                 const bool lt = d < best[r];
@@ -215,6 +259,17 @@ __global__ __launch_bounds__(kNnThreads) __attribute__((amdgpu_waves_per_eu(GATE
     match_emit(a, f, q, aslot, live, has1, has2, d1, d2, has1 ? bi : -1, d1 < (a.max_ratio * a.max_ratio) * d2);
 }
 
+template <int K, int TB>
+void launch_k(const NnMatchArgs &a, unsigned blocks, hipStream_t s) {
+    switch (gate_of(a)) {
+        case kGateNone: hipLaunchKernelGGL((k_nn_match<K, TB, kGateNone>), dim3(blocks), dim3(kNnThreads), 0, s, a); break;
+        case kGateWindow: hipLaunchKernelGGL((k_nn_match<K, TB, kGateWindow>), dim3(blocks), dim3(kNnThreads), 0, s, a); break;
+        case kGateF: hipLaunchKernelGGL((k_nn_match<K, TB, kGateF>), dim3(blocks), dim3(kNnThreads), 0, s, a); break;
+        case kGateHFwd: hipLaunchKernelGGL((k_nn_match<K, TB, kGateHFwd>), dim3(blocks), dim3(kNnThreads), 0, s, a); break;
+        default: hipLaunchKernelGGL((k_nn_match<K, TB, kGateHRev>), dim3(blocks), dim3(kNnThreads), 0, s, a); break;
+    }
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -235,17 +290,10 @@ hipError_t launch_nn_match(NnMatchArgs a, hipStream_t s) {
     if (blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
     a.b_vec = aligned16(a.b_desc);
     const unsigned g = static_cast<unsigned>(blocks);
-    if (a.dim <= 128) {
-        if (a.a_xy)
-            hipLaunchKernelGGL((k_nn_match<128, 64, true>), dim3(g), dim3(kNnThreads), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_nn_match<128, 64, false>), dim3(g), dim3(kNnThreads), 0, s, a);
-    } else {
-        if (a.a_xy)
-            hipLaunchKernelGGL((k_nn_match<256, 32, true>), dim3(g), dim3(kNnThreads), 0, s, a);
-        else
-            hipLaunchKernelGGL((k_nn_match<256, 32, false>), dim3(g), dim3(kNnThreads), 0, s, a);
-    }
+    if (a.dim <= 128)
+        launch_k<128, 64>(a, g, s);
+    else
+        launch_k<256, 32>(a, g, s);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // Host runtime of libfdhip.so: the descriptor matchers. fd_brief_match (Hamming, fd_match.hip) and
-// fd_nn_match (squared L2, fd_nn_match.hip) and their guided entries are one driver, run_match; what a
+// fd_nn_match (squared L2, fd_nn_match.hip) and their guided and model-gated entries are one driver, run_match; what a
 // matcher brings of its own (option checks, bytes per descriptor slot, its argument fields, the NN norms
 // pre-pass) is a traits struct, BriefMatch / NnMatch.
 #include <algorithm>
@@ -79,13 +79,15 @@ struct NnMatch {
     static hipError_t launch(const Args &a, hipStream_t s) { return fdk::launch_nn_match(a, s); }
 };
 
-// The cross-check's reverse pass of the forward arguments: the sets change roles (the gate is symmetric),
-// the reverse table is the only output and nothing is tested.
+// The cross-check's reverse pass of the forward arguments: the sets change roles (the window is symmetric;
+// the model gate is told which set is the query), the reverse table is the only output and nothing is tested.
 template <class M>
 typename M::Args swapped(typename M::Args a, int32_t *rev) {
     std::swap(a.a_counts, a.b_counts);
     std::swap(a.a_stride, a.b_stride);
     std::swap(a.a_xy, a.b_xy);
+    std::swap(a.a_gate, a.b_gate);
+    a.a_is_query = !a.a_is_query;
     M::swap_sets(a);
     a.out_idx = rev;
     a.out_dist = nullptr;
@@ -105,6 +107,16 @@ int check_gate(fd_ctx *c, const fd_match_gate *gate, const float *q_xy, const fl
     return FD_OK;
 }
 
+// The model-gated matchers' arguments (mg null: another entry, nothing to check); its radii are check_gate's.
+int check_model_gate(fd_ctx *c, const fd_match_model_gate *mg, const double *model) {
+    if (!mg) return FD_OK;
+    if (!model) return fail(c, FD_ERR_INVALID, "model is NULL");
+    if (mg->model != FD_RANSAC_FUNDAMENTAL && mg->model != FD_RANSAC_HOMOGRAPHY)
+        return fail(c, FD_ERR_INVALID, "gate model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
+    if (!std::isfinite(mg->threshold) || mg->threshold <= 0.0f) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    return FD_OK;
+}
+
 // One set's arrays as the kernels take them: the caller's device pointers, or their staged copies.
 hipError_t stage_side(HostIo &io, Side &s, size_t slot_bytes, size_t slots, int batch) {
     const uint8_t *desc = static_cast<const uint8_t *>(s.desc);
@@ -119,14 +131,22 @@ hipError_t stage_side(HostIo &io, Side &s, size_t slot_bytes, size_t slots, int 
 // A matcher call. With cross_check the kernel runs twice, first with the roles swapped into the reverse
 // table (the best query of every train descriptor), then forward, where it applies the tests, the reverse
 // table among them; out_counts is zeroed on the stream before it. gate (with q.xy, t.xy) is the guided
-// entries' window, null for the unguided ones.
+// entries' window, null for the unguided ones. mg (with model, [batch][9]) is the model-gated entries' gate,
+// whose radii are the window then: k_match_gate_vectors first writes both sets' gate vectors into workspace.
 template <class M>
-int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match_gate *gate, Side q, Side t,
-              int32_t *out_idx, decltype(M::Args::out_dist) out_dist, int32_t *out_counts, int io_on_device) {
+int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match_gate *gate, const fd_match_model_gate *mg,
+              const double *model, Side q, Side t, int32_t *out_idx, decltype(M::Args::out_dist) out_dist,
+              int32_t *out_counts, int io_on_device) {
     const int32_t *host_counts = q.counts;  // (q and t are staged below)
     if (!opts || !q.desc || !t.desc || !out_idx) return fail(c, FD_ERR_INVALID, "bad arguments");
+    fd_match_gate window{};
+    if (mg) {
+        window = {mg->radius_x, mg->radius_y};
+        gate = &window;
+    }
     int rc = check_gate(c, gate, q.xy, t.xy);
     if (rc) return rc;
+    if ((rc = check_model_gate(c, mg, model))) return rc;
     if (batch < 1 || q.stride < 0 || t.stride < 0) return fail(c, FD_ERR_INVALID, "need batch >= 1 and strides >= 0");
     if ((rc = M::check(c, *opts))) return rc;
     FD_HIP_TRY(c, hipSetDevice(c->device));
@@ -137,6 +157,7 @@ int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match
     HostIo io(c, io_on_device);
     FD_HIP_TRY(c, stage_side(io, q, M::slot_bytes(*opts), qslots, batch));
     FD_HIP_TRY(c, stage_side(io, t, M::slot_bytes(*opts), tslots, batch));
+    if (mg) FD_HIP_TRY(c, io.in(model, static_cast<size_t>(batch) * 9, model));
     FD_HIP_TRY(c, io.out_slots(out_idx, qslots, 1, a.out_idx));
     FD_HIP_TRY(c, io.out_slots(out_dist, qslots, 2, a.out_dist));
     FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
@@ -146,11 +167,23 @@ int run_match(fd_ctx *c, int batch, const typename M::Opts *opts, const fd_match
     a.b_stride = t.stride;
     a.batch = batch;
     a.max_ratio = opts->max_ratio;
+    a.a_is_query = 1;
     if (gate) {
         a.a_xy = q.xy;
         a.b_xy = t.xy;
         a.radius_x = gate->radius_x;
         a.radius_y = gate->radius_y;
+    }
+    if (mg) {
+        double *vec = nullptr;
+        FD_HIP_TRY(c, ensure_as(c, c->m_gate, 4 * (qslots + tslots), vec));
+        const double th = static_cast<double>(mg->threshold);
+        a.a_gate = vec;
+        a.b_gate = vec + 4 * qslots;
+        a.gate_tt = th * th;
+        a.gate_model = mg->model;
+        const fdk::MatchGateArgs ga{{q.xy, t.xy}, {vec, vec + 4 * qslots}, {q.stride, t.stride}, batch, mg->model, model, a.gate_tt};
+        FD_HIP_TRY(c, fdk::launch_match_gate_vectors(ga, c->stream));
     }
     if ((rc = M::bind(c, a, *opts, q, t))) return rc;
     if (opts->cross_check && t.stride > 0) {
@@ -173,7 +206,7 @@ int fd_brief_match(fd_ctx *c, int batch, const fd_match_opts *opts, const uint32
                    const int32_t *t_counts, int32_t t_stride, int32_t *out_idx, int32_t *out_dist, int32_t *out_counts,
                    int io_on_device) {
     if (!c) return FD_ERR_INVALID;
-    return run_match<BriefMatch>(c, batch, opts, nullptr, {q_bits, q_valid, q_counts, q_stride, nullptr},
+    return run_match<BriefMatch>(c, batch, opts, nullptr, nullptr, nullptr, {q_bits, q_valid, q_counts, q_stride, nullptr},
                                  {t_bits, t_valid, t_counts, t_stride, nullptr}, out_idx, out_dist, out_counts, io_on_device);
 }
 
@@ -184,7 +217,7 @@ int fd_brief_match_guided(fd_ctx *c, int batch, const fd_match_opts *opts, const
                           int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!gate) return fail(c, FD_ERR_INVALID, "gate is NULL");
-    return run_match<BriefMatch>(c, batch, opts, gate, {q_bits, q_valid, q_counts, q_stride, q_xy},
+    return run_match<BriefMatch>(c, batch, opts, gate, nullptr, nullptr, {q_bits, q_valid, q_counts, q_stride, q_xy},
                                  {t_bits, t_valid, t_counts, t_stride, t_xy}, out_idx, out_dist, out_counts, io_on_device);
 }
 
@@ -193,7 +226,7 @@ int fd_nn_match(fd_ctx *c, int batch, const fd_nn_match_opts *opts, const float 
                 const int32_t *t_counts, int32_t t_stride, int32_t *out_idx, float *out_dist, int32_t *out_counts,
                 int io_on_device) {
     if (!c) return FD_ERR_INVALID;
-    return run_match<NnMatch>(c, batch, opts, nullptr, {q_desc, q_valid, q_counts, q_stride, nullptr},
+    return run_match<NnMatch>(c, batch, opts, nullptr, nullptr, nullptr, {q_desc, q_valid, q_counts, q_stride, nullptr},
                               {t_desc, t_valid, t_counts, t_stride, nullptr}, out_idx, out_dist, out_counts, io_on_device);
 }
 
@@ -203,7 +236,29 @@ int fd_nn_match_guided(fd_ctx *c, int batch, const fd_nn_match_opts *opts, const
                        const float *t_xy, int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!gate) return fail(c, FD_ERR_INVALID, "gate is NULL");
-    return run_match<NnMatch>(c, batch, opts, gate, {q_desc, q_valid, q_counts, q_stride, q_xy},
+    return run_match<NnMatch>(c, batch, opts, gate, nullptr, nullptr, {q_desc, q_valid, q_counts, q_stride, q_xy},
+                              {t_desc, t_valid, t_counts, t_stride, t_xy}, out_idx, out_dist, out_counts, io_on_device);
+}
+
+int fd_brief_match_model(fd_ctx *c, int batch, const fd_match_opts *opts, const fd_match_model_gate *gate,
+                         const double *model, const uint32_t *q_bits, const uint8_t *q_valid, const int32_t *q_counts,
+                         int32_t q_stride, const float *q_xy, const uint32_t *t_bits, const uint8_t *t_valid,
+                         const int32_t *t_counts, int32_t t_stride, const float *t_xy, int32_t *out_idx, int32_t *out_dist,
+                         int32_t *out_counts, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!gate) return fail(c, FD_ERR_INVALID, "gate is NULL");
+    return run_match<BriefMatch>(c, batch, opts, nullptr, gate, model, {q_bits, q_valid, q_counts, q_stride, q_xy},
+                                 {t_bits, t_valid, t_counts, t_stride, t_xy}, out_idx, out_dist, out_counts, io_on_device);
+}
+
+int fd_nn_match_model(fd_ctx *c, int batch, const fd_nn_match_opts *opts, const fd_match_model_gate *gate,
+                      const double *model, const float *q_desc, const uint8_t *q_valid, const int32_t *q_counts,
+                      int32_t q_stride, const float *q_xy, const float *t_desc, const uint8_t *t_valid,
+                      const int32_t *t_counts, int32_t t_stride, const float *t_xy, int32_t *out_idx, float *out_dist,
+                      int32_t *out_counts, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!gate) return fail(c, FD_ERR_INVALID, "gate is NULL");
+    return run_match<NnMatch>(c, batch, opts, nullptr, gate, model, {q_desc, q_valid, q_counts, q_stride, q_xy},
                               {t_desc, t_valid, t_counts, t_stride, t_xy}, out_idx, out_dist, out_counts, io_on_device);
 }
 

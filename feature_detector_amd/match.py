@@ -6,7 +6,9 @@ the same [batch][stride] layouts, so a detect -> describe -> match chain stays o
 the same stage after nn_descriptors / nn_select_list. The semantics (validity, ties, the three acceptance tests) are in include/fd_hip.h.
 
 Both take an optional search window (q_xy, t_xy, radius): guided matching over fd_brief_match_guided /
-fd_nn_match_guided, where a train keypoint is a candidate of a query only within radius pixels of it.
+fd_nn_match_guided, where a train keypoint is a candidate of a query only within radius pixels of it. With a
+two-view model (model, model_kind, threshold) the pair must agree with it as well: the second, model-gated
+matching pass over fd_brief_match_model / fd_nn_match_model.
 """
 from __future__ import annotations
 
@@ -16,7 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_match_gate, fd_match_opts, fd_nn_match_opts
+from ._lib import fd_match_gate, fd_match_model_gate, fd_match_opts, fd_nn_match_opts
+from .geometry import MODELS, GeometryResult
 from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
@@ -28,18 +31,43 @@ class MatchResult:
     counts: object  # int32 [B]: accepted matches per frame
 
 
-def _guided(q_xy, t_xy, radius) -> bool:
-    """Whether the call is the guided one: all three given; none given is the unguided call."""
+OPEN_RADIUS = 3.0e38  # a window that holds every finite position
+
+
+def _guided(q_xy, t_xy, radius, model=None, model_kind="fundamental") -> bool:
+    """Whether the call is the guided one: all three given; none given is the unguided call. With a model
+    the positions are needed and radius is optional."""
+    if model is not None:
+        if q_xy is None or t_xy is None:
+            raise ValueError("model-gated matching needs q_xy and t_xy")
+        if model_kind not in MODELS:
+            raise ValueError(f"model_kind must be one of {sorted(MODELS)}")
+        return True
     given = [x is not None for x in (q_xy, t_xy, radius)]
     if any(given) and not all(given):
         raise ValueError("guided matching needs q_xy, t_xy and radius together")
     return all(given)
 
 
-def _gate(q_xy, t_xy, radius, on_dev, b, sq, st):
-    """The guided call's (gate, q_xy, t_xy), or None for the unguided call."""
-    if not _guided(q_xy, t_xy, radius):
+def _gate(q_xy, t_xy, radius, on_dev, b, sq, st, model=None, model_kind="fundamental", threshold=1.0):
+    """The guided call's (gate, q_xy, t_xy), the model-gated call's (gate, q_xy, t_xy, model), or None for the
+    unguided call."""
+    if not _guided(q_xy, t_xy, radius, model, model_kind):
         return None
+    if model is not None:
+        if isinstance(model, GeometryResult):
+            model = model.model
+        if _is_torch_device_tensor(model) != on_dev:
+            raise ValueError("model must be on the side (host / device) of the descriptors")
+        if not on_dev:
+            model = np.asarray(model)
+        if str(model.dtype).split(".")[-1] != "float64":
+            raise TypeError("model must be float64")
+        if tuple(int(d) for d in model.shape) not in (((b, 9),) + (((9,),) if b == 1 else ())):
+            raise ValueError(f"model must be [{b}, 9]" + (" or [9]" if b == 1 else ""))
+        model = model.contiguous() if on_dev else np.ascontiguousarray(model)
+        if radius is None:
+            radius = OPEN_RADIUS
     try:
         rx, ry = (float(r) for r in radius)
     except TypeError:
@@ -53,6 +81,8 @@ def _gate(q_xy, t_xy, radius, on_dev, b, sq, st):
         if tuple(int(d) for d in p.shape) != (b, s, 2):
             raise ValueError(msg)
         sides.append(p)
+    if model is not None:
+        return fd_match_model_gate(MODELS[model_kind], float(threshold), rx, ry), sides[0], sides[1], model
     return fd_match_gate(rx, ry), sides[0], sides[1]
 
 
@@ -73,7 +103,8 @@ def _side(x, valid, counts, on_dev, name, check):
 
 def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg=None):
     """What both matchers end with: the outputs (dist: the distances' dtype name; out: the caller's tensors,
-    checked against their shapes), then the entry point `entry`, or with a gate `entry`_guided."""
+    checked against their shapes), then the entry point `entry`, or with a gate `entry`_guided, or with a
+    gate that carries a model `entry`_model."""
     (qx, qv, qc, b, sq), (tx, tv, tc, _, st) = q, t
     specs = (((b, sq), "int32", -1), ((b, sq, 2), dist, -1), ((b,), "int32", 0))
     idx, dst, counts = outputs(specs, out, on_dev, qx.device if on_dev else None,
@@ -83,6 +114,9 @@ def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg=None):
     qa, ta = (ptr(qx), ptr(qv), ptr(qc), sq), (ptr(tx), ptr(tv), ptr(tc), st)
     if gate is None:
         rc = getattr(_lib.load(), entry)(*head, *qa, *ta, *outs)
+    elif len(gate) == 4:
+        rc = getattr(_lib.load(), entry + "_model")(*head, ctypes.byref(gate[0]), ptr(gate[3]), *qa, ptr(gate[1]), *ta,
+                                                    ptr(gate[2]), *outs)
     else:
         rc = getattr(_lib.load(), entry + "_guided")(*head, ctypes.byref(gate[0]), *qa, ptr(gate[1]), *ta, ptr(gate[2]),
                                                      *outs)
@@ -92,7 +126,8 @@ def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg=None):
 
 def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_valid=None, length: int = 256,
                 max_distance: int = -1, max_ratio: float = 0.0, cross_check: bool = False, out=None,
-                ctx: Context | None = None, q_xy=None, t_xy=None, radius=None) -> MatchResult:
+                ctx: Context | None = None, q_xy=None, t_xy=None, radius=None, model=None,
+                model_kind: str = "fundamental", threshold: float = 1.0) -> MatchResult:
     """fd_brief_match for a batch: frame b of the query set against frame b of the train set.
 
     q_bits / t_bits: int32 or uint32 words [B, S, ceil(length/32)] or [S, words] (batch 1), as
@@ -107,8 +142,14 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     1) on the descriptors' side, as detect_points leaves them, and radius, a float or an (rx, ry) pair:
     train entry j is a candidate of query i only if |t_xy[j] - q_xy[i]| <= radius on both axes. Give all
     three or none.
+
+    Model-gated matching (fd_brief_match_model): model, float64 [B, 9] (or [9] for batch 1) on the
+    descriptors' side, or the GeometryResult of verify_geometry / refit_geometry; model_kind "fundamental" or
+    "homography"; threshold in pixels. Train entry j is then a candidate of query i only if the pair passes
+    the model's Sampson (F) or forward transfer (H) test, and the window if radius is given (None: open).
+    q_xy and t_xy are required. A frame whose model is all zeros (no model) is gated by the window alone.
     """
-    _guided(q_xy, t_xy, radius)
+    _guided(q_xy, t_xy, radius, model, model_kind)
     ctx = _resolve_ctx(ctx, q_bits, t_bits)
     nw = (int(length) + 31) // 32 if 1 <= int(length) <= 256 else 0
     opts = fd_match_opts(int(length), int(max_distance), float(max_ratio), 1 if cross_check else 0)
@@ -128,14 +169,14 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     t = _side(t_bits, t_valid, t_counts, on_dev, "t", check)
     if t[3] != q[3]:
         raise ValueError("q_bits and t_bits must have the same batch")
-    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4])
+    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4], model, model_kind, threshold)
     return _run(ctx, "fd_brief_match", opts, q, t, gate, on_dev, "int32", out,
                 "out must be contiguous int32 tensors of shapes {}, {}, {}")
 
 
 def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid=None, max_distance: float = -1.0,
              max_ratio: float = 0.0, cross_check: bool = False, out=None, ctx: Context | None = None, q_xy=None,
-             t_xy=None, radius=None) -> MatchResult:
+             t_xy=None, radius=None, model=None, model_kind: str = "fundamental", threshold: float = 1.0) -> MatchResult:
     """fd_nn_match for a batch: frame b of the query set against frame b of the train set, squared L2.
 
     q_desc / t_desc: float32 [B, S, dim] or [S, dim] (batch 1), as nn_descriptors / nn_select_list return
@@ -143,9 +184,10 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
     out= are as in brief_match, except that dist (and out's dist tensor) is float32 [B, Sq, 2]: squared
     distances, -1.0 where absent. max_distance bounds the squared distance; max_ratio is Lowe's ratio of
     distances (applied squared to the squared distances). q_xy, t_xy and radius give the guided call
-    (fd_nn_match_guided), as in brief_match.
+    (fd_nn_match_guided), and model, model_kind and threshold the model-gated call (fd_nn_match_model), as in
+    brief_match.
     """
-    _guided(q_xy, t_xy, radius)
+    _guided(q_xy, t_xy, radius, model, model_kind)
     ctx = _resolve_ctx(ctx, q_desc, t_desc)
     on_dev = _is_torch_device_tensor(q_desc)
     if on_dev != _is_torch_device_tensor(t_desc):
@@ -165,5 +207,5 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
     if int(t[0].shape[2]) != dim:
         raise ValueError("q_desc and t_desc must have the same dim")
     opts = fd_nn_match_opts(dim, float(max_distance), float(max_ratio), 1 if cross_check else 0)
-    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4])
+    gate = _gate(q_xy, t_xy, radius, on_dev, q[3], q[4], t[4], model, model_kind, threshold)
     return _run(ctx, "fd_nn_match", opts, q, t, gate, on_dev, "float32", out)

@@ -442,6 +442,70 @@ int fd_nn_match_guided(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts, con
                        const float *t_xy,
                        int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
 
+/* ---- Model-gated matching: an epipolar or homography gate for both matchers (MI355X extension) ------- */
+typedef struct fd_match_model_gate {
+    int32_t model;      /* FD_RANSAC_FUNDAMENTAL (0) or FD_RANSAC_HOMOGRAPHY (1), defined with fd_ransac below */
+    float   threshold;  /* pixels, finite, > 0 */
+    float   radius_x, radius_y; /* fd_match_gate's window, applied as well; 3.0e38f leaves it open */
+} fd_match_model_gate;
+
+/*
+ * fd_brief_match_model / fd_nn_match_model -- fd_brief_match_guided / fd_nn_match_guided with a second gate,
+ * the two-view model of the frame: the second matching pass of a front end that has estimated F or H
+ * (search by epipolar line, guided matching). A train keypoint is a candidate of a query only if the pair
+ * agrees with the model, so matches come back that the ratio test and the cross-check rejected while the
+ * whole frame competed.
+ * model: double [batch][9], row-major 3 x 3 in pixel coordinates, one per frame: out_model of fd_ransac or
+ * fd_ransac_refit as it is (a device pointer when io_on_device, so verify -> refit -> rematch needs no
+ * synchronisation). q_xy / t_xy and every other argument are the guided entries'.
+ *
+ * The gate, a definite sequence: all of it double, every operation rounded once, no contraction. With
+ * (x, y) = (double)q_xy[i], (u, v) = (double)t_xy[j], M the frame's nine doubles and t = (double)threshold,
+ * train entry j is a candidate of query i iff the window test of fd_match_gate holds with radius_x / radius_y
+ * (exactly as in the guided entries) and the model test holds:
+ *   F:  l0 = (M0*x + M1*y) + M2;  l1 = (M3*x + M4*y) + M5;  l2 = (M6*x + M7*y) + M8
+ *       m0 = (M0*u + M3*v) + M6;  m1 = (M1*u + M4*v) + M7
+ *       e = (u*l0 + v*l1) + l2
+ *       candidate iff e*e <= (t*t) * ((l0*l0 + l1*l1) + (m0*m0 + m1*m1))            (the Sampson test)
+ *   H (query -> train, fd_ransac's direction):
+ *       px = (M0*x + M1*y) + M2;  py = (M3*x + M4*y) + M5;  w = (M6*x + M7*y) + M8
+ *       dx = px - u*w;  dy = py - v*w
+ *       candidate iff dx*dx + dy*dy <= (t*t) * (w*w)                                 (the forward transfer test)
+ * The grouping (l0*l0 + l1*l1) + (m0*m0 + m1*m1) lets each side's half be computed once per entry. It is
+ * not fd_ransac's left-to-right sum, and the gate works on pixel coordinates where fd_ransac works on
+ * conditioned ones: the gate is fd_ransac's inlier test mathematically, not bit for bit.
+ * A NaN fails the compare, so a position or a model entry that is not finite yields no candidate (a frame
+ * whose model holds a NaN matches nothing). A frame whose model is nine zeros ("no model", as fd_ransac
+ * writes it) passes every pair of finite positions (0 <= 0): that frame falls back to the window alone, and
+ * with both radii 3.0e38f to the unguided call.
+ * The cross-check's reverse search evaluates the same expressions on the same operands: a pair is always
+ * (query, train), whichever set is searched, so the gate has the same bits in both directions and the
+ * cross-check stays decided on the pairs of the forward search. For H the reverse search therefore uses the
+ * forward transfer predicate, not the inverse homography.
+ * Everything else is the guided entries' contract over "valid train descriptors that pass the gate": the best
+ * distance with the lowest train index on ties, the second distance (-1 with fewer than two candidates, and
+ * the ratio test is then skipped), no candidate giving out_idx -1 and both distances -1, max_distance, the
+ * ratio formulas, out_counts, the unwritten slots >= q_counts[b], the zero-stride cases, host staging against
+ * device pointers, and graph capture once a first call of the shape has sized the workspace (the gate
+ * vectors of both sets, 32 bytes per slot, beside the guided entries' workspace).
+ * FD_ERR_INVALID: whatever the guided entry rejects (gate->radius_x / radius_y are its radii); model NULL;
+ * gate->model outside {0, 1}; a threshold that is not finite or is <= 0.
+ */
+int fd_brief_match_model(fd_ctx *ctx, int batch, const fd_match_opts *opts, const fd_match_model_gate *gate,
+                         const double *model,
+                         const uint32_t *q_bits, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                         const float *q_xy,
+                         const uint32_t *t_bits, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                         const float *t_xy,
+                         int32_t *out_idx, int32_t *out_dist, int32_t *out_counts, int io_on_device);
+int fd_nn_match_model(fd_ctx *ctx, int batch, const fd_nn_match_opts *opts, const fd_match_model_gate *gate,
+                      const double *model,
+                      const float *q_desc, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                      const float *q_xy,
+                      const float *t_desc, const uint8_t *t_valid, const int32_t *t_counts, int32_t t_stride,
+                      const float *t_xy,
+                      int32_t *out_idx, float *out_dist, int32_t *out_counts, int io_on_device);
+
 /* ---- Image pyramid and pyramidal Lucas-Kanade tracking (MI355X extension) --------------------------- */
 #define FD_PYR_MAX_LEVELS 6
 

@@ -6,7 +6,8 @@
 // descriptor is neither matched nor a candidate, and a best match is reported only if it passes the
 // enabled tests of Options. MatchGuided adds the tracker's search window (fd_brief_match_guided): a train
 // descriptor is a candidate of a query only if its keypoint lies within (radius_x, radius_y) pixels of the
-// query's.
+// query's. MatchModel adds a two-view model (fd_brief_match_model): a train descriptor is a candidate only if
+// the pair of keypoints passes the fundamental matrix's Sampson test or the homography's transfer test.
 #ifndef FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
 #define FEATURE_DETECTOR_DESCRIPTOR_MATCHER_H_
 
@@ -18,6 +19,11 @@
 #include "device_context.h"
 
 namespace feature_detector {
+
+// The model kinds of MatchModel (FD_RANSAC_FUNDAMENTAL / FD_RANSAC_HOMOGRAPHY of include/fd_hip.h).
+enum class MatchModelKind : int32_t { kFundamental = 0, kHomography = 1 };
+// A window radius that holds every finite position: MatchModel's default, the model gate alone.
+constexpr float kOpenMatchRadius = 3.0e38f;
 
 /* Class BriefMatcher Declaration. */
 class BriefMatcher {
@@ -54,6 +60,19 @@ public:
                      std::vector<int32_t> &train_index, std::vector<int32_t> *distance = nullptr,
                      const std::vector<uint8_t> *query_valid = nullptr, const std::vector<uint8_t> *train_valid = nullptr);
 
+    // Match under a two-view model, the second pass after the model is known: train[j] is a candidate of
+    // query[i] only if the pair (query_uv[i], train_uv[j]) passes the model test of fd_brief_match_model (the
+    // Sampson test of a fundamental matrix, the query -> train transfer test of a homography; `threshold` in
+    // pixels) and MatchGuided's window (open by default). model: row-major 3 x 3 in pixel coordinates, as
+    // fd_ransac / fd_ransac_refit write it; nine zeros (no model) leave the window alone. Outputs and the
+    // return value are MatchGuided's; also false for a null model or a threshold that is not finite and > 0.
+    bool MatchModel(const std::vector<BriefType> &query, const std::vector<BriefType> &train,
+                    const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, const double model[9],
+                    MatchModelKind kind, float threshold, std::vector<int32_t> &train_index,
+                    std::vector<int32_t> *distance = nullptr, const std::vector<uint8_t> *query_valid = nullptr,
+                    const std::vector<uint8_t> *train_valid = nullptr, float radius_x = kOpenMatchRadius,
+                    float radius_y = kOpenMatchRadius);
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -63,9 +82,11 @@ public:
     const std::string &last_error() const { return context_.last_error(); }
 
 private:
+    // model null: Match / MatchGuided
     bool Run(const std::vector<BriefType> &query, const std::vector<BriefType> &train, const std::vector<Vec2> *query_uv,
              const std::vector<Vec2> *train_uv, float radius_x, float radius_y, std::vector<int32_t> &train_index,
-             std::vector<int32_t> *distance, const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid);
+             std::vector<int32_t> *distance, const std::vector<uint8_t> *query_valid, const std::vector<uint8_t> *train_valid,
+             const double *model = nullptr, MatchModelKind kind = MatchModelKind::kFundamental, float threshold = 0.0f);
 
 private:
     Options options_;
@@ -109,6 +130,13 @@ public:
                      std::vector<float> *distance = nullptr, const std::vector<uint8_t> *query_valid = nullptr,
                      const std::vector<uint8_t> *train_valid = nullptr);
 
+    // Match under a two-view model (fd_nn_match_model), as BriefMatcher::MatchModel.
+    bool MatchModel(const float *query, int32_t n_query, const float *query_xy, const float *train, int32_t n_train,
+                    const float *train_xy, int32_t dim, const double model[9], MatchModelKind kind, float threshold,
+                    std::vector<int32_t> &train_index, std::vector<float> *distance = nullptr,
+                    const std::vector<uint8_t> *query_valid = nullptr, const std::vector<uint8_t> *train_valid = nullptr,
+                    float radius_x = kOpenMatchRadius, float radius_y = kOpenMatchRadius);
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -118,10 +146,12 @@ public:
     const std::string &last_error() const { return context_.last_error(); }
 
 private:
+    // model null: Match / MatchGuided
     bool Run(const float *query, int32_t n_query, const float *query_xy, const float *train, int32_t n_train,
              const float *train_xy, int32_t dim, bool guided, float radius_x, float radius_y,
              std::vector<int32_t> &train_index, std::vector<float> *distance, const std::vector<uint8_t> *query_valid,
-             const std::vector<uint8_t> *train_valid);
+             const std::vector<uint8_t> *train_valid, const double *model = nullptr,
+             MatchModelKind kind = MatchModelKind::kFundamental, float threshold = 0.0f);
 
 private:
     Options options_;
