@@ -19,7 +19,7 @@ EXPORTS = (
     "fd_ctx_get_stream",
     "fd_ctx_synchronize", "fd_ctx_reserve", "fd_ctx_stage", "fd_ctx_set_tie_order", "fd_ctx_frame_status", "fd_points_detect", "fd_points_candidates", "fd_points_response",
     "fd_points_response_append", "fd_points_select",
-    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_brief_match_model", "fd_nn_match_model", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_frames_warp", "fd_frames_equalize", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
+    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_brief_match_model", "fd_nn_match_model", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_frames_warp", "fd_frames_equalize", "fd_blur_taps", "fd_frames_blur", "fd_pyr_build_gauss", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
     "fd_nn_bias_relu", "fd_nn_conv3x3_c1", "fd_nn_conv3x3_c64",
     "fd_nn_heat_softmax", "fd_nn_desc_normalize",
     "fd_build_info", "fd_abi_version", "fd_png_info", "fd_png_decode", "fd_png_frames",
@@ -112,6 +112,13 @@ class fd_equalize_opts(ctypes.Structure):
     _fields_ = [("tiles_x", ctypes.c_int32), ("tiles_y", ctypes.c_int32), ("clip_milli", ctypes.c_int32)]
 
 
+FD_BLUR_MAX_RADIUS = 15
+
+
+class fd_blur_opts(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_int32), ("taps", ctypes.c_int32 * 16), ("step", ctypes.c_int32)]
+
+
 class fd_line_desc_opts(ctypes.Structure):
     _fields_ = [("bands", ctypes.c_int32), ("band_width", ctypes.c_int32)]
 
@@ -179,6 +186,9 @@ def load() -> ctypes.CDLL:
         "fd_ransac_refit": (i32, [P, i32, ctypes.POINTER(fd_refit_opts), P, P, i32, P, i32, P, P, P, P, P, P, P, P, i32]),
         "fd_frames_warp": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_warp_opts), P, i32, i32, i32, P, P, i32]),
         "fd_frames_equalize": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_equalize_opts), P, i32]),
+        "fd_blur_taps": (i32, [ctypes.c_double, i32, ctypes.POINTER(fd_blur_opts)]),
+        "fd_frames_blur": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_blur_opts), P, i32]),
+        "fd_pyr_build_gauss": (i32, [P, P, i32, i32, i32, i32, i32, P, i32]),
         "fd_lines_describe": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_line_desc_opts), P, i32, P, i32, P, P, P, i32]),
         "fd_nn_select": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_nn_opts), P, P, P, i32, P, i32]),
         "fd_nn_select_list": (i32, [P, P, P, P, i64, i32, i32, i32, i32, ctypes.POINTER(fd_nn_opts), P, P, P, i32, P,

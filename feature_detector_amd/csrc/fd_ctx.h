@@ -232,6 +232,9 @@ int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device);
 // k_flow_finish after zeroing its counts (fd_flow_lk, fd_points_refine).
 int finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin);
 
+// fd_blur_opts as fd_frames_blur checks them, into the kernel's radius, step and taps (fd_rt_blur.cpp).
+int blur_options(fd_ctx *c, const fd_blur_opts &o, fdk::BlurArgs &a);
+
 // Host threads of the line stage and the PNG decoder (OMP_NUM_THREADS caps, FD_LINE_THREADS overrides).
 int default_line_threads();
 

@@ -491,6 +491,21 @@ struct EqualizeArgs {
     int lanes_log2, chunks, row_split;  // launch_equalize's: lanes per tile row, workgroup columns per row, workgroups per row cell
 };
 
+// Separable integer smoothing (fd_blur.hip; fd_frames_blur and fd_pyr_build_gauss of include/fd_hip.h).
+constexpr int kBlurTileCols = 128;  // output columns of a workgroup's tile
+constexpr int kBlurTileRows = 32;   // output rows of a tile (16 or 8 at small launches: launch_blur)
+struct BlurArgs {
+    const uint8_t *frames;       // [batch][rows][cols], any byte alignment
+    uint8_t *out;                // [batch][out_rows][out_cols], any byte alignment; must not be frames
+    int batch, rows, cols;
+    // the rows and columns stored: ((rows | cols) + step - 1) / step, or fewer (the pyramid's floor dimensions
+    // crop the last row and column of an odd level)
+    int out_rows, out_cols;
+    int radius, step;            // 0..15; 1 or 2
+    int taps[16];                // w[0..radius]; launch_blur zeroes the rest (an instance may run a wider loop)
+    int tile_rows, chunks;       // launch_blur's: output rows per workgroup, workgroup columns per output row
+};
+
 // Line band descriptor (fd_line_desc.hip; fd_lines_describe of include/fd_hip.h).
 struct LineDescArgs {
     const uint8_t *frames;   // [batch][rows][cols]
@@ -507,6 +522,8 @@ struct LineDescArgs {
 hipError_t launch_line_desc(const LineDescArgs &a, hipStream_t s);
 // the three kernels of fd_frames_equalize, in order
 hipError_t launch_equalize(EqualizeArgs a, hipStream_t s);
+// k_blur, one launch (out_rows or out_cols 0: none)
+hipError_t launch_blur(BlurArgs a, hipStream_t s);
 hipError_t launch_warp(WarpArgs a, hipStream_t s);
 // the three kernels of fd_ransac, in order
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);

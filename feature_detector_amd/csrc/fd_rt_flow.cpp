@@ -1,5 +1,5 @@
-// Host runtime of libfdhip.so: the image pyramid (fd_pyr_layout, fd_pyr_build) and the pyramidal
-// Lucas-Kanade tracker (fd_flow_lk) over the kernels of fd_flow.hip.
+// Host runtime of libfdhip.so: the image pyramids (fd_pyr_layout, fd_pyr_build, fd_pyr_build_gauss) and the pyramidal
+// Lucas-Kanade tracker (fd_flow_lk) over the kernels of fd_flow.hip (and k_blur of fd_blur.hip: the Gaussian levels).
 #include <algorithm>
 #include <cmath>
 
@@ -23,6 +23,55 @@ bool pyr_offsets(int batch, int rows, int cols, int levels, int64_t *off) {
     return true;
 }
 
+// One level [batch][rows >> 1][cols >> 1] of fd_pyr_build_gauss from the level [batch][rows][cols] below it: k_blur
+// with pyrDown's taps and step 2, storing the floor dimensions.
+hipError_t pyr_down_gauss(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s) {
+    fdk::BlurArgs a{};
+    a.frames = src;
+    a.out = dst;
+    a.batch = batch;
+    a.rows = rows;
+    a.cols = cols;
+    a.out_rows = rows >> 1;
+    a.out_cols = cols >> 1;
+    a.radius = 2;
+    a.step = 2;
+    a.taps[0] = 96;
+    a.taps[1] = 64;
+    a.taps[2] = 16;
+    return fdk::launch_blur(a, s);
+}
+
+// fd_pyr_build and fd_pyr_build_gauss: the checks, the staging and the level loop; the level kernel differs.
+int pyr_build(fd_ctx *c, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols, int levels, uint8_t *pyr,
+              int pyr_on_device, bool gauss) {
+    int rc = check_shape(c, FD_HARRIS, batch, rows, cols, false);
+    if (rc) return rc;
+    if (!frames || !pyr) return fail(c, FD_ERR_INVALID, "frames or pyr is NULL");
+    int64_t off[FD_PYR_MAX_LEVELS + 1];
+    if (!pyr_offsets(batch, rows, cols, levels, off))
+        return fail(c, FD_ERR_INVALID, "levels must be in [1, 6] and the top level must keep a pixel");
+    if (pyr_on_device && (reinterpret_cast<uintptr_t>(pyr) & 255))
+        return fail(c, FD_ERR_INVALID, "a device pyr must be 256-byte aligned");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = refuse_sync_under_capture(c, pyr_on_device && frames_on_device))) return rc;
+    uint8_t *dpyr = pyr;
+    if (!pyr_on_device) FD_HIP_TRY(c, ensure_as(c, c->staging[0], static_cast<size_t>(off[levels]), dpyr));
+    const size_t bytes0 = static_cast<size_t>(batch) * rows * cols;
+    FD_HIP_TRY(c, hipMemcpyAsync(dpyr, frames, bytes0, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                 c->stream));
+    for (int l = 0; l + 1 < levels; ++l)
+        FD_HIP_TRY(c, (gauss ? pyr_down_gauss : fdk::launch_pyr_down)(dpyr + off[l], dpyr + off[l + 1], batch, rows >> l, cols >> l,
+                                                                      c->stream));
+    if (!pyr_on_device) {
+        for (int l = 0; l < levels; ++l)  // the levels only: the caller's padding bytes stay
+            FD_HIP_TRY(c, hipMemcpyAsync(pyr + off[l], dpyr + off[l], static_cast<size_t>(batch) * (rows >> l) * (cols >> l),
+                                         hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!pyr_on_device || !frames_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return FD_OK;
+}
+
 }  // namespace
 
 int fdrt::finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin) {
@@ -43,30 +92,12 @@ int fd_pyr_layout(int batch, int rows, int cols, int levels, int64_t *offsets) {
 
 int fd_pyr_build(fd_ctx *c, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols, int levels,
                  uint8_t *pyr, int pyr_on_device) {
-    int rc = check_shape(c, FD_HARRIS, batch, rows, cols, false);
-    if (rc) return rc;
-    if (!frames || !pyr) return fail(c, FD_ERR_INVALID, "frames or pyr is NULL");
-    int64_t off[FD_PYR_MAX_LEVELS + 1];
-    if (!pyr_offsets(batch, rows, cols, levels, off))
-        return fail(c, FD_ERR_INVALID, "levels must be in [1, 6] and the top level must keep a pixel");
-    if (pyr_on_device && (reinterpret_cast<uintptr_t>(pyr) & 255))
-        return fail(c, FD_ERR_INVALID, "a device pyr must be 256-byte aligned");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = refuse_sync_under_capture(c, pyr_on_device && frames_on_device))) return rc;
-    uint8_t *dpyr = pyr;
-    if (!pyr_on_device) FD_HIP_TRY(c, ensure_as(c, c->staging[0], static_cast<size_t>(off[levels]), dpyr));
-    const size_t bytes0 = static_cast<size_t>(batch) * rows * cols;
-    FD_HIP_TRY(c, hipMemcpyAsync(dpyr, frames, bytes0, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                 c->stream));
-    for (int l = 0; l + 1 < levels; ++l)
-        FD_HIP_TRY(c, fdk::launch_pyr_down(dpyr + off[l], dpyr + off[l + 1], batch, rows >> l, cols >> l, c->stream));
-    if (!pyr_on_device) {
-        for (int l = 0; l < levels; ++l)  // the levels only: the caller's padding bytes stay
-            FD_HIP_TRY(c, hipMemcpyAsync(pyr + off[l], dpyr + off[l], static_cast<size_t>(batch) * (rows >> l) * (cols >> l),
-                                         hipMemcpyDeviceToHost, c->stream));
-    }
-    if (!pyr_on_device || !frames_on_device) FD_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return FD_OK;
+    return pyr_build(c, frames, frames_on_device, batch, rows, cols, levels, pyr, pyr_on_device, false);
+}
+
+int fd_pyr_build_gauss(fd_ctx *c, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols, int levels,
+                       uint8_t *pyr, int pyr_on_device) {
+    return pyr_build(c, frames, frames_on_device, batch, rows, cols, levels, pyr, pyr_on_device, true);
 }
 
 int fd_flow_lk(fd_ctx *c, int batch, int rows, int cols, int levels, const fd_flow_opts *opts, const uint8_t *prev_pyr,

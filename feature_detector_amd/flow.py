@@ -1,4 +1,5 @@
-"""Image pyramids and pyramidal Lucas-Kanade feature tracking over the C ABI (fd_pyr_build, fd_flow_lk).
+"""Image pyramids and pyramidal Lucas-Kanade feature tracking over the C ABI (fd_pyr_build, fd_pyr_build_gauss,
+fd_flow_lk).
 
 An MI355X extension (the reference has no tracker): the step before detect_points in a VIO / SLAM front
 end, on the [batch][stride] layouts detect_points writes, so detect -> track -> (mask survivors) -> detect
@@ -42,14 +43,19 @@ class Pyramid:
         return self.data[self.offsets[l]:self.offsets[l] + self.batch * r * c].reshape(self.batch, r, c)
 
 
-def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_out: bool | None = None) -> Pyramid:
+def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_out: bool | None = None,
+                  kernel: str = "box") -> Pyramid:
     """fd_pyr_build for a batch of uint8 frames [B, rows, cols] (or [rows, cols]): level 0 is the frames,
-    every further level the rounded 2 x 2 box mean of the one below it.
+    every further level the rounded 2 x 2 box mean of the one below it. kernel="gauss" (fd_pyr_build_gauss):
+    every further level is the one below it smoothed by the 5 x 5 binomial kernel [1 4 6 4 1] (blur_frames with
+    taps [96, 64, 16]) and decimated by 2, pyrDown's arithmetic, in the same layout: track_lk takes either kind.
 
     Torch device frames give a device pyramid, asynchronous on torch's current stream (kernels and one
     copy: graph-capturable). Host (numpy) frames give a numpy pyramid, or with device_out=True a device
     pyramid (what track_lk builds from host frames).
     """
+    if kernel not in ("box", "gauss"):
+        raise ValueError('kernel must be "box" or "gauss"')
     fptr, on_dev, b, r, c, keep = _frames(frames)
     ctx = _resolve_ctx(ctx, frames)
     off = pyramid_layout(b, r, c, levels)
@@ -63,7 +69,8 @@ def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_ou
     else:
         data = np.zeros((off[-1],), np.uint8)
     _bind_stream(ctx, bool(on_dev))
-    rc = _lib.load().fd_pyr_build(ctx.ptr, ctypes.c_void_p(fptr), on_dev, b, r, c, int(levels), ptr(data), 1 if dev_out else 0)
+    build = _lib.load().fd_pyr_build_gauss if kernel == "gauss" else _lib.load().fd_pyr_build
+    rc = build(ctx.ptr, ctypes.c_void_p(fptr), on_dev, b, r, c, int(levels), ptr(data), 1 if dev_out else 0)
     _lib.check(ctx.ptr, rc)
     return Pyramid(data, b, r, c, int(levels), off)
 

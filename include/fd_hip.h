@@ -963,6 +963,72 @@ typedef struct fd_equalize_opts {
 int fd_frames_equalize(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
                        const fd_equalize_opts *opts, uint8_t *out, int out_on_device);
 
+/* ---- Gaussian smoothing and the Gaussian pyramid (MI355X extension) ----------------------------------- */
+#define FD_BLUR_MAX_RADIUS 15
+typedef struct fd_blur_opts {
+    int32_t radius;    /* r in 0..15: the kernel is (2r+1) x (2r+1), separable, symmetric */
+    int32_t taps[16];  /* w[0..r] >= 0 with w[0] + 2*(w[1]+...+w[r]) == 256; entries above r ignored */
+    int32_t step;      /* 1: same size; 2: every second row and column (pyrDown's decimation) */
+} fd_blur_opts;
+
+/*
+ * fd_blur_taps -- the integer taps of a Gaussian of standard deviation sigma, into *opts. A host function (no
+ * context, no GPU), and the only implementation of this rounding: every binding calls it.
+ *   r = radius if radius is in 1..15, otherwise r = min(15, max(1, ceil(3*sigma)))
+ *   g[k] = exp(-(k*k) / (2*sigma*sigma)) in double, k = 0..r;   S = g[0] + 2*(g[1] + ... + g[r])
+ *   w[k] = floor(256*g[k]/S + 0.5) for k = 1..r;   w[0] = 256 - 2*(w[1] + ... + w[r])
+ * opts->radius = r, opts->taps[0..r] = w, the taps above r are 0, opts->step = 1.
+ * FD_ERR_INVALID: opts NULL; sigma not finite or <= 0; w[0] < w[1] (the rounding left a dip in the middle).
+ */
+int fd_blur_taps(double sigma, int radius /* 0: choose */, fd_blur_opts *opts);
+
+/*
+ * fd_frames_blur -- every frame of frames [batch][rows][cols] uint8 smoothed by a separable symmetric kernel
+ * of integer taps into out [batch][out_rows][out_cols] uint8, out_rows = (rows + step - 1)/step and out_cols
+ * likewise: the low-pass ahead of fd_brief_compute (ORB smooths before it compares single samples), and with
+ * step 2 one level of a Gaussian pyramid. The reference has no such stage: the contract is this text. Every
+ * quantity is an integer. Frames are independent.
+ *
+ * Border: reflect-101, iterated, so that any dimension works with any radius. For a dimension n and an index i
+ * (any integer): refl(i, n) = 0 if n == 1; otherwise p = 2(n-1), m = ((i mod p) + p) mod p (so 0 <= m < p), and
+ * refl = m if m < n, else p - m. I(Y, X) below stands for frame[refl(Y, rows)][refl(X, cols)]: a read never
+ * crosses into a neighbouring frame of the batch.
+ *
+ * Output pixel (y, x) is centred on source pixel (Y, X) = (step*y, step*x). With w = taps and r = radius:
+ *   h(Y', X) = w[0]*I(Y', X) + sum over k = 1..r of w[k]*(I(Y', X-k) + I(Y', X+k))      0 <= h <= 255*256 = 65280
+ *   v        = w[0]*h(Y, X)  + sum over k = 1..r of w[k]*(h(Y-k, X) + h(Y+k, X))        0 <= v <= 255*2^16
+ *   out(y, x) = (v + 2^15) >> 16
+ * One rounding, at the end; none between the passes (h is kept whole, in 16 bits).
+ * Consequences: r = 0 with step 1 is a copy. A constant frame is unchanged. taps {96, 64, 16} with step 2 is
+ * (S16 + 128) >> 8 with S16 the sum under the 5 x 5 kernel [1 4 6 4 1] x [1 4 6 4 1] (every tap is 16 times its
+ * binomial weight, so v = 256*S16): the arithmetic of OpenCV's pyrDown with its default border, an equality
+ * with OpenCV that is not verified here. Taps need not decrease ({0, 128} is legal). The output depends only on
+ * the frame and the options, never on the launch shape.
+ *
+ * No alignment beyond a byte is asked of frames or out, and every dimension may be odd. frames and out are
+ * device pointers when their *_on_device flag is set. Host frames are staged through the context as
+ * fd_pyr_build stages them, a host out through a context buffer; a call with a host array is complete on
+ * return. With both pointers on the device the call is one kernel on the context's stream: asynchronous and
+ * graph-capturable (no workspace is involved). out == frames on the same side is refused (a workgroup's halo
+ * would be overwritten by its neighbour: there is no in-place call); any other overlap is the caller's error
+ * and is not detected.
+ * FD_ERR_INVALID: ctx, opts, frames or out NULL; batch, rows or cols < 1; rows or cols > 2^30; radius outside 0..15; a negative tap
+ * among w[0..r]; w[0] + 2*(w[1]+...+w[r]) != 256; step not 1 or 2; out == frames on the same side.
+ */
+int fd_frames_blur(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                   const fd_blur_opts *opts, uint8_t *out, int out_on_device);
+
+/*
+ * fd_pyr_build_gauss -- fd_pyr_build with a Gaussian in place of the 2 x 2 box: the same packed layout
+ * (fd_pyr_layout), staging, alignment rule and errors, so that fd_flow_lk takes the pyramid as it is. Level 0
+ * is a copy of the frames. Level l+1 is the top-left (rows_l >> 1) x (cols_l >> 1) block of fd_frames_blur of
+ * level l (rows_l x cols_l, reflected at that level's own edges) with radius 2, taps {96, 64, 16} and step 2:
+ * for an odd dimension the blur's last row or column is dropped. Padding bytes between the levels are not
+ * written.
+ */
+int fd_pyr_build_gauss(fd_ctx *ctx, const uint8_t *frames, int frames_on_device, int batch, int rows, int cols,
+                       int levels, uint8_t *pyr, int pyr_on_device);
+
 /* ---- Line band descriptor (MI355X extension) ---------------------------------------------------------- */
 typedef struct fd_line_desc_opts {
     int32_t bands;      /* 1..32 (default 9): bands across the line; the descriptor has dim = 8*bands floats */

@@ -28,6 +28,12 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      --eq-size vga1 (640x480 batch 1, 200 calls), vga64 (640x480 batch 64, 20 calls) or hd
                      (1920x1080 batch 64, 10 calls); all: the three in turn (a trace per shape keeps its statistics
                      one shape's)
+  --shape blur       fd_frames_blur on device tensors, out preallocated, one k_blur per call: r = 2 {96, 64, 16} at step 1
+                     and at step 2, r = 3 gaussian_taps(2.0, 3) and r = 15 gaussian_taps(5.0) at step 1 (--blur-case
+                     blur); fd_pyr_build_gauss against fd_pyr_build, 3 levels (--blur-case pyramid); on blurred-noise
+                     frames at --blur-size vga1 (640x480 batch 1, 200 calls), vga64 (640x480 batch 64, 20 calls) or
+                     hd (1920x1080 batch 64, 10 calls); all: everything in turn (a trace per size and case keeps a
+                     kernel instance's statistics one shape's). Every call is also timed here with events
   --shape linedesc   fd_lines_describe on device tensors, default options (9 bands of 7 rows, dim 72), 512 seeded
                      segments per frame with lengths 20..300 px at any angle on 640x480 frames of blurred noise:
                      batch 64 (20 calls), then batch 1 (200 calls); one k_line_desc per call, also timed here with
@@ -54,7 +60,7 @@ import feature_detector_amd as fd  # noqa: E402
 
 THR = {"harris": 30.0, "shi_tomasi": 40.0, "fast": 10.0}
 p = argparse.ArgumentParser()
-p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "equalize", "linedesc", "nnmatch", "lsd",
+p.add_argument("--shape", default="bench", choices=["bench", "northstar", "nsdetect", "fast720", "fast720r", "fastbrief", "fastmatch", "fastflow", "strefine", "fastverify", "warp", "equalize", "blur", "linedesc", "nnmatch", "lsd",
                                                    "ties", "nsties"])
 p.add_argument("--kind", default=None, choices=[None, "harris", "shi_tomasi", "fast", "dense", "compact", "dense_unpitched"])
 p.add_argument("--calls", type=int, default=0)
@@ -64,6 +70,8 @@ p.add_argument("--refit", action="store_true", help="fastverify: fd_ransac_refit
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
 p.add_argument("--warp-size", default="both", choices=["both", "hd", "vga"], help="warp: one of the two shapes (a trace per shape)")
 p.add_argument("--eq-size", default="all", choices=["all", "vga1", "vga64", "hd"], help="equalize: one of the three shapes (a trace per shape)")
+p.add_argument("--blur-size", default="all", choices=["all", "vga1", "vga64", "hd"], help="blur: one of the three shapes (a trace per shape)")
+p.add_argument("--blur-case", default="all", choices=["all", "blur", "pyramid"], help="blur: the smoothing calls or the pyramids")
 p.add_argument("--thr", type=float, default=None, help="response threshold override (e.g. 1e30: no candidates)")
 a = p.parse_args()
 g = torch.Generator(device="cuda")
@@ -258,6 +266,34 @@ elif a.shape == "equalize":
             fd.equalize_frames(frames, (8, 8), 3.0, out=out)
         print(f"equalize {cols}x{rows}x{b}: mean in {float(frames.float().mean()):.1f}, mean out {float(out.float().mean()):.1f}, "
               f"levels in {int(frames.unique().numel())}, levels out {int(out.unique().numel())}")
+elif a.shape == "blur":
+    kind = "r 2 / 3 / 15, pyramids"
+
+    def timed(what, call, calls):
+        for _ in range(3):
+            call()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(calls + 1)]
+        ev[0].record()
+        for e in ev[1:]:
+            call()
+            e.record()
+        torch.cuda.synchronize()
+        us = sorted(1e3 * x.elapsed_time(y) for x, y in zip(ev, ev[1:]))
+        print(f"{what}: median {us[len(us) // 2]:.1f} us per call (min {us[0]:.1f}, max {us[-1]:.1f}), {len(us)} calls")
+
+    sizes = {"vga1": (1, 480, 640, a.calls or 200), "vga64": (64, 480, 640, a.calls or 20), "hd": (64, 1080, 1920, a.calls or 10)}
+    for b, rows, cols, calls in (sizes.values() if a.blur_size == "all" else (sizes[a.blur_size],)):
+        frames = torch.nn.functional.avg_pool2d(noise(b, rows + 4, cols + 4).float()[:, None], 5, 1)[:, 0].clamp(0, 255).to(torch.uint8).contiguous()
+        if a.blur_case in ("all", "blur"):
+            full, half = torch.empty_like(frames), torch.empty((b, (rows + 1) // 2, (cols + 1) // 2), dtype=torch.uint8, device="cuda")
+            for name, taps, step in (("r 2 step 1", [96, 64, 16], 1), ("r 2 step 2", [96, 64, 16], 2),
+                                     ("r 3 step 1", fd.gaussian_taps(2.0, 3)[1], 1), ("r 15 step 1", fd.gaussian_taps(5.0)[1], 1)):
+                out = half if step == 2 else full
+                timed(f"fd.blur_frames {cols}x{rows}x{b} {name}", lambda: fd.blur_frames(frames, taps=taps, step=step, out=out), calls)
+                print(f"  mean in {float(frames.float().mean()):.2f}, mean out {float(out.float().mean()):.2f}")
+        if a.blur_case in ("all", "pyramid"):
+            for kernel in ("box", "gauss"):
+                timed(f"fd.build_pyramid {cols}x{rows}x{b} 3 levels {kernel}", lambda: fd.build_pyramid(frames, 3, kernel=kernel), calls)
 elif a.shape == "linedesc":
     kind = "9 bands x 7 rows"
     rows, cols, S = 480, 640, 512
