@@ -1,5 +1,7 @@
 // GeometricVerifier over libfdhip.so (fd_ransac): an MI355X extension, the reference has no such stage.
 // One host-pointer call per Verify: the positions go up, three kernels run, the mask and the model come back.
+// Refit, RecoverPose and Triangulate are one host-pointer call each as well (fd_ransac_refit, fd_pose_recover,
+// fd_triangulate).
 #include "feature_detector/geometric_verifier.h"
 
 #include <algorithm>
@@ -79,6 +81,87 @@ bool GeometricVerifier::Refit(const std::vector<Vec2> &query_uv, const std::vect
     inlier.swap(out_inlier);
     std::copy(m, m + 9, model.begin());
     if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
+namespace {
+
+fd_pose_opts PoseOpts(const GeometricVerifier::Camera &q, const GeometricVerifier::Camera &t, const GeometricVerifier::PoseOptions &o) {
+    return fd_pose_opts{q.fx, q.fy, q.cx, q.cy, t.fx, t.fy, t.cx, t.cy, o.kMaxDepth, o.kMinParallax};
+}
+
+}  // namespace
+
+bool GeometricVerifier::RecoverPose(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv,
+                                    const std::vector<uint8_t> &inlier, const std::array<double, 9> &model,
+                                    const Camera &query_camera, const Camera &train_camera, std::array<double, 12> &pose,
+                                    std::vector<std::array<float, 3>> &points, std::vector<uint8_t> &point_valid,
+                                    const std::vector<int32_t> *train_index, const std::vector<uint8_t> *valid, int32_t *choice) {
+    const size_t n = query_uv.size();
+    pose.fill(0.0);
+    points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
+    point_valid.assign(n, 0);
+    if (choice) *choice = -1;
+    if (n == 0) return context_.Fail("RecoverPose: no query points");
+    if (inlier.size() != n) return context_.Fail("RecoverPose: one inlier flag per query point is needed");
+    if (train_index && train_index->size() != n) return context_.Fail("RecoverPose: one train index per query point is needed");
+    if (valid && valid->size() != n) return context_.Fail("RecoverPose: one valid flag per query point is needed");
+    if (!train_index && train_uv.size() < n)
+        return context_.Fail("RecoverPose: without train_index every query point needs its train point");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    const std::vector<float> q = Flatten(query_uv);
+    std::vector<float> t = Flatten(train_uv);
+    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
+    int32_t won = -1;
+    const int rc = fd_pose_recover(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
+                                   static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
+                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), pose.data(), &won,
+                                   points[0].data(), point_valid.data(), nullptr, 0);
+    if (rc != FD_OK) {
+        pose.fill(0.0);
+        points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
+        point_valid.assign(n, 0);
+        return context_.FailCall("fd_pose_recover");
+    }
+    if (won < 0) return context_.Fail("RecoverPose: no pose (a degenerate model, a pure rotation, or no inlier in front)");
+    if (choice) *choice = won;
+    return true;
+}
+
+bool GeometricVerifier::Triangulate(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv,
+                                    const std::array<double, 12> &pose, const Camera &query_camera, const Camera &train_camera,
+                                    std::vector<std::array<float, 3>> &points, std::vector<uint8_t> &point_valid,
+                                    const std::vector<uint8_t> *inlier, const std::vector<int32_t> *train_index,
+                                    const std::vector<uint8_t> *valid, int32_t *count) {
+    const size_t n = query_uv.size();
+    points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
+    point_valid.assign(n, 0);
+    if (count) *count = 0;
+    if (n == 0) return context_.Fail("Triangulate: no query points");
+    if (inlier && inlier->size() != n) return context_.Fail("Triangulate: one inlier flag per query point is needed");
+    if (train_index && train_index->size() != n) return context_.Fail("Triangulate: one train index per query point is needed");
+    if (valid && valid->size() != n) return context_.Fail("Triangulate: one valid flag per query point is needed");
+    if (!train_index && train_uv.size() < n)
+        return context_.Fail("Triangulate: without train_index every query point needs its train point");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    const std::vector<float> q = Flatten(query_uv);
+    std::vector<float> t = Flatten(train_uv);
+    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
+    int32_t found = 0;
+    const int rc = fd_triangulate(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
+                                  static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
+                                  valid ? valid->data() : nullptr, pose.data(), inlier ? inlier->data() : nullptr,
+                                  points[0].data(), point_valid.data(), &found, 0);
+    if (rc != FD_OK) {
+        points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
+        point_valid.assign(n, 0);
+        return context_.FailCall("fd_triangulate");
+    }
+    if (count) *count = found;
     return true;
 }
 

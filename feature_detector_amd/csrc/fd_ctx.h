@@ -63,7 +63,7 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest call is a model-gated match (9 inputs, 3 outputs)
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs) and fd_pose_recover (7 and 5)
     static constexpr int kStaging = 12;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and

@@ -470,6 +470,25 @@ struct RefitArgs {
     int32_t *out_rounds;         // [batch] or null
 };
 
+// Pose from a fundamental matrix and triangulation (fd_ransac.hip; fd_pose_recover and fd_triangulate of
+// include/fd_hip.h). The pair arrays are fd_ransac's.
+struct PoseArgs {
+    const float *q_xy, *t_xy;
+    const int32_t *q_counts;
+    const int32_t *match_idx;
+    const uint8_t *pair_valid;
+    const uint8_t *in_inlier;    // [batch][q_stride]; only a byte equal to 1 takes part; null (fd_triangulate): all
+    const double *in_model;      // fd_pose_recover: F [batch][9]; fd_triangulate: the pose [batch][12]
+    int batch, q_stride, t_stride;
+    double cam[8];               // fx, fy, cx, cy of the q camera, then of the t camera
+    double mm, D;                // (double)min_parallax squared; (double)max_depth
+    double *out_pose;            // [batch][12] or null (fd_pose_recover)
+    int32_t *out_choice;         // [batch] or null (fd_pose_recover)
+    float *out_points;           // [batch][q_stride][3] or null
+    uint8_t *out_valid;          // [batch][q_stride] or null
+    int32_t *out_counts;         // [batch] or null
+};
+
 // Image warp (fd_warp.hip): every destination pixel of out [batch][out_rows][out_cols] sampled from the frames
 // [batch][rows][cols] at the position a per-frame model gives (fd_frames_warp of include/fd_hip.h).
 struct WarpArgs {
@@ -529,6 +548,10 @@ hipError_t launch_warp(WarpArgs a, hipStream_t s);
 hipError_t launch_ransac(const RansacArgs &a, hipStream_t s);
 // k_ransac_compact, then k_ransac_refit (all rounds in one launch)
 hipError_t launch_ransac_refit(const RefitArgs &a, hipStream_t s);
+// k_pose_recover, one workgroup per frame
+hipError_t launch_pose_recover(const PoseArgs &a, hipStream_t s);
+// a memset of out_counts, then k_triangulate (q_stride >= 1)
+hipError_t launch_triangulate(const PoseArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);

@@ -19,6 +19,12 @@
 // contract's order (256 partials in registers, an LDS tree in slices of 9 entries), its smallest eigenvector
 // comes from a fixed number of cyclic Jacobi sweeps on one wave with the matrix and V in LDS, F is projected
 // to rank 2 by the same routine on F^T F, and every correspondence is classified again.
+//
+// k_pose_recover (fd_pose_recover), one workgroup per frame: one wave turns the frame's F into the essential
+// matrix and its four pose candidates (the same Jacobi on E^T E, the 3 x 3 matrices in LDS), every thread walks
+// the slots t, t + 256, ... with four counts in registers, the workgroup picks the winner, and a second walk
+// writes the points. k_triangulate (fd_triangulate), one thread per slot, runs the same step for a given pose.
+// Neither needs k_ransac_compact: nothing in them depends on a correspondence's number in the list.
 #include "fd_hip.h"
 #include "fd_window.h"
 
@@ -373,11 +379,11 @@ __device__ __forceinline__ int wg_count(uint32_t mine, int *total) {
 // so the lanes read their two elements, then write them (the matrix rows mirrored into the columns), and the
 // result is the serial restatement's bit for bit. The dependent chain of a rotation (two divisions, two square
 // roots) is computed by every lane alike; p, q and the skip are wave-uniform.
-template <int N>
+template <int N, int SWEEPS>
 __device__ __forceinline__ void jacobi(double *m, int lane) {
     const bool live = lane < 2 * N, sym = lane < N;
     const int r = live ? lane : 0;
-    for (int sweep = 0; sweep < kSweeps; ++sweep)
+    for (int sweep = 0; sweep < SWEEPS; ++sweep)
         for (int p = 0; p < N - 1; ++p)
             for (int q = p + 1; q < N; ++q) {
                 const double apq = m[p * N + q];
@@ -500,7 +506,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
         }
         if (tid < 81) mat[81 + tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
         __syncthreads();
-        if (tid < kWave) jacobi<9>(mat, lane);
+        if (tid < kWave) jacobi<9, kSweeps>(mat, lane);
         __syncthreads();
         double d[9], x[9];
 #pragma unroll
@@ -530,7 +536,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
                     }
             }
             __syncthreads();
-            if (tid < kWave) jacobi<3>(mat3, lane);
+            if (tid < kWave) jacobi<3, kSweeps>(mat3, lane);
             __syncthreads();
             double d3[3], v[3];
 #pragma unroll
@@ -600,7 +606,249 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
     write_model<MODEL>(xa, e->r.cx, e->r.cy, e->r.scale, om);
 }
 
+// ---- fd_pose_recover, fd_triangulate: the pose of a fundamental matrix and the inliers' 3-D points ----------
+constexpr int kPoseSweeps = FD_POSE_SWEEPS;
+
+// Whether slot i of frame f (slots from s0) takes part, by fd_ransac's rules and the in_inlier byte, and its
+// normalised rays (ax, ay), (bx, by).
+__device__ __forceinline__ bool pose_rays(const PoseArgs &a, int f, int64_t s0, int i, double &ax, double &ay, double &bx,
+                                          double &by) {
+    bool take = !a.pair_valid || a.pair_valid[s0 + i] == 1;
+    take = take && (!a.in_inlier || a.in_inlier[s0 + i] == 1);
+    const int j = a.match_idx ? a.match_idx[s0 + i] : i;
+    take = take && j >= 0 && j < a.t_stride;
+    ax = ay = bx = by = 0.0;
+    if (!take) return false;
+    const float2 q = reinterpret_cast<const float2 *>(a.q_xy)[s0 + i];
+    const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[static_cast<int64_t>(f) * a.t_stride + j];
+    ax = (static_cast<double>(q.x) - a.cam[2]) / a.cam[0];
+    ay = (static_cast<double>(q.y) - a.cam[3]) / a.cam[1];
+    bx = (static_cast<double>(t.x) - a.cam[6]) / a.cam[4];
+    by = (static_cast<double>(t.y) - a.cam[7]) / a.cam[5];
+    return isfinite(q.x) && isfinite(q.y) && isfinite(t.x) && isfinite(t.y);
+}
+
+__device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
+    return a0 * b0 + a1 * b1 + a2 * b2;
+}
+
+// The contract's step for the pose (R, t): whether the point is in front, and its depth z1 along (ax, ay, 1).
+__device__ __forceinline__ bool pose_step(const double (&R)[9], const double (&t)[3], double ax, double ay, double bx, double by,
+                                          double mm, double D, double &z1) {
+    const double r0 = R[0] * ax + R[1] * ay + R[2];
+    const double r1 = R[3] * ax + R[4] * ay + R[5];
+    const double r2 = R[6] * ax + R[7] * ay + R[8];
+    const double rr = dot3(r0, r1, r2, r0, r1, r2), pp = dot3(bx, by, 1.0, bx, by, 1.0), rp = dot3(r0, r1, r2, bx, by, 1.0);
+    const double rt = dot3(r0, r1, r2, t[0], t[1], t[2]), pt = dot3(bx, by, 1.0, t[0], t[1], t[2]);
+    const double det = rr * pp - rp * rp;
+    z1 = (rp * pt - pp * rt) / det;
+    const double z2 = (rr * pt - rp * rt) / det;
+    return det > mm * (rr * pp) && z1 > 0.0 && z2 > 0.0 && z1 <= D && z2 <= D;
+}
+
+// A slot's outputs: the byte, and the point (z1 ax, z1 ay, z1) or zeros.
+__device__ __forceinline__ void write_point(const PoseArgs &a, int64_t slot, bool in, double ax, double ay, double z1) {
+    if (a.out_valid) a.out_valid[slot] = in ? 1 : 0;
+    if (a.out_points) {
+        a.out_points[3 * slot] = in ? static_cast<float>(z1 * ax) : 0.0f;
+        a.out_points[3 * slot + 1] = in ? static_cast<float>(z1 * ay) : 0.0f;
+        a.out_points[3 * slot + 2] = in ? static_cast<float>(z1) : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(kRansacThreads) void k_triangulate(PoseArgs a, int chunks) {
+    const int f = static_cast<int>(blockIdx.x) / chunks;
+    const int i = (static_cast<int>(blockIdx.x) - f * chunks) * kRansacThreads + static_cast<int>(threadIdx.x);
+    const int nf = frame_count(a.q_counts, f, a.q_stride);
+    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
+    double R[9], t[3];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) R[c] = a.in_model[static_cast<int64_t>(f) * 12 + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = a.in_model[static_cast<int64_t>(f) * 12 + 9 + c];
+    bool in = false;
+    if (i < nf) {  // nf <= q_stride
+        double ax, ay, bx, by, z1 = 0.0;
+        in = pose_rays(a, f, s0, i, ax, ay, bx, by);
+        in = pose_step(R, t, ax, ay, bx, by, a.mm, a.D, z1) && in;
+        write_point(a, s0 + i, in, ax, ay, z1);
+    }
+    const uint32_t wave_n = wave_total_add(in ? 1u : 0u);
+    if (lane_id() == 0 && wave_n && a.out_counts) atomicAdd(a.out_counts + f, static_cast<int>(wave_n));  // zeroed by the launcher
+}
+
+__global__ __launch_bounds__(kRansacThreads) void k_pose_recover(PoseArgs a) {
+    __shared__ double mat3[6 * 3];  // G, then V
+    __shared__ double em[9];        // E
+    __shared__ double cand[21];     // Ra, Rb, u3
+    __shared__ int has_cand;
+    __shared__ int cnt[4];
+    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x), lane = lane_id();
+    const int nf = frame_count(a.q_counts, f, a.q_stride);
+    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
+
+    if (tid < kWave) {  // steps 1-4 on one wave
+        if (tid == 0) {
+            double F[9], FK[9], E[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) F[c] = a.in_model[static_cast<int64_t>(f) * 9 + c];
+            const double Kq[9] = {a.cam[0], 0.0, a.cam[2], 0.0, a.cam[1], a.cam[3], 0.0, 0.0, 1.0};
+            const double KtT[9] = {a.cam[4], 0.0, 0.0, 0.0, a.cam[5], 0.0, a.cam[6], a.cam[7], 1.0};
+            matmul3(F, Kq, FK);
+            matmul3(KtT, FK, E);
+#pragma unroll
+            for (int c = 0; c < 9; ++c) em[c] = E[c];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) s = s + E[3 * k + i] * E[3 * k + j];
+                    mat3[3 * i + j] = s;
+                    mat3[9 + 3 * i + j] = i == j ? 1.0 : 0.0;
+                }
+        }
+        wave_lds_sync();
+        jacobi<3, kPoseSweeps>(mat3, lane);
+        wave_lds_sync();
+        if (tid == 0) {
+            double d[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[k] = mat3[3 * k + k];
+            const int j = smallest<3>(d);
+            const int ia = j == 0 ? 1 : 0, ib = j == 2 ? 1 : 2;
+            double dmax = d[0];
+#pragma unroll
+            for (int k = 1; k < 3; ++k)
+                if (d[k] > dmax) dmax = d[k];
+            const double da = mat3[3 * ia + ia], db = mat3[3 * ib + ib];
+            const double dmin = db < da ? db : da;
+            double v1[3], v2[3], w1[3], w2[3], u1[3], u2[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                v1[k] = mat3[(3 + k) * 3 + ia];
+                v2[k] = mat3[(3 + k) * 3 + ib];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                w1[i] = dot3(em[3 * i], em[3 * i + 1], em[3 * i + 2], v1[0], v1[1], v1[2]);
+                w2[i] = dot3(em[3 * i], em[3 * i + 1], em[3 * i + 2], v2[0], v2[1], v2[2]);
+            }
+            const double n1 = sqrt(dot3(w1[0], w1[1], w1[2], w1[0], w1[1], w1[2]));
+            const double n2 = sqrt(dot3(w2[0], w2[1], w2[2], w2[0], w2[1], w2[2]));
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                u1[i] = w1[i] / n1;
+                u2[i] = w2[i] / n2;
+            }
+            const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+            const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+            bool ok = isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && dmin > 1e-12 * dmax;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double ra = (u2[i] * v1[k] - u1[i] * v2[k]) + u3[i] * v3[k];
+                    const double rb = (u1[i] * v2[k] - u2[i] * v1[k]) + u3[i] * v3[k];
+                    cand[3 * i + k] = ra;
+                    cand[9 + 3 * i + k] = rb;
+                    ok = ok && isfinite(ra) && isfinite(rb);
+                }
+                cand[18 + i] = u3[i];
+                ok = ok && isfinite(u3[i]) && isfinite(v1[i]) && isfinite(v2[i]);
+            }
+            has_cand = ok ? 1 : 0;
+        }
+    }
+    if (tid < 4) cnt[tid] = 0;
+    __syncthreads();
+
+    const bool has = has_cand != 0;
+    double Ra[9], Rb[9], tp[3], tn[3];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) {
+        Ra[c] = cand[c];
+        Rb[c] = cand[9 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        tp[c] = cand[18 + c];
+        tn[c] = -tp[c];
+    }
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    if (has)
+        for (int i = tid; i < nf; i += kRansacThreads) {
+            double ax, ay, bx, by, z;
+            if (!pose_rays(a, f, s0, i, ax, ay, bx, by)) continue;
+            c0 += pose_step(Ra, tp, ax, ay, bx, by, a.mm, a.D, z) ? 1u : 0u;
+            c1 += pose_step(Ra, tn, ax, ay, bx, by, a.mm, a.D, z) ? 1u : 0u;
+            c2 += pose_step(Rb, tp, ax, ay, bx, by, a.mm, a.D, z) ? 1u : 0u;
+            c3 += pose_step(Rb, tn, ax, ay, bx, by, a.mm, a.D, z) ? 1u : 0u;
+        }
+    const uint32_t w0 = wave_total_add(c0), w1 = wave_total_add(c1), w2 = wave_total_add(c2), w3 = wave_total_add(c3);
+    if (lane == 0) {
+        if (w0) atomicAdd(&cnt[0], static_cast<int>(w0));
+        if (w1) atomicAdd(&cnt[1], static_cast<int>(w1));
+        if (w2) atomicAdd(&cnt[2], static_cast<int>(w2));
+        if (w3) atomicAdd(&cnt[3], static_cast<int>(w3));
+    }
+    __syncthreads();
+    int best = cnt[0], choice = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+        if (cnt[k] > best) {
+            best = cnt[k];
+            choice = k;
+        }
+    const bool pose = has && best > 0;  // uniform over the workgroup
+    double R[9], t[3];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) R[c] = choice < 2 ? Ra[c] : Rb[c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = (choice & 1) ? tn[c] : tp[c];
+    if (a.out_valid || a.out_points)
+        for (int i = tid; i < nf; i += kRansacThreads) {
+            double ax = 0.0, ay = 0.0, bx, by, z1 = 0.0;
+            bool in = false;
+            if (pose) {
+                in = pose_rays(a, f, s0, i, ax, ay, bx, by);
+                in = pose_step(R, t, ax, ay, bx, by, a.mm, a.D, z1) && in;
+            }
+            write_point(a, s0 + i, in, ax, ay, z1);
+        }
+    if (tid != 0) return;
+    if (a.out_counts) a.out_counts[f] = pose ? best : 0;
+    if (a.out_choice) a.out_choice[f] = pose ? choice : -1;
+    if (a.out_pose) {
+        double *op = a.out_pose + static_cast<int64_t>(f) * 12;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) op[c] = pose ? R[c] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) op[9 + c] = pose ? t[c] : 0.0;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_pose_recover(const PoseArgs &a, hipStream_t s) {
+    if (a.batch < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pose_recover, dim3(static_cast<unsigned>(a.batch)), dim3(kRansacThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// One thread per slot, (chunks, batch) workgroups as one grid dimension (no 65535 limit on the batch).
+hipError_t launch_triangulate(const PoseArgs &a, hipStream_t s) {
+    const int chunks = (a.q_stride + kRansacThreads - 1) / kRansacThreads;
+    const int64_t blocks = static_cast<int64_t>(a.batch) * chunks;
+    if (a.batch < 1 || chunks < 1 || blocks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+    if (a.out_counts) {
+        const hipError_t e = hipMemsetAsync(a.out_counts, 0, sizeof(int32_t) * a.batch, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_triangulate, dim3(static_cast<unsigned>(blocks)), dim3(kRansacThreads), 0, s, a, chunks);
+    return hipGetLastError();
+}
 
 hipError_t launch_ransac_refit(const RefitArgs &a, hipStream_t s) {
     if (a.r.batch < 1) return hipErrorInvalidValue;

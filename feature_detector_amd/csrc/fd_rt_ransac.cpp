@@ -1,5 +1,6 @@
-// Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac) and the least-squares
-// refit of its model (fd_ransac_refit) over the kernels of fd_ransac.hip.
+// Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac), the least-squares
+// refit of its model (fd_ransac_refit), the pose of a fundamental matrix (fd_pose_recover) and triangulation
+// (fd_triangulate) over the kernels of fd_ransac.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -42,6 +43,45 @@ int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_
     FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
     FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
     FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
+    return FD_OK;
+}
+
+// What fd_triangulate and fd_pose_recover ask of the arguments they share, and the option fields of the kernels'
+// argument block.
+int pose_args(fd_ctx *c, fdk::PoseArgs &a, int batch, const fd_pose_opts *o, int32_t q_stride, int32_t t_stride,
+              const int32_t *match_idx) {
+    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
+    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
+    if (!match_idx && t_stride < q_stride)
+        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
+    const double cam[8] = {o->fx_q, o->fy_q, o->cx_q, o->cy_q, o->fx_t, o->fy_t, o->cx_t, o->cy_t};
+    for (int k = 0; k < 8; ++k) {
+        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
+        a.cam[k] = cam[k];
+    }
+    if (cam[0] == 0.0 || cam[1] == 0.0 || cam[4] == 0.0 || cam[5] == 0.0)
+        return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
+    if (!(o->max_depth > 0.0f)) return fail(c, FD_ERR_INVALID, "max_depth must be > 0");
+    if (!(o->min_parallax >= 0.0f && o->min_parallax <= 1.0f)) return fail(c, FD_ERR_INVALID, "min_parallax must be in [0, 1]");
+    a.batch = batch;
+    a.q_stride = q_stride;
+    a.t_stride = t_stride;
+    const double m = static_cast<double>(o->min_parallax);
+    a.mm = m * m;
+    a.D = static_cast<double>(o->max_depth);
+    return FD_OK;
+}
+
+// The pair arrays of both calls, staged or handed on.
+int pose_pairs(fd_ctx *c, HostIo &io, fdk::PoseArgs &a, const float *q_xy, const int32_t *q_counts, const float *t_xy,
+               const int32_t *match_idx, const uint8_t *pair_valid, const uint8_t *in_inlier) {
+    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride, ts = static_cast<size_t>(a.batch) * a.t_stride;
+    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, a.q_xy));
+    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
+    FD_HIP_TRY(c, io.in(q_counts, a.batch, a.q_counts));
+    FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
+    FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
+    FD_HIP_TRY(c, io.in(in_inlier, qs, a.in_inlier));
     return FD_OK;
 }
 
@@ -141,6 +181,68 @@ int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float
     FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
     FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
     FD_HIP_TRY(c, fdk::launch_ransac_refit(g, c->stream));
+    return io.finish(q_counts, batch, q_stride);
+}
+
+int fd_triangulate(fd_ctx *c, int batch, const fd_pose_opts *opts, const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+                   const float *t_xy, int32_t t_stride, const int32_t *match_idx, const uint8_t *pair_valid,
+                   const double *in_pose, const uint8_t *in_inlier, float *out_points, uint8_t *out_valid, int32_t *out_counts,
+                   int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_xy || !t_xy || !in_pose) return fail(c, FD_ERR_INVALID, "bad arguments");
+    fdk::PoseArgs a{};
+    int rc = pose_args(c, a, batch, opts, q_stride, t_stride, match_idx);
+    if (rc) return rc;
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    if (q_stride == 0) return out_counts ? zero_counts(c, out_counts, batch, io_on_device) : FD_OK;
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
+    HostIo io(c, io_on_device);
+    rc = pose_pairs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid, in_inlier);
+    if (rc) return rc;
+    FD_HIP_TRY(c, io.in(in_pose, static_cast<size_t>(12) * batch, a.in_model));
+    FD_HIP_TRY(c, io.out_slots(out_points, qs, 3, a.out_points));
+    FD_HIP_TRY(c, io.out_slots(out_valid, qs, 1, a.out_valid));
+    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
+    FD_HIP_TRY(c, fdk::launch_triangulate(a, c->stream));
+    return io.finish(q_counts, batch, q_stride);
+}
+
+int fd_pose_recover(fd_ctx *c, int batch, const fd_pose_opts *opts, const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+                    const float *t_xy, int32_t t_stride, const int32_t *match_idx, const uint8_t *pair_valid,
+                    const double *in_model, const uint8_t *in_inlier, double *out_pose, int32_t *out_choice, float *out_points,
+                    uint8_t *out_valid, int32_t *out_counts, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !q_xy || !t_xy || !in_model || !in_inlier) return fail(c, FD_ERR_INVALID, "bad arguments");
+    fdk::PoseArgs a{};
+    int rc = pose_args(c, a, batch, opts, q_stride, t_stride, match_idx);
+    if (rc) return rc;
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    const size_t poses = static_cast<size_t>(12) * batch;
+    if (q_stride == 0) {  // no slots: no frame has a pose
+        if (io_on_device) {
+            if (out_pose) FD_HIP_TRY(c, hipMemsetAsync(out_pose, 0, sizeof(double) * poses, c->stream));
+            if (out_choice) FD_HIP_TRY(c, hipMemsetAsync(out_choice, 0xFF, sizeof(int32_t) * batch, c->stream));
+        } else {
+            if (out_pose) std::fill(out_pose, out_pose + poses, 0.0);
+            if (out_choice) std::fill(out_choice, out_choice + batch, -1);
+        }
+        return out_counts ? zero_counts(c, out_counts, batch, io_on_device) : FD_OK;
+    }
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
+    HostIo io(c, io_on_device);  // 7 inputs and 5 outputs: the whole staging pool
+    rc = pose_pairs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid, in_inlier);
+    if (rc) return rc;
+    FD_HIP_TRY(c, io.in(in_model, static_cast<size_t>(9) * batch, a.in_model));
+    FD_HIP_TRY(c, io.out(out_pose, poses, a.out_pose));
+    FD_HIP_TRY(c, io.out(out_choice, batch, a.out_choice));
+    FD_HIP_TRY(c, io.out_slots(out_points, qs, 3, a.out_points));
+    FD_HIP_TRY(c, io.out_slots(out_valid, qs, 1, a.out_valid));
+    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
+    FD_HIP_TRY(c, fdk::launch_pose_recover(a, c->stream));
     return io.finish(q_counts, batch, q_stride);
 }
 

@@ -1,4 +1,5 @@
-"""RANSAC verification of matches and tracks over the C ABI (fd_ransac).
+"""RANSAC verification of matches and tracks over the C ABI (fd_ransac), the refit of its model
+(fd_ransac_refit), the relative pose of a fundamental matrix (fd_pose_recover) and triangulation (fd_triangulate).
 
 An MI355X extension (the reference has no such stage): the step after brief_match / nn_match or track_lk
 in a VIO / SLAM front end, on their [batch][stride] layouts, so detect -> describe -> match -> verify and
@@ -8,10 +9,13 @@ hypothesis, every hypothesis evaluated) is in include/fd_hip.h.
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 
+import numpy as np
+
 from . import _lib
-from ._lib import fd_ransac_opts, fd_refit_opts
+from ._lib import fd_pose_opts, fd_ransac_opts, fd_refit_opts
 from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
@@ -129,3 +133,117 @@ def refit_geometry(q_xy, t_xy, result: GeometryResult, matches=None, valid=None,
                                      ptr(im), ptr(ii), ptr(om), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return RefitResult(om, oi, oc, result.best, orr)
+
+
+@dataclass
+class PointsResult:
+    points: object  # float32 [B, S, 3]: the 3-D point of every valid slot in the query camera's frame; zeros elsewhere
+    valid: object   # uint8 [B, S]: 1 = a participating correspondence whose point is in front of both cameras
+    counts: object  # int32 [B]: valid points per frame
+
+
+@dataclass
+class PoseResult(PointsResult):
+    pose: object = None    # float64 [B, 12]: R row-major, then t of unit length, X_t = R X_q + t; zeros: no pose
+    choice: object = None  # int32 [B]: the winning candidate 0..3, -1: no pose
+
+    def rotation(self, b=0):
+        """Frame b's R as a [3, 3] view."""
+        return self.pose[b, :9].reshape(3, 3)
+
+    def translation(self, b=0):
+        return self.pose[b, 9:]
+
+
+def intrinsics(K, name="K"):
+    """(fx, fy, cx, cy) as floats from a 3 x 3 camera matrix or those four values. A non-zero skew, a last row
+    other than (0, 0, 1), a non-finite value and a zero focal length are a ValueError."""
+    k = np.asarray(K.cpu() if hasattr(K, "cpu") else K, np.float64)
+    if k.shape == (3, 3):
+        if k[0, 1] != 0.0 or k[1, 0] != 0.0 or k[2, 0] != 0.0 or k[2, 1] != 0.0 or k[2, 2] != 1.0:
+            raise ValueError(f"{name} must be a zero-skew pinhole matrix [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+        k = np.array([k[0, 0], k[1, 1], k[0, 2], k[1, 2]])
+    if k.shape != (4,):
+        raise ValueError(f"{name} must be a 3 x 3 matrix or (fx, fy, cx, cy)")
+    if not np.all(np.isfinite(k)) or k[0] == 0.0 or k[1] == 0.0:
+        raise ValueError(f"{name} must be finite with non-zero fx and fy")
+    return tuple(float(v) for v in k)
+
+
+def _pose_call(q_xy, t_xy, given, given_name, given_width, K, K_t, matches, valid, counts, inliers, max_depth, min_parallax, ctx):
+    """What recover_pose and triangulate share: the checked arguments of the two entry points."""
+    on_dev = _is_torch_device_tensor(q_xy)
+    sides = [_is_torch_device_tensor(t_xy), _is_torch_device_tensor(given)]
+    if inliers is not None:
+        sides.append(_is_torch_device_tensor(inliers))
+    if any(side != on_dev for side in sides):
+        raise ValueError(f"t_xy, {given_name} and the inliers must be on the side (host / device) of q_xy")
+    ctx = _resolve_ctx(ctx, q_xy, t_xy)
+    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
+    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
+    if int(pt.shape[0]) != b:
+        raise ValueError("q_xy and t_xy must have the same batch")
+    if matches is None and ts < s:
+        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
+    if not (max_depth > 0) or not 0.0 <= min_parallax <= 1.0 or math.isnan(min_parallax):
+        raise ValueError("max_depth must be > 0 and min_parallax in [0, 1]")
+    cam_q = intrinsics(K)
+    cam_t = cam_q if K_t is None else intrinsics(K_t, "K_t")
+    opts = fd_pose_opts(*cam_q, *cam_t, float(max_depth), float(min_parallax))
+    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
+    cn = slot_arg(counts, "int32", (b,), on_dev)
+    gm, ii = slot_arg(given, "float64", (b, given_width), on_dev), slot_arg(inliers, "uint8", (b, s), on_dev)
+    return ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii
+
+
+POINT_SPECS = lambda b, s: (((b, s, 3), "float32", 0), ((b, s), "uint8", 0), ((b,), "int32", 0))  # noqa: E731
+
+
+def triangulate(q_xy, t_xy, pose, K, K_t=None, matches=None, valid=None, counts=None, inliers=None,
+                max_depth: float = math.inf, min_parallax: float = 1e-3, out=None, ctx: Context | None = None) -> PointsResult:
+    """fd_triangulate: the 3-D point of every correspondence under a known relative pose (a calibrated stereo
+    rig behind track_lk, or a pose from elsewhere), in the query camera's frame.
+
+    q_xy, t_xy, matches, valid and counts are verify_geometry's. pose: float64 [B, 12] (or [12] for batch 1), R
+    row-major then t, X_t = R X_q + t; the points come out in the unit of t. K, K_t: the query and train
+    cameras as 3 x 3 zero-skew pinhole matrices or (fx, fy, cx, cy) (K_t None: the same camera). inliers uint8
+    [B, S] (None: every correspondence): only the slots equal to 1 take part. A point is valid when both
+    depths are positive and at most max_depth, and the sine of the angle between the rays exceeds min_parallax.
+
+    Returns a PointsResult. Host and device inputs and out= (points float32 [B, S, 3], valid uint8 [B, S],
+    counts int32 [B]) behave as in verify_geometry.
+    """
+    ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii = _pose_call(
+        q_xy, t_xy, pose, "pose", 12, K, K_t, matches, valid, counts, inliers, max_depth, min_parallax, ctx)
+    op, ov, oc = outputs(POINT_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_triangulate(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v), ptr(gm),
+                                    ptr(ii), ptr(op), ptr(ov), ptr(oc), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return PointsResult(op, ov, oc)
+
+
+def recover_pose(q_xy, t_xy, result: GeometryResult, K, K_t=None, matches=None, valid=None, counts=None,
+                 max_depth: float = math.inf, min_parallax: float = 1e-3, out=None, ctx: Context | None = None) -> PoseResult:
+    """fd_pose_recover: the relative camera pose of a fundamental matrix and the 3-D points of its inliers, the
+    step after verify_geometry / refit_geometry (model="fundamental") in a VIO / SLAM front end.
+
+    q_xy, t_xy, matches, valid and counts are verify_geometry's: pass the same ones. result: what
+    verify_geometry or refit_geometry returned (its model float64 [B, 9] and inliers uint8 [B, S], on the side
+    of q_xy). K, K_t, max_depth and min_parallax: as in triangulate. Of the four poses an essential matrix
+    allows, the one with the most inliers in front of both cameras wins (the lowest index among equals).
+
+    Returns a PoseResult: pose float64 [B, 12] (R row-major, then t of unit length; X_t = R X_q + t), choice
+    int32 [B] (-1 and a zero pose: no pose, e.g. a zero or rank-1 model, a pure rotation, no inlier in front),
+    and the winner's points, valid and counts. Host and device inputs and out= (pose float64 [B, 12], choice
+    int32 [B], points float32 [B, S, 3], valid uint8 [B, S], counts int32 [B]) behave as in verify_geometry.
+    """
+    ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii = _pose_call(
+        q_xy, t_xy, result.model, "result", 9, K, K_t, matches, valid, counts, result.inliers, max_depth, min_parallax, ctx)
+    oo, och, op, ov, oc = outputs((((b, 12), "float64", 0), ((b,), "int32", 0)) + POINT_SPECS(b, s), out, on_dev,
+                                  pq.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_pose_recover(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v), ptr(gm),
+                                     ptr(ii), ptr(oo), ptr(och), ptr(op), ptr(ov), ptr(oc), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return PoseResult(op, ov, oc, oo, och)

@@ -846,6 +846,91 @@ int fd_ransac_refit(fd_ctx *ctx, int batch, const fd_refit_opts *opts,
                     double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
                     int io_on_device);
 
+/* ---- Relative pose from a fundamental matrix, and triangulation (MI355X extension) --------------------- */
+/* Jacobi sweeps of fd_pose_recover. Found on the CPU with the restatement (tests/pose_ref.py) by
+ * FD_REFIT_SWEEPS's rule: over every scene of tests/test_pose_host.py and tests/test_gpu_pose.py the diagonal and
+ * V of E^T E change no bit after 5 sweeps; the rule adds 2 (tests/test_pose_host.py::test_sweep_count_rule). */
+#define FD_POSE_SWEEPS 7
+
+typedef struct fd_pose_opts {
+    double fx_q, fy_q, cx_q, cy_q; /* zero-skew pinhole camera of the q image: finite, fx and fy non-zero */
+    double fx_t, fy_t, cx_t, cy_t; /* the t image's */
+    float max_depth;    /* > 0, +inf allowed: the largest accepted depth along either ray, in units of |t| */
+    float min_parallax; /* 0..1: the sine of the smallest accepted angle between the two rays */
+} fd_pose_opts;
+
+/*
+ * fd_triangulate and fd_pose_recover -- what a front end verifies matches or tracks for: the relative camera
+ * pose (R, t), X_t = R X_q + t, from the fundamental matrix of fd_ransac / fd_ransac_refit, and the 3-D
+ * points of the inliers in the q camera's frame. Definite sequences like fd_ransac's, with its conventions:
+ * all floating point double, every operation rounded once, no contraction, f64 division and square root
+ * correctly rounded. No lens distortion (undistort or warp first), no five-point solver, no PnP.
+ *
+ * q_xy, q_counts, q_stride, t_xy, t_stride, match_idx, pair_valid: fd_ransac's, with its rules for which
+ * slots are correspondences. Coordinates are plain pixels, x = (double)q.x: no conditioning transform.
+ * Normalised rays: ax = (x - cx_q) / fx_q, ay = (y - cy_q) / fy_q, and (bx, by) the same of t_xy[j] with the t
+ * camera.
+ *
+ * The step, per correspondence and pose (R row-major, t):
+ *   r[i] = R[i][0]*ax + R[i][1]*ay + R[i][2] (left to right);  p' = (bx, by, 1)
+ *   rr = r.r, pp = p'.p', rp = r.p', rt = r.t, pt = p'.t, each a left-to-right sum of three products
+ *   det = rr*pp - rp*rp;  z1 = (rp*pt - pp*rt) / det;  z2 = (rr*pt - rp*rt) / det
+ * (the depths along the two rays that minimise |z1 r - z2 p' + t|). The point is in front iff
+ *   det > (m*m) * (rr*pp), m = (double)min_parallax;  z1 > 0;  z2 > 0;  z1 <= D;  z2 <= D, D = (double)max_depth
+ * (a NaN fails every compare). The 3-D point is (z1*ax, z1*ay, z1), each component rounded once to float.
+ *
+ * fd_triangulate, a known pose (a calibrated stereo rig behind fd_flow_lk, or a pose from elsewhere).
+ * in_pose double [batch][12]: R row-major, then t, of any scale. in_inlier uint8 [batch][q_stride] (NULL: every
+ * correspondence): only the slots whose byte is exactly 1 take part. out_points float [batch][q_stride][3],
+ * out_valid uint8 [batch][q_stride]: 1 and the point for a participating correspondence that is in front; 0
+ * and a zero point for every other slot below q_counts[b]; slots >= q_counts[b] are not written. out_counts
+ * int32 [batch]: the ones. Each of the three may be NULL. q_stride 0: out_counts = 0.
+ *
+ * fd_pose_recover. in_model double [batch][9]: a fundamental matrix with (u, v, 1) F (x, y, 1)^T = 0, (u, v)
+ * from t_xy (fd_ransac's out_model); in_inlier as above, required.
+ * 1. E = K_t^T (F K_q), K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]: both products plain triple loops, each sum
+ *    from 0.0 with the inner index ascending.
+ * 2. G[i][j] = sum over k ascending from 0.0 of E[k][i]*E[k][j]; fd_ransac_refit's cyclic Jacobi on G (n = 3,
+ *    V = identity), FD_POSE_SWEEPS sweeps; d = the diagonal; j = the index of its smallest entry (strict < from
+ *    entry 0), a < b the other two; v1 = V[:, a], v2 = V[:, b].
+ * 3. w1 = E v1, w2 = E v2 (rows summed left to right); u1 = w1 / sqrt(w1.w1), u2 = w2 / sqrt(w2.w2) (the dot
+ *    products left to right); u3 = u1 x u2, v3 = v1 x v2, every component a*b - c*d with both products rounded
+ *    first: (u1, u2, u3) and (v1, v2, v3) are right-handed, so no determinant needs a sign fix.
+ * 4. Ra[i][k] = (u2[i]*v1[k] - u1[i]*v2[k]) + u3[i]*v3[k];  Rb[i][k] = (u1[i]*v2[k] - u2[i]*v1[k]) + u3[i]*v3[k].
+ *    Candidates: 0 (Ra, +u3), 1 (Ra, -u3), 2 (Rb, +u3), 3 (Rb, -u3).
+ *    There is no pose unless d, v1, v2, u3, Ra and Rb are all finite and min(d[a], d[b]) > 1e-12 * max(d): a zero
+ *    model and a model of rank 1 have none.
+ * 5. Every correspondence whose in_inlier byte is exactly 1 runs the step for the four candidates; c_k = the
+ *    number in front. The winner is the largest c_k, the lowest k among equals; c_k = 0: no pose. A pure
+ *    rotation has a rank-2 E but parallel rays: with min_parallax > 0 no candidate has a point.
+ * out_pose double [batch][12]: the winner's R, then its t (|t| = 1 to rounding); twelve zeros without a pose.
+ * out_choice int32 [batch]: 0..3, or -1. out_points, out_valid, out_counts: fd_triangulate's, for the winner and
+ * the in_inlier set; without a pose zeros below q_counts[b]. Every output may be NULL. q_stride 0: out_counts =
+ * 0, out_choice = -1, a zero pose.
+ *
+ * Device pointers when io_on_device: asynchronous on the context's stream (one kernel, no workspace: always
+ * graph-capturable). Host pointers otherwise: staged through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, q_xy, t_xy, in_pose (fd_triangulate), in_model or in_inlier (fd_pose_recover)
+ * NULL; batch < 1; a negative stride; match_idx NULL with t_stride < q_stride; a camera value not finite, fx
+ * or fy zero; max_depth not > 0 (a NaN included); min_parallax outside 0..1.
+ */
+int fd_triangulate(fd_ctx *ctx, int batch, const fd_pose_opts *opts,
+                   const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+                   const float *t_xy, int32_t t_stride,
+                   const int32_t *match_idx, const uint8_t *pair_valid,
+                   const double *in_pose, const uint8_t *in_inlier,
+                   float *out_points, uint8_t *out_valid, int32_t *out_counts,
+                   int io_on_device);
+
+int fd_pose_recover(fd_ctx *ctx, int batch, const fd_pose_opts *opts,
+                    const float *q_xy, const int32_t *q_counts, int32_t q_stride,
+                    const float *t_xy, int32_t t_stride,
+                    const int32_t *match_idx, const uint8_t *pair_valid,
+                    const double *in_model, const uint8_t *in_inlier,
+                    double *out_pose, int32_t *out_choice,
+                    float *out_points, uint8_t *out_valid, int32_t *out_counts,
+                    int io_on_device);
+
 /* ---- Image warp by a homography or a camera model (MI355X extension) --------------------------------- */
 #define FD_WARP_HOMOGRAPHY 0 /* params: double[9], row-major 3 x 3, fd_ransac's out_model layout */
 #define FD_WARP_CAMERA 1     /* params: double[22], below */

@@ -5,12 +5,14 @@
 // a front end hands to DetectGoodFeatures(image, need, features) as the features it already has. The
 // semantics, a definite arithmetic sequence (a counter-based sampler, a fixed number of hypotheses that are
 // all evaluated, one solve in double each), are those of fd_ransac (include/fd_hip.h): the model is the
-// best minimal-sample model, not a refit.
+// best minimal-sample model, not a refit. Refit refits it (fd_ransac_refit); RecoverPose and Triangulate turn a
+// fundamental matrix into the relative camera pose and the inliers' 3-D points (fd_pose_recover, fd_triangulate).
 #ifndef FEATURE_DETECTOR_GEOMETRIC_VERIFIER_H_
 #define FEATURE_DETECTOR_GEOMETRIC_VERIFIER_H_
 
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -72,6 +74,43 @@ public:
                std::array<double, 9> &model, int32_t rounds = 2, const std::vector<int32_t> *train_index = nullptr,
                const std::vector<uint8_t> *valid = nullptr, int32_t *accepted_rounds = nullptr);
 
+    // A zero-skew pinhole camera, and what a triangulated point must satisfy.
+    struct Camera {
+        double fx = 1.0, fy = 1.0, cx = 0.0, cy = 0.0;
+    };
+    struct PoseOptions {
+        float kMaxDepth = std::numeric_limits<float>::infinity();  // no limit; the largest depth along either ray, in units of |t|
+        float kMinParallax = 1e-3f;              // the sine of the smallest accepted angle between the two rays
+    };
+
+    // The relative camera pose of Verify's / Refit's fundamental matrix and the 3-D points of its inliers
+    // (fd_pose_recover of include/fd_hip.h). query_uv, train_uv, train_index and valid are what Verify took,
+    // inlier and model what it (or Refit) returned. pose: R row-major, then t of unit length, X_train = R X_query
+    // + t: of the four poses the matrix allows, the one with the most inliers in front of both cameras.
+    // points[i] (query camera frame, in units of |t|) and point_valid[i] = 1 for every inlier in front; zeros
+    // elsewhere. choice (optional): the winning candidate 0..3.
+    // False, with a zero pose and no valid point, when there is no pose (a zero or rank-1 model, a pure rotation,
+    // no inlier in front), for no query points, an inlier, train_index or valid of the wrong size, fewer train
+    // than query points without train_index, a camera or option out of range, or a libfdhip failure.
+    bool RecoverPose(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, const std::vector<uint8_t> &inlier,
+                     const std::array<double, 9> &model, const Camera &query_camera, const Camera &train_camera,
+                     std::array<double, 12> &pose, std::vector<std::array<float, 3>> &points, std::vector<uint8_t> &point_valid,
+                     const std::vector<int32_t> *train_index = nullptr, const std::vector<uint8_t> *valid = nullptr,
+                     int32_t *choice = nullptr);
+
+    // The 3-D points of the correspondences under a known pose (fd_triangulate): a calibrated stereo rig behind
+    // OpticalFlowLK, or a pose from elsewhere; t of any length sets the unit. inlier (optional): only the points
+    // flagged exactly 1 take part. count (optional): the valid points. False for the size and range errors of
+    // RecoverPose or a libfdhip failure.
+    bool Triangulate(const std::vector<Vec2> &query_uv, const std::vector<Vec2> &train_uv, const std::array<double, 12> &pose,
+                     const Camera &query_camera, const Camera &train_camera, std::vector<std::array<float, 3>> &points,
+                     std::vector<uint8_t> &point_valid, const std::vector<uint8_t> *inlier = nullptr,
+                     const std::vector<int32_t> *train_index = nullptr, const std::vector<uint8_t> *valid = nullptr,
+                     int32_t *count = nullptr);
+
+    PoseOptions &pose_options() { return pose_options_; }
+    const PoseOptions &pose_options() const { return pose_options_; }
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -82,6 +121,7 @@ public:
 
 private:
     Options options_;
+    PoseOptions pose_options_;
     DeviceContext context_;
 };
 

@@ -18,7 +18,8 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      frame i's refined corners into frame i + 1, 10 calls
   --shape fastverify FAST (need 500, dist 15) + BRIEF-256 on the 64 frames of fastflow's moving scene, fd_brief_match of
                      frame i against frame i + 1 and fd_ransac (256 hypotheses, threshold 1 px) on the matches, the
-                     fundamental matrix and then the homography, 10 calls (--refit: fd_ransac_refit, rounds 2, after each)
+                     fundamental matrix and then the homography, 10 calls (--refit: fd_ransac_refit, rounds 2, after each;
+                     --pose: fd_pose_recover and fd_triangulate on the fundamental matrix)
   --shape warp       fd_frames_warp with a mask, on device tensors: a rotation by 3 degrees with scale 1.02 and a mild
                      perspective (homography), then a barrel-distortion camera model, at 1920x1080 batch 64 (10
                      calls each) and at 640x480 batch 1 (200 calls each), destination shape = source shape
@@ -67,6 +68,8 @@ p.add_argument("--calls", type=int, default=0)
 p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
 p.add_argument("--fb", action="store_true", help="fastflow: track with the forward-backward check")
 p.add_argument("--refit", action="store_true", help="fastverify: fd_ransac_refit (rounds 2) on each model after fd_ransac")
+p.add_argument("--pose", action="store_true",
+               help="fastverify: fd_pose_recover on the fundamental matrix (the refit one with --refit), then fd_triangulate with its pose")
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
 p.add_argument("--warp-size", default="both", choices=["both", "hd", "vga"], help="warp: one of the two shapes (a trace per shape)")
 p.add_argument("--eq-size", default="all", choices=["all", "vga1", "vga64", "hd"], help="equalize: one of the three shapes (a trace per shape)")
@@ -209,7 +212,8 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
     base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
     base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)
     frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
-    out, refit = None, {}
+    out, refit, pose, tri = None, {}, None, None
+    cam = (1000.0, 1000.0, 639.5, 359.5)
     for _ in range(a.calls or 10):
         res = fd.detect_points(kind, frames, 500, 15, THR[kind])
         if out is None:
@@ -229,6 +233,19 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
                 fd.refit_geometry(res.xy[:-1], res.xy[1:], fd.GeometryResult(*o), matches=out[0], counts=res.counts[:-1],
                                   model=model, rounds=2, threshold=1.0, image_size=(720, 1280),
                                   out=refit.setdefault(model, tuple(torch.empty_like(x) for x in o)))
+            if a.pose and model == "fundamental":
+                given = fd.GeometryResult(*(refit[model] if a.refit else o))
+                if pose is None:
+                    pose = (torch.empty((63, 12), dtype=torch.float64, device="cuda"), torch.empty((63,), dtype=torch.int32, device="cuda"),
+                            torch.empty((63, s, 3), dtype=torch.float32, device="cuda"), torch.empty((63, s), dtype=torch.uint8, device="cuda"),
+                            torch.empty((63,), dtype=torch.int32, device="cuda"))
+                    tri = tuple(torch.empty_like(x) for x in pose[2:])
+                fd.recover_pose(res.xy[:-1], res.xy[1:], given, cam, matches=out[0], counts=res.counts[:-1], out=pose)
+                fd.triangulate(res.xy[:-1], res.xy[1:], pose[0], cam, matches=out[0], counts=res.counts[:-1], inliers=given.inliers,
+                               out=tri)
+    if a.pose:
+        print("frames with a pose:", int((pose[1] >= 0).sum()), "points in front per pair (mean):", float(pose[4].float().mean()),
+              "triangulated (mean):", float(tri[2].float().mean()))
     if a.refit:
         print("refit inliers F / H (mean):", *(float(refit[m][2].float().mean()) for m in ("fundamental", "homography")),
               "accepted rounds F / H (mean):", *(float(refit[m][3].float().mean()) for m in ("fundamental", "homography")))
