@@ -165,4 +165,82 @@ bool GeometricVerifier::Triangulate(const std::vector<Vec2> &query_uv, const std
     return true;
 }
 
+namespace {
+
+// The size checks SolvePnP and RefinePnP share; nullptr when the arguments fit.
+const char *PnpSizes(size_t n, size_t images, const std::vector<uint8_t> *point_valid, const std::vector<int32_t> *image_index,
+                     const std::vector<uint8_t> *valid) {
+    if (n == 0) return "no points";
+    if (point_valid && point_valid->size() != n) return "one point_valid flag per point is needed";
+    if (image_index && image_index->size() != n) return "one image index per point is needed";
+    if (valid && valid->size() != n) return "one valid flag per point is needed";
+    if (!image_index && images < n) return "without image_index every point needs its image position";
+    return nullptr;
+}
+
+fd_pnp_opts PnpOpts(const GeometricVerifier::PnpOptions &o, const GeometricVerifier::Camera &c, int32_t rounds) {
+    return fd_pnp_opts{o.kHypotheses, o.kSeed, rounds, o.kThreshold, c.fx, c.fy, c.cx, c.cy,
+                       {o.kCenter[0], o.kCenter[1], o.kCenter[2]}, o.kScale};
+}
+
+}  // namespace
+
+bool GeometricVerifier::SolvePnP(const std::vector<std::array<float, 3>> &points, const std::vector<Vec2> &image_uv,
+                                 const Camera &camera, std::array<double, 12> &pose, std::vector<uint8_t> &inlier,
+                                 const std::vector<uint8_t> *point_valid, const std::vector<int32_t> *image_index,
+                                 const std::vector<uint8_t> *valid, int32_t *best_hypothesis) {
+    const size_t n = points.size();
+    pose.fill(0.0);
+    inlier.assign(n, 0);
+    if (best_hypothesis) *best_hypothesis = -1;
+    if (const char *why = PnpSizes(n, image_uv.size(), point_valid, image_index, valid))
+        return context_.Fail(std::string("SolvePnP: ") + why);
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    std::vector<float> t = Flatten(image_uv);
+    t.resize(t.size() + 2);  // two floats of padding behind the image positions
+    const fd_pnp_opts o = PnpOpts(pnp_options_, camera, 1);
+    int32_t best = -1;
+    const int rc = fd_pnp_ransac(ctx, 1, &o, points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
+                                 static_cast<int32_t>(n), t.data(), static_cast<int32_t>(image_uv.size()),
+                                 image_index ? image_index->data() : nullptr, valid ? valid->data() : nullptr, pose.data(),
+                                 inlier.data(), nullptr, &best, 0);
+    if (rc != FD_OK) {
+        pose.fill(0.0);
+        inlier.assign(n, 0);
+        return context_.FailCall("fd_pnp_ransac");
+    }
+    if (best < 0) return context_.Fail("SolvePnP: no pose (fewer than 6 correspondences, or every sample degenerate)");
+    if (best_hypothesis) *best_hypothesis = best;
+    return true;
+}
+
+bool GeometricVerifier::RefinePnP(const std::vector<std::array<float, 3>> &points, const std::vector<Vec2> &image_uv,
+                                  const Camera &camera, std::array<double, 12> &pose, std::vector<uint8_t> &inlier, int32_t rounds,
+                                  const std::vector<uint8_t> *point_valid, const std::vector<int32_t> *image_index,
+                                  const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
+    const size_t n = points.size();
+    if (accepted_rounds) *accepted_rounds = 0;
+    if (const char *why = PnpSizes(n, image_uv.size(), point_valid, image_index, valid))
+        return context_.Fail(std::string("RefinePnP: ") + why);
+    if (inlier.size() != n) return context_.Fail("RefinePnP: one inlier flag per point is needed");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    std::vector<float> t = Flatten(image_uv);
+    t.resize(t.size() + 2);  // two floats of padding behind the image positions
+    const fd_pnp_opts o = PnpOpts(pnp_options_, camera, rounds);
+    std::vector<uint8_t> out_inlier(n);
+    double p[12];
+    int32_t accepted = 0;
+    const int rc = fd_pnp_refit(ctx, 1, &o, points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
+                                static_cast<int32_t>(n), t.data(), static_cast<int32_t>(image_uv.size()),
+                                image_index ? image_index->data() : nullptr, valid ? valid->data() : nullptr, pose.data(),
+                                inlier.data(), p, out_inlier.data(), nullptr, &accepted, 0);
+    if (rc != FD_OK) return context_.FailCall("fd_pnp_refit");
+    inlier.swap(out_inlier);
+    std::copy(p, p + 12, pose.begin());
+    if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
 }  // namespace feature_detector

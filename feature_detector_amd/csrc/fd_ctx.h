@@ -63,7 +63,7 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs) and fd_pose_recover (7 and 5)
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs), fd_pose_recover (7 and 5) and fd_pnp_refit (8 and 4)
     static constexpr int kStaging = 12;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
@@ -74,7 +74,8 @@ struct fd_ctx {
     fdrt::DevBuf f_bxy, f_bst;
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
-    // per-frame best-hypothesis words; fd_ransac_refit: the support sets by list position ([batch][2][q_stride] bytes)
+    // per-frame best-hypothesis words; fd_ransac_refit: the support sets by list position ([batch][2][q_stride] bytes).
+    // fd_pnp_ransac and fd_pnp_refit use the same buffers with 5 doubles per correspondence and 12 per hypothesis
     fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best, g_member;
     // fd_frames_equalize: the tiles' LUTs ([batch][tiles_y][tiles_x][256] bytes), then the columns' and rows'
     // interpolation entries ([cols + rows] words)

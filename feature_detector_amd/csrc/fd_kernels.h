@@ -489,6 +489,42 @@ struct PoseArgs {
     int32_t *out_counts;         // [batch] or null
 };
 
+// Absolute pose from 3-D points (fd_pnp.hip; fd_pnp_ransac and fd_pnp_refit of include/fd_hip.h): one block for
+// its kernels. k_pnp_compact fills corr, cidx, n and zeroes best; k_pnp_hyp fills models and raises best;
+// k_pnp_finish writes the outputs.
+struct PnpArgs {
+    const float *p_xyz, *t_xy;   // [batch][q_stride][3], [batch][t_stride][2]
+    const uint8_t *p_valid;      // [batch][q_stride] or null; only a byte equal to 1 takes part
+    const int32_t *q_counts;     // [batch] or null (= q_stride); bits 25..31 ignored
+    const int32_t *match_idx;    // [batch][q_stride] or null (slot i pairs with slot i)
+    const uint8_t *pair_valid;   // [batch][q_stride] or null; only a byte equal to 1 takes part
+    int batch, q_stride, t_stride;
+    int hypotheses;              // 1..4096
+    uint32_t seed;
+    double cam[4];               // fx, fy, cx, cy of the t image
+    double center[3], scale;     // the conditioning of the 3-D points (fd_pnp_refit: 0 and 1)
+    double tt;                   // (double)threshold squared
+    double *corr;                // [batch][q_stride][5] (Xc, Yc, Zc, bx, by) of the correspondences, in slot order
+    int32_t *cidx;               // [batch][q_stride] a slot's index in corr, or -1
+    int32_t *n;                  // [batch] correspondences
+    double *models;              // [batch][hypotheses][12] camera matrices of the conditioned points
+    unsigned long long *best;    // [batch] as RansacArgs::best
+    double *out_pose;            // [batch][12]
+    uint8_t *out_inlier;         // [batch][q_stride] or null
+    int32_t *out_counts, *out_best;  // [batch] or null
+};
+
+// k_pnp_compact runs on `r` (hypotheses, seed, models, out_best unused); k_pnp_refit reads r's lists and writes
+// r.out_pose, r.out_inlier, r.out_counts.
+struct PnpRefitArgs {
+    PnpArgs r;
+    const double *in_pose;       // [batch][12]; may be r.out_pose
+    const uint8_t *in_inlier;    // [batch][q_stride]; only a byte equal to 1 is a member; may be r.out_inlier
+    uint8_t *member;             // [batch][2][q_stride] workspace: membership by list position, current and candidate
+    int rounds;                  // 1..8
+    int32_t *out_rounds;         // [batch] or null
+};
+
 // Image warp (fd_warp.hip): every destination pixel of out [batch][out_rows][out_cols] sampled from the frames
 // [batch][rows][cols] at the position a per-frame model gives (fd_frames_warp of include/fd_hip.h).
 struct WarpArgs {
@@ -552,6 +588,10 @@ hipError_t launch_ransac_refit(const RefitArgs &a, hipStream_t s);
 hipError_t launch_pose_recover(const PoseArgs &a, hipStream_t s);
 // a memset of out_counts, then k_triangulate (q_stride >= 1)
 hipError_t launch_triangulate(const PoseArgs &a, hipStream_t s);
+// k_pnp_compact, k_pnp_hyp, k_pnp_finish
+hipError_t launch_pnp_ransac(const PnpArgs &a, hipStream_t s);
+// k_pnp_compact, then k_pnp_refit (all rounds in one launch)
+hipError_t launch_pnp_refit(const PnpRefitArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);

@@ -25,115 +25,19 @@
 // the slots t, t + 256, ... with four counts in registers, the workgroup picks the winner, and a second walk
 // writes the points. k_triangulate (fd_triangulate), one thread per slot, runs the same step for a given pose.
 // Neither needs k_ransac_compact: nothing in them depends on a correspondence's number in the list.
-#include "fd_hip.h"
-#include "fd_window.h"
+//
+// The sampler, the elimination, the Jacobi routine and the small products are fd_solve.h's, shared with fd_pnp.hip.
+#include "fd_solve.h"
 
 namespace fdk {
 namespace {
 
-constexpr int kRansacThreads = 256;  // k_ransac_compact, k_ransac_finish
-constexpr int kTile = 256;           // correspondences per LDS tile of the scoring loop (8 KiB)
 constexpr int kFundamental = 0;      // FD_RANSAC_FUNDAMENTAL
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t mix(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-// The M distinct picks of hypothesis h of frame f among n correspondences; false when there are fewer
-// than M or a pick found no new index in 32 tries.
-template <int M>
-__device__ __forceinline__ bool sample(uint32_t seed, int f, int h, int n, int (&pick)[M]) {
-#pragma unroll
-    for (int k = 0; k < M; ++k) pick[k] = 0;
-    if (n < M) return false;
-    const uint32_t base = mix(mix(seed + 0x9E3779B9u * static_cast<uint32_t>(f)) + static_cast<uint32_t>(h));
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-        bool found = false;
-        for (int a = 0; a < 32 && !found && ok; ++a) {
-            const int idx = static_cast<int>(__umulhi(mix(base + 32u * k + a), static_cast<uint32_t>(n)));
-            bool dup = false;
-#pragma unroll
-            for (int j = 0; j < k; ++j) dup |= pick[j] == idx;
-            if (!dup) {
-                pick[k] = idx;
-                found = true;
-            }
-        }
-        ok = ok && found;
-    }
-    return ok;
-}
-
 // Element (r, c) of a lane's 8 x 9 system: A points at the lane's column of the [element][lane] array.
-__device__ __forceinline__ double &el(double *A, int r, int c) { return A[(9 * r + c) * kWave]; }
-
-// Null vector of the lane's system by Gaussian elimination with complete pivoting, into x; false for a
-// pivot that fails the relative test or a non-finite result. Destroys the system.
-__device__ __forceinline__ bool null_vector(double *A, double (&x)[9]) {
-    uint64_t perm = 0x876543210ull;  // nibble c: the original column now at position c
-    bool ok = true;
-    double p0 = 0.0;
-    for (int k = 0; k < 8; ++k) {
-        double best = -1.0;
-        int pr = k, pc = k;
-        for (int r = k; r < 8; ++r)
-            for (int c = k; c < 9; ++c) {
-                const double m = fabs(el(A, r, c));
-                if (m > best) {  // false for a NaN
-                    best = m;
-                    pr = r;
-                    pc = c;
-                }
-            }
-        if (k == 0) p0 = best;
-        ok = ok && best > 1e-12 * p0;
-        for (int c = k; c < 9; ++c) {  // the columns left of k are never read again
-            const double t = el(A, k, c);
-            el(A, k, c) = el(A, pr, c);
-            el(A, pr, c) = t;
-        }
-        for (int r = 0; r < 8; ++r) {
-            const double t = el(A, r, k);
-            el(A, r, k) = el(A, r, pc);
-            el(A, r, pc) = t;
-        }
-        const uint64_t nk = (perm >> (4 * k)) & 15u, nc = (perm >> (4 * pc)) & 15u;
-        perm = (perm & ~(15ull << (4 * k))) | (nc << (4 * k));
-        perm = (perm & ~(15ull << (4 * pc))) | (nk << (4 * pc));
-        const double piv = el(A, k, k);
-        for (int r = k + 1; r < 8; ++r) {
-            const double f = el(A, r, k) / piv;
-            for (int c = k + 1; c < 9; ++c) el(A, r, c) = el(A, r, c) - f * el(A, k, c);
-        }
-    }
-    double y[9];
-    y[8] = 1.0;
-#pragma unroll
-    for (int k = 7; k >= 0; --k) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = k + 1; c < 9; ++c) s = s + el(A, k, c) * y[c];
-        y[k] = (0.0 - s) / el(A, k, k);
-    }
-    // undo the column permutation through the (now free) first elements of the lane's column
-#pragma unroll
-    for (int c = 0; c < 9; ++c) A[static_cast<int>((perm >> (4 * c)) & 15u) * kWave] = y[c];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) {
-        x[c] = A[c * kWave];
-        ok = ok && isfinite(x[c]);
-    }
-    return ok;
-}
+__device__ __forceinline__ double &el(double *A, int r, int c) { return fdk::el<8, kWave>(A, r, c); }
 
 // The inlier test of a conditioned model h on a conditioned correspondence p = (x, y, u, v): the Sampson
 // distance (F) or the forward transfer error (H) against tt = t * t, without a division. A NaN fails.
@@ -244,7 +148,7 @@ __global__ __launch_bounds__(kWave) void k_ransac_hyp(RansacArgs a) {
         }
     }
     double x[9];
-    ok = null_vector(A, x) && ok;
+    ok = null_vector<8, kWave>(A, x) && ok;
 
     int count = 0;
     for (int base = 0; base < n; base += kTile) {  // n is the frame's: uniform over the workgroup
@@ -264,19 +168,6 @@ __global__ __launch_bounds__(kWave) void k_ransac_hyp(RansacArgs a) {
     const uint32_t top = wave_max_u32(hi);
     const uint32_t lo = wave_max_u32(hi == top ? 0xFFFFFFFFu - static_cast<uint32_t>(h) : 0u);
     if (lane == 0 && top) atomicMax(a.best + f, (static_cast<unsigned long long>(top) << 32) | lo);
-}
-
-// out = a * b, 3 x 3 row-major, every sum from 0.0 with the inner index ascending.
-__device__ __forceinline__ void matmul3(const double (&a)[9], const double (&b)[9], double (&out)[9]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) acc = acc + a[3 * i + k] * b[3 * k + j];
-            out[3 * i + j] = acc;
-        }
 }
 
 // The pixel-coordinate model of the conditioned one x, divided by its entry of largest magnitude, into om[9]
@@ -361,73 +252,6 @@ __device__ __forceinline__ void add_row(double (&acc)[kNormal], const double (&r
     for (int i = 0; i < 9; ++i)
 #pragma unroll
         for (int j = i; j < 9; ++j, ++e) acc[e] = acc[e] + r[i] * r[j];
-}
-
-// The workgroup's sum of one count per thread.
-__device__ __forceinline__ int wg_count(uint32_t mine, int *total) {
-    __syncthreads();
-    if (threadIdx.x == 0) *total = 0;
-    __syncthreads();
-    const uint32_t wave_n = wave_total_add(mine);
-    if (lane_id() == 0 && wave_n) atomicAdd(total, static_cast<int>(wave_n));
-    __syncthreads();
-    return *total;
-}
-
-// Cyclic Jacobi of the contract on one wave. m holds 2 N rows of N doubles in LDS: the symmetric matrix, then
-// V. Lane r < 2 N owns row r: every element update of a rotation is an expression of the values before it,
-// so the lanes read their two elements, then write them (the matrix rows mirrored into the columns), and the
-// result is the serial restatement's bit for bit. The dependent chain of a rotation (two divisions, two square
-// roots) is computed by every lane alike; p, q and the skip are wave-uniform.
-template <int N, int SWEEPS>
-__device__ __forceinline__ void jacobi(double *m, int lane) {
-    const bool live = lane < 2 * N, sym = lane < N;
-    const int r = live ? lane : 0;
-    for (int sweep = 0; sweep < SWEEPS; ++sweep)
-        for (int p = 0; p < N - 1; ++p)
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = m[p * N + q];
-                if (apq == 0.0) continue;
-                const double app = m[p * N + p], aqq = m[q * N + q];
-                const double xp = m[r * N + p], xq = m[r * N + q];
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0);
-                const double s = t * c;
-                double np = c * xp - s * xq, nq = s * xp + c * xq;
-                if (sym && r == p) {
-                    np = app - t * apq;
-                    nq = 0.0;
-                }
-                if (sym && r == q) {
-                    np = 0.0;
-                    nq = aqq + t * apq;
-                }
-                wave_lds_sync();
-                if (live) {
-                    m[r * N + p] = np;
-                    m[r * N + q] = nq;
-                }
-                if (sym) {
-                    m[p * N + r] = np;
-                    m[q * N + r] = nq;
-                }
-                wave_lds_sync();
-            }
-}
-
-// Index of the smallest of d: a strict < from entry 0.
-template <int N>
-__device__ __forceinline__ int smallest(const double (&d)[N]) {
-    int at = 0;
-    double best = d[0];
-#pragma unroll
-    for (int i = 1; i < N; ++i)
-        if (d[i] < best) {
-            best = d[i];
-            at = i;
-        }
-    return at;
 }
 
 // One workgroup per frame, all rounds. The support set lives in global memory by list position, the current
@@ -626,10 +450,6 @@ __device__ __forceinline__ bool pose_rays(const PoseArgs &a, int f, int64_t s0, 
     bx = (static_cast<double>(t.x) - a.cam[6]) / a.cam[4];
     by = (static_cast<double>(t.y) - a.cam[7]) / a.cam[5];
     return isfinite(q.x) && isfinite(q.y) && isfinite(t.x) && isfinite(t.y);
-}
-
-__device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-    return a0 * b0 + a1 * b1 + a2 * b2;
 }
 
 // The contract's step for the pose (R, t): whether the point is in front, and its depth z1 along (ax, ay, 1).

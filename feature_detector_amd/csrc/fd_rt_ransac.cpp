@@ -1,6 +1,7 @@
 // Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac), the least-squares
 // refit of its model (fd_ransac_refit), the pose of a fundamental matrix (fd_pose_recover) and triangulation
-// (fd_triangulate) over the kernels of fd_ransac.hip.
+// (fd_triangulate) over the kernels of fd_ransac.hip, and the absolute pose from 3-D points (fd_pnp_ransac,
+// fd_pnp_refit) over those of fd_pnp.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -85,9 +86,150 @@ int pose_pairs(fd_ctx *c, HostIo &io, fdk::PoseArgs &a, const float *q_xy, const
     return FD_OK;
 }
 
+// What fd_pnp_ransac and fd_pnp_refit ask of the arguments they share, the fields both fill alike, and the
+// workspace of k_pnp_compact. The conditioning is the caller's (fd_pnp_ransac) or none (fd_pnp_refit).
+int pnp_args(fd_ctx *c, fdk::PnpArgs &a, int batch, const fd_pnp_opts *o, int32_t q_stride, int32_t t_stride,
+             const int32_t *match_idx, bool conditioned) {
+    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
+    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
+    if (!match_idx && t_stride < q_stride)
+        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
+    if (!std::isfinite(o->threshold) || !(o->threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    const double cam[4] = {o->fx, o->fy, o->cx, o->cy};
+    for (int k = 0; k < 4; ++k) {
+        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
+        a.cam[k] = cam[k];
+    }
+    if (cam[0] == 0.0 || cam[1] == 0.0) return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
+    for (int k = 0; k < 3; ++k) {
+        if (conditioned && !std::isfinite(o->center[k])) return fail(c, FD_ERR_INVALID, "center must be finite");
+        a.center[k] = conditioned ? o->center[k] : 0.0;
+    }
+    if (conditioned && (!std::isfinite(o->scale) || !(o->scale > 0.0))) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    a.scale = conditioned ? o->scale : 1.0;
+    a.batch = batch;
+    a.q_stride = q_stride;
+    a.t_stride = t_stride;
+    const double t = static_cast<double>(o->threshold);
+    a.tt = t * t;
+    return FD_OK;
+}
+
+int pnp_workspace(fd_ctx *c, fdk::PnpArgs &a) {
+    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
+    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 5 * qs, a.corr));
+    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
+    FD_HIP_TRY(c, ensure_as(c, c->g_n, a.batch, a.n));
+    FD_HIP_TRY(c, ensure_as(c, c->g_best, a.batch, a.best));
+    return FD_OK;
+}
+
+// The input arrays of both calls, staged or handed on.
+int pnp_inputs(fd_ctx *c, HostIo &io, fdk::PnpArgs &a, const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts,
+               const float *t_xy, const int32_t *match_idx, const uint8_t *pair_valid) {
+    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride, ts = static_cast<size_t>(a.batch) * a.t_stride;
+    FD_HIP_TRY(c, io.in(p_xyz, 3 * qs, a.p_xyz));
+    FD_HIP_TRY(c, io.in(p_valid, qs, a.p_valid));
+    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
+    FD_HIP_TRY(c, io.in(q_counts, a.batch, a.q_counts));
+    FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
+    FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
+    return FD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fd_pnp_ransac(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_xyz, const uint8_t *p_valid,
+                  const int32_t *q_counts, int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx,
+                  const uint8_t *pair_valid, double *out_pose, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
+                  int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !p_xyz || !t_xy || !out_pose) return fail(c, FD_ERR_INVALID, "bad arguments");
+    fdk::PnpArgs a{};
+    int rc = pnp_args(c, a, batch, opts, q_stride, t_stride, match_idx, true);
+    if (rc) return rc;
+    if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
+        return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    const size_t poses = static_cast<size_t>(12) * batch;
+    if (q_stride == 0) {  // no slots: no frame has a pose
+        if (io_on_device) {
+            FD_HIP_TRY(c, hipMemsetAsync(out_pose, 0, sizeof(double) * poses, c->stream));
+            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+            if (out_best) FD_HIP_TRY(c, hipMemsetAsync(out_best, 0xFF, sizeof(int32_t) * batch, c->stream));
+        } else {
+            std::fill(out_pose, out_pose + poses, 0.0);
+            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
+            if (out_best) std::fill(out_best, out_best + batch, -1);
+        }
+        return FD_OK;
+    }
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
+    a.hypotheses = opts->hypotheses;
+    a.seed = opts->seed;
+    rc = pnp_workspace(c, a);
+    if (rc) return rc;
+    FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 12, a.models));
+    HostIo io(c, io_on_device);
+    rc = pnp_inputs(c, io, a, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
+    if (rc) return rc;
+    FD_HIP_TRY(c, io.out(out_pose, poses, a.out_pose));
+    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
+    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
+    FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
+    FD_HIP_TRY(c, fdk::launch_pnp_ransac(a, c->stream));
+    return io.finish(q_counts, batch, q_stride);
+}
+
+int fd_pnp_refit(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_xyz, const uint8_t *p_valid,
+                 const int32_t *q_counts, int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx,
+                 const uint8_t *pair_valid, const double *in_pose, const uint8_t *in_inlier, double *out_pose,
+                 uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds, int io_on_device) {
+    if (!c) return FD_ERR_INVALID;
+    if (!opts || !p_xyz || !t_xy || !in_pose || !in_inlier || !out_pose) return fail(c, FD_ERR_INVALID, "bad arguments");
+    fdk::PnpRefitArgs g{};
+    int rc = pnp_args(c, g.r, batch, opts, q_stride, t_stride, match_idx, false);
+    if (rc) return rc;
+    if (opts->rounds < 1 || opts->rounds > FD_PNP_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 8]");
+    FD_HIP_TRY(c, hipSetDevice(c->device));
+    rc = refuse_sync_under_capture(c, io_on_device);
+    if (rc) return rc;
+    const size_t poses = static_cast<size_t>(12) * batch;
+    if (q_stride == 0) {  // no slots: no round is accepted
+        if (io_on_device) {
+            if (out_pose != in_pose)
+                FD_HIP_TRY(c, hipMemcpyAsync(out_pose, in_pose, sizeof(double) * poses, hipMemcpyDeviceToDevice, c->stream));
+            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
+            if (out_rounds) FD_HIP_TRY(c, hipMemsetAsync(out_rounds, 0, sizeof(int32_t) * batch, c->stream));
+        } else {
+            if (out_pose != in_pose) std::copy(in_pose, in_pose + poses, out_pose);
+            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
+            if (out_rounds) std::fill(out_rounds, out_rounds + batch, 0);
+        }
+        return FD_OK;
+    }
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
+    g.rounds = opts->rounds;
+    rc = pnp_workspace(c, g.r);
+    if (rc) return rc;
+    FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
+    HostIo io(c, io_on_device);  // 8 inputs and 4 outputs: the whole staging pool
+    rc = pnp_inputs(c, io, g.r, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
+    if (rc) return rc;
+    FD_HIP_TRY(c, io.in(in_pose, poses, g.in_pose));
+    FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
+    FD_HIP_TRY(c, io.out(out_pose, poses, g.r.out_pose));
+    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, g.r.out_inlier));
+    FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
+    FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
+    FD_HIP_TRY(c, fdk::launch_pnp_refit(g, c->stream));
+    return io.finish(q_counts, batch, q_stride);
+}
+
 
 int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_xy, const int32_t *q_counts,
               int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx, const uint8_t *pair_valid,

@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_pose_opts, fd_ransac_opts, fd_refit_opts
+from ._lib import fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
 from ._slots import outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
@@ -247,3 +247,105 @@ def recover_pose(q_xy, t_xy, result: GeometryResult, K, K_t=None, matches=None, 
                                      ptr(ii), ptr(oo), ptr(och), ptr(op), ptr(ov), ptr(oc), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return PoseResult(op, ov, oc, oo, och)
+
+
+@dataclass
+class PnpResult:
+    pose: object     # float64 [B, 12]: R row-major, then t, X_t = R X + t in the units of the points; zeros: no pose
+    inliers: object  # uint8 [B, S]: 1 = a correspondence within `threshold` pixels of its reprojection
+    counts: object   # int32 [B]: inliers per frame
+    best: object     # int32 [B]: the winning hypothesis, -1: no pose
+
+    def rotation(self, b=0):
+        """Frame b's R as a [3, 3] view."""
+        return self.pose[b, :9].reshape(3, 3)
+
+    def translation(self, b=0):
+        return self.pose[b, 9:]
+
+
+@dataclass
+class PnpRefineResult(PnpResult):
+    rounds: object = None  # int32 [B]: accepted Gauss-Newton rounds; 0: pose and inliers are the given ones
+
+
+def _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, extra, ctx):
+    """What solve_pnp and refine_pnp share: the checked arguments of the two entry points. `extra`: further
+    arrays that must be on the side of t_xy."""
+    if isinstance(points, PointsResult):
+        points, point_valid = points.points, (points.valid if point_valid is None else point_valid)
+    on_dev = _is_torch_device_tensor(t_xy)
+    sides = [_is_torch_device_tensor(points)] + [_is_torch_device_tensor(x) for x in extra]
+    if point_valid is not None:
+        sides.append(_is_torch_device_tensor(point_valid))
+    if any(side != on_dev for side in sides):
+        raise ValueError("points, point_valid and the given result must be on the side (host / device) of t_xy")
+    ctx = _resolve_ctx(ctx, t_xy, points)
+    pt = positions(t_xy, "t_xy", on_dev)
+    b, ts = int(pt.shape[0]), int(pt.shape[1])
+    shape = tuple(points.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[2] != 3 or shape[0] != b:
+        raise ValueError("points must be float32 [B, S, 3] (or [S, 3] for batch 1) with t_xy's batch")
+    s = int(shape[1])
+    pp = slot_arg(points, "float32", (b, s, 3), on_dev)
+    if matches is None and ts < s:
+        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as points")
+    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
+    pv, cn = slot_arg(point_valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev)
+    return ctx, on_dev, pp, pv, pt, b, s, ts, intrinsics(K), mi, v, cn
+
+
+def solve_pnp(points, t_xy, K, matches=None, valid=None, point_valid=None, counts=None, hypotheses: int = 256, seed: int = 0,
+              threshold: float = 2.0, center=None, scale: float = 1.0, out=None, ctx: Context | None = None) -> PnpResult:
+    """fd_pnp_ransac: the camera pose of an image against known 3-D points, the step that places the next frame
+    against the points recover_pose / triangulate left (at their scale): the 6-point DLT camera matrix with the
+    most inliers among `hypotheses` samples, made a rotation and a translation.
+
+    points: float32 [B, S, 3] (or [S, 3] for batch 1), or a PointsResult / PoseResult as it is (its valid bytes
+    then are point_valid). t_xy: float32 [B, T, 2], the image positions. K: the image's camera as in
+    triangulate. matches, valid, counts: verify_geometry's (track_lk's status passes as valid). threshold is
+    the reprojection error in pixels. center (three values, default 0) and scale condition the 3-D points,
+    Xc = (X - center) * scale: the scene's centroid and the inverse of its spread are a good choice. A planar
+    scene has no DLT pose.
+
+    Returns a PnpResult. Host and device inputs and out= (pose float64 [B, 12], inliers uint8 [B, S], counts
+    int32 [B], best int32 [B]) behave as in verify_geometry.
+    """
+    ctx, on_dev, pp, pv, pt, b, s, ts, cam, mi, v, cn = _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, (), ctx)
+    c3 = (0.0, 0.0, 0.0) if center is None else tuple(float(x) for x in np.asarray(center, np.float64).reshape(3))
+    opts = fd_pnp_opts(int(hypotheses), int(seed) & 0xFFFFFFFF, 1, float(threshold), *cam, (ctypes.c_double * 3)(*c3), float(scale))
+    oo, oi, oc, ob = outputs((((b, 12), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
+                             on_dev, pt.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_pnp_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pp), ptr(pv), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
+                                   ptr(oo), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return PnpResult(oo, oi, oc, ob)
+
+
+def refine_pnp(points, t_xy, result: PnpResult, K, matches=None, valid=None, point_valid=None, counts=None, rounds: int = 4,
+               threshold: float = 2.0, out=None, ctx: Context | None = None) -> PnpRefineResult:
+    """fd_pnp_refit: Gauss-Newton on the reprojection error over solve_pnp's inliers, the inliers classified
+    again, up to `rounds` (1..8) times while their number does not fall.
+
+    points, t_xy, K, matches, valid, point_valid, counts and threshold are solve_pnp's: pass the same ones.
+    result: what solve_pnp returned (its pose float64 [B, 12] and inliers uint8 [B, S], on the side of t_xy). A
+    frame whose first round is rejected keeps its pose bit for bit and has rounds 0.
+
+    Returns a PnpRefineResult: pose, inliers, counts as solve_pnp's, best as given, and rounds int32 [B]. Host
+    and device inputs and out= (pose float64 [B, 12], inliers uint8 [B, S], counts int32 [B], rounds int32 [B])
+    behave as in verify_geometry; out= may hold result's own pose and inliers tensors.
+    """
+    ctx, on_dev, pp, pv, pt, b, s, ts, cam, mi, v, cn = _pnp_call(points, t_xy, K, matches, valid, point_valid, counts,
+                                                                  (result.pose, result.inliers), ctx)
+    ip, ii = slot_arg(result.pose, "float64", (b, 12), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
+    opts = fd_pnp_opts(1, 0, int(rounds), float(threshold), *cam, (ctypes.c_double * 3)(0.0, 0.0, 0.0), 1.0)
+    oo, oi, oc, orr = outputs((((b, 12), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
+                              on_dev, pt.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_pnp_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pp), ptr(pv), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
+                                  ptr(ip), ptr(ii), ptr(oo), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return PnpRefineResult(oo, oi, oc, result.best, orr)

@@ -864,7 +864,7 @@ typedef struct fd_pose_opts {
  * pose (R, t), X_t = R X_q + t, from the fundamental matrix of fd_ransac / fd_ransac_refit, and the 3-D
  * points of the inliers in the q camera's frame. Definite sequences like fd_ransac's, with its conventions:
  * all floating point double, every operation rounded once, no contraction, f64 division and square root
- * correctly rounded. No lens distortion (undistort or warp first), no five-point solver, no PnP.
+ * correctly rounded. No lens distortion (undistort or warp first), no five-point solver (PnP: fd_pnp_ransac below).
  *
  * q_xy, q_counts, q_stride, t_xy, t_stride, match_idx, pair_valid: fd_ransac's, with its rules for which
  * slots are correspondences. Coordinates are plain pixels, x = (double)q.x: no conditioning transform.
@@ -930,6 +930,121 @@ int fd_pose_recover(fd_ctx *ctx, int batch, const fd_pose_opts *opts,
                     double *out_pose, int32_t *out_choice,
                     float *out_points, uint8_t *out_valid, int32_t *out_counts,
                     int io_on_device);
+
+/* ---- Absolute pose from 3-D points: PnP RANSAC and refinement (MI355X extension) ----------------------- */
+#define FD_PNP_MAX_ROUNDS 8
+
+typedef struct fd_pnp_opts {
+    int32_t hypotheses; /* 1..4096, all evaluated (fd_pnp_ransac; fd_pnp_refit ignores it) */
+    uint32_t seed;      /* fd_pnp_ransac */
+    int32_t rounds;     /* 1..8 (fd_pnp_refit; fd_pnp_ransac ignores it) */
+    float threshold;    /* pixels, finite, > 0: the reprojection error */
+    double fx, fy, cx, cy; /* zero-skew pinhole camera of the t image: finite, fx and fy non-zero */
+    double center[3], scale; /* fixed conditioning of the 3-D points, finite, scale > 0 (fd_pnp_ransac; fd_pnp_refit
+                                works in the camera's units and ignores them) */
+} fd_pnp_opts;
+
+/*
+ * fd_pnp_ransac and fd_pnp_refit -- the camera pose (R, t), X_t = R X + t, of the t image against known 3-D
+ * points: the step that places the next frame against the points fd_pose_recover / fd_triangulate left, at
+ * their scale. Definite sequences like fd_ransac's, with its conventions: all floating point double, every
+ * operation rounded once, no contraction, f64 division and square root correctly rounded; only + - * / sqrt. An
+ * expression written a + b + c is summed left to right; "from 0.0" means the sum starts at 0.0.
+ *
+ * p_xyz float [batch][q_stride][3]: fd_triangulate's / fd_pose_recover's out_points as it is; p_valid uint8
+ * [batch][q_stride]: their out_valid as it is (NULL: all). t_xy float [batch][t_stride][2]. q_counts, match_idx,
+ * pair_valid: fd_ransac's (the tracker's out_status passes as pair_valid as it is).
+ * Correspondences of frame b: slot i is one when i < q_counts[b], p_valid and pair_valid are each NULL or exactly
+ * 1 at the slot, j = match_idx ? match_idx[i] : i satisfies 0 <= j < t_stride, and the three coordinates of the
+ * point and the two of t_xy[j] are finite. They are taken in ascending i and numbered 0..n-1, each with
+ *   the ray  bx = ((double)u - cx) / fx,  by = ((double)v - cy) / fy,  (u, v) = t_xy[j], and
+ *   the point  Xc = ((double)p.x - center[0]) * scale, Yc and Zc likewise (fd_pnp_refit: X = (double)p.x).
+ *
+ * Inlier test of a 3 x 4 matrix P (row-major) on a correspondence, with t = (double)threshold:
+ *   y_i = P[i][0]*Xc + P[i][1]*Yc + P[i][2]*Zc + P[i][3];  w = y_2
+ *   dx = fx * (y_0 - bx*w);  dy = fy * (y_1 - by*w);  inlier iff w > 0 and dx*dx + dy*dy <= (t*t) * (w*w)
+ * (division-free like fd_ransac's H; a NaN fails).
+ *
+ * fd_pnp_ransac: fixed-count RANSAC over 6-point DLT camera matrices.
+ * Sample: m = 6 picks by fd_ransac's sampler unchanged. System: pick k gives the rows 2k and 2k + 1,
+ *   [Xc, Yc, Zc, 1, 0, 0, 0, 0, -(bx*Xc), -(bx*Yc), -(bx*Zc), -bx]
+ *   [0, 0, 0, 0, Xc, Yc, Zc, 1, -(by*Xc), -(by*Yc), -(by*Zc), -by]
+ * and the first 11 rows form the 11 x 12 system. Null vector: fd_ransac's Gaussian elimination with complete
+ * pivoting, with R = 11 rows and R + 1 columns where that text has 8 and 9 (r = k..R-1 outer, c = k..R inner, the
+ * same strict >, the same test best > 1e-12 * p0, back substitution from x[R] = 1, the permutation undone, a
+ * non-finite entry invalid). The twelve entries are P, row-major.
+ * Sign: det = (P0*(P5*P10 - P6*P9) - P1*(P4*P10 - P6*P8)) + P2*(P4*P9 - P5*P8), P0..P11 the entries in order
+ * (the determinant of the left 3 x 3 block M); the hypothesis is invalid if det is 0 or not finite; if det < 0
+ * all twelve entries are negated. Coplanar points and other degenerate samples fail the pivot test: a planar
+ * scene has no DLT pose (points that are coplanar only up to their float rounding pass the test with a matrix that
+ * fits them and an arbitrary pose).
+ * Score: the inlier test over the frame's correspondences. The best hypothesis is the valid one with the most
+ * inliers, the lowest index among equals. n < 6: no hypothesis is valid.
+ * Winner to pose: G[i][j] = sum over k ascending from 0.0 of M[k][i]*M[k][j]; fd_ransac_refit's cyclic Jacobi on G
+ * (n = 3, V = identity), FD_POSE_SWEEPS sweeps, giving the diagonal d and V; sd[j] = sqrt(d[j]);
+ * W[i][j] = sum over k from 0.0 of M[i][k]*V[k][j];  R[i][k] = sum over j from 0.0 of (W[i][j] / sd[j]) * V[k][j];
+ * ks = (sd[0] + sd[1] + sd[2]) / 3.0;  tc[i] = P[i][3] / ks;
+ * t[i] = tc[i] / scale - (R[i][0]*center[0] + R[i][1]*center[1] + R[i][2]*center[2]).
+ * There is no pose unless d, V, R and t are all finite and min(d) > 1e-12 * max(d). A frame whose winner has no
+ * pose is treated as one without a valid hypothesis.
+ * Outputs. out_pose double [batch][12]: R row-major, then t; twelve zeros without a pose. out_inlier uint8
+ * [batch][q_stride] (NULL to skip): 1 for a correspondence the winning P classifies as an inlier, 0 for every
+ * other slot below q_counts[b] (all of them without a pose); slots >= q_counts[b] are not written. out_counts
+ * [batch] (NULL to skip): the ones. out_best [batch] (NULL to skip): the winning hypothesis, or -1. q_stride 0:
+ * nothing but out_counts = 0, out_best = -1 and a zero pose.
+ *
+ * fd_pnp_refit: Gauss-Newton on the reprojection error over the inliers, unconditioned (center 0, scale 1).
+ * in_pose double [batch][12] and in_inlier uint8 [batch][q_stride]: fd_pnp_ransac's out_pose and out_inlier.
+ * Start: S_0 = the correspondences whose in_inlier byte is exactly 1; the current pose is in_pose; c_0 = the
+ * number of correspondences of the whole list that P = [R | t] of in_pose classifies as inliers. (Not |S_0|:
+ * orthonormalising a projective winner usually loses inliers, and this c_0 lets the first round be accepted.)
+ * Round r = 1..rounds, for the current (R, t):
+ * 1. For each member of S_(r-1): y_i = R[i][0]*X + R[i][1]*Y + R[i][2]*Z + t[i]; iz = 1.0 / y_2; a = y_0*iz;
+ *    b = y_1*iz; the two rows of seven
+ *      jx = [fx * -(a*b), fx * (1.0 + a*a), fx * -b, fx * iz, 0.0, fx * -(a*iz), fx * (a - bx)]
+ *      jy = [fy * -(1.0 + b*b), fy * (a*b), fy * a, 0.0, fy * iz, fy * -(b*iz), fy * (b - by)]
+ *    (the Jacobian of the left perturbation y' = y + w x y + delta, then the residual). The 27 entries (i, j),
+ *    i = 0..5, j = i..6, row-major, are summed: acc = acc + jx[i]*jx[j], then acc = acc + jy[i]*jy[j]. Order:
+ *    fd_ransac_refit's, 256 partials from 0.0 over the list positions L, L + 256, ... ascending (members only),
+ *    then the tree P[L] = P[L] + P[L + step], step = 128..1. They fill the 6 x 7 system [N | g], N mirrored.
+ * 2. x = the null vector of [N | g] by the elimination above with R = 6 (x[6] = 1): N x + g = 0.
+ *    w = x[0..2], delta = x[3..5].
+ * 3. Cayley transform: h[i] = w[i] / 2.0; hh = h0*h0 + h1*h1 + h2*h2; f = 2.0 / (1.0 + hh);
+ *    K = [[0, -h2, h1], [h2, 0, -h0], [-h1, h0, 0]];
+ *    C[i][j] = (i == j ? 1.0 : 0.0) + f * (K[i][j] + (h[i]*h[j] - (i == j ? hh : 0.0)));
+ *    R' = C R (sums from 0.0, inner index ascending); t'[i] = C[i][0]*t[0] + C[i][1]*t[1] + C[i][2]*t[2] + delta[i].
+ *    The round is invalid unless the solve is valid and R', t' are finite.
+ * 4. Classify every correspondence of the list with P = [R' | t']: S_r, c_r = |S_r|.
+ * 5. Guard: the round is accepted iff it is valid and c_r >= c_(r-1); (R', t') becomes the current pose.
+ *    Otherwise the loop stops and the state of the last accepted round stands.
+ * Outputs. out_pose: the pose of the last accepted round; with none the twelve doubles of in_pose, bit for bit.
+ * out_inlier (NULL to skip): 1 for the members of the last accepted round's S (of S_0 with none), 0 for every
+ * other slot below q_counts[b]; slots >= q_counts[b] are not written. out_counts (NULL to skip): the ones of
+ * out_inlier. out_rounds int32 [batch] (NULL to skip): the accepted rounds, 0..rounds. out_pose may be in_pose
+ * and out_inlier may be in_inlier. q_stride 0: out_pose = in_pose, out_counts = 0, out_rounds = 0.
+ *
+ * Device pointers when io_on_device: asynchronous on the context's stream (three kernels; fd_pnp_refit: two),
+ * graph-capturable once a first call of the shape has sized the workspace. Host pointers otherwise: staged
+ * through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, p_xyz, t_xy or out_pose NULL (fd_pnp_refit: in_pose or in_inlier too); batch < 1; a
+ * negative stride; match_idx NULL with t_stride < q_stride; threshold not finite or not > 0; a camera value not
+ * finite, fx or fy zero; fd_pnp_ransac: hypotheses outside 1..4096, center or scale not finite, scale not > 0;
+ * fd_pnp_refit: rounds outside 1..8.
+ */
+int fd_pnp_ransac(fd_ctx *ctx, int batch, const fd_pnp_opts *opts,
+                  const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts, int32_t q_stride,
+                  const float *t_xy, int32_t t_stride,
+                  const int32_t *match_idx, const uint8_t *pair_valid,
+                  double *out_pose, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
+                  int io_on_device);
+
+int fd_pnp_refit(fd_ctx *ctx, int batch, const fd_pnp_opts *opts,
+                 const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts, int32_t q_stride,
+                 const float *t_xy, int32_t t_stride,
+                 const int32_t *match_idx, const uint8_t *pair_valid,
+                 const double *in_pose, const uint8_t *in_inlier,
+                 double *out_pose, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
+                 int io_on_device);
 
 /* ---- Image warp by a homography or a camera model (MI355X extension) --------------------------------- */
 #define FD_WARP_HOMOGRAPHY 0 /* params: double[9], row-major 3 x 3, fd_ransac's out_model layout */

@@ -111,6 +111,45 @@ public:
     PoseOptions &pose_options() { return pose_options_; }
     const PoseOptions &pose_options() const { return pose_options_; }
 
+    // Options of SolvePnP and RefinePnP.
+    struct PnpOptions {
+        int32_t kHypotheses = 256;   // 1..4096, all evaluated
+        uint32_t kSeed = 0;
+        float kThreshold = 2.0f;     // pixels: the reprojection error
+        // the fixed conditioning (X - center) * scale of the 3-D points in SolvePnP: the scene's centroid and
+        // the inverse of its spread are a good choice
+        std::array<double, 3> kCenter{{0.0, 0.0, 0.0}};
+        double kScale = 1.0;
+    };
+
+    // The camera pose of an image against known 3-D points (fd_pnp_ransac of include/fd_hip.h): the 6-point DLT
+    // camera matrix with the most inliers among kHypotheses samples, made a rotation and a translation. points[i]
+    // <-> image_uv[image_index[i]] (or image_uv[i] without image_index); RecoverPose's / Triangulate's points and
+    // point_valid pass as they are (point_valid and valid optional: only the points flagged exactly 1 take
+    // part). pose: R row-major, then t, X_camera = R X + t in the points' units. inlier[i]: 1 if point i
+    // reprojects within kThreshold pixels.
+    // False, with a zero pose and inlier all 0, when there is no pose (fewer than 6 correspondences, every sample
+    // degenerate: a planar scene has none), for no points, a mask or index of the wrong size, fewer image
+    // positions than points without image_index, a camera or option out of range, or a libfdhip failure.
+    bool SolvePnP(const std::vector<std::array<float, 3>> &points, const std::vector<Vec2> &image_uv, const Camera &camera,
+                  std::array<double, 12> &pose, std::vector<uint8_t> &inlier, const std::vector<uint8_t> *point_valid = nullptr,
+                  const std::vector<int32_t> *image_index = nullptr, const std::vector<uint8_t> *valid = nullptr,
+                  int32_t *best_hypothesis = nullptr);
+
+    // Refines SolvePnP's pose on its inliers by Gauss-Newton on the reprojection error (fd_pnp_refit): up to
+    // `rounds` (1..8) times, the inliers classified again after each, while their number does not fall. The
+    // other arguments are what SolvePnP took; pose and inlier are what it returned and receive the result.
+    // accepted_rounds (optional): the rounds taken; with 0 pose keeps its bits and inlier its members.
+    // False for the size and range errors of SolvePnP, rounds out of range, or a libfdhip failure; pose and
+    // inlier are then left as given.
+    bool RefinePnP(const std::vector<std::array<float, 3>> &points, const std::vector<Vec2> &image_uv, const Camera &camera,
+                   std::array<double, 12> &pose, std::vector<uint8_t> &inlier, int32_t rounds = 4,
+                   const std::vector<uint8_t> *point_valid = nullptr, const std::vector<int32_t> *image_index = nullptr,
+                   const std::vector<uint8_t> *valid = nullptr, int32_t *accepted_rounds = nullptr);
+
+    PnpOptions &pnp_options() { return pnp_options_; }
+    const PnpOptions &pnp_options() const { return pnp_options_; }
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -122,6 +161,7 @@ public:
 private:
     Options options_;
     PoseOptions pose_options_;
+    PnpOptions pnp_options_;
     DeviceContext context_;
 };
 

@@ -19,7 +19,9 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
   --shape fastverify FAST (need 500, dist 15) + BRIEF-256 on the 64 frames of fastflow's moving scene, fd_brief_match of
                      frame i against frame i + 1 and fd_ransac (256 hypotheses, threshold 1 px) on the matches, the
                      fundamental matrix and then the homography, 10 calls (--refit: fd_ransac_refit, rounds 2, after each;
-                     --pose: fd_pose_recover and fd_triangulate on the fundamental matrix)
+                     --pose: fd_pose_recover and fd_triangulate on the fundamental matrix; --pnp: with --pose, fd_pnp_ransac
+                     (256 hypotheses, threshold 2 px) and fd_pnp_refit (rounds 4) of frame i + 1 against the points
+                     fd_pose_recover left)
   --shape warp       fd_frames_warp with a mask, on device tensors: a rotation by 3 degrees with scale 1.02 and a mild
                      perspective (homography), then a barrel-distortion camera model, at 1920x1080 batch 64 (10
                      calls each) and at 640x480 batch 1 (200 calls each), destination shape = source shape
@@ -68,6 +70,8 @@ p.add_argument("--calls", type=int, default=0)
 p.add_argument("--cross-check", action="store_true", help="fastmatch: match with the cross-check")
 p.add_argument("--fb", action="store_true", help="fastflow: track with the forward-backward check")
 p.add_argument("--refit", action="store_true", help="fastverify: fd_ransac_refit (rounds 2) on each model after fd_ransac")
+p.add_argument("--pnp", action="store_true",
+               help="fastverify: implies --pose; fd_pnp_ransac and fd_pnp_refit of the pair's second frame against fd_pose_recover's points")
 p.add_argument("--pose", action="store_true",
                help="fastverify: fd_pose_recover on the fundamental matrix (the refit one with --refit), then fd_triangulate with its pose")
 p.add_argument("--dim", type=int, default=256, help="nnmatch: floats per descriptor")
@@ -212,7 +216,8 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
     base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
     base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)
     frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
-    out, refit, pose, tri = None, {}, None, None
+    out, refit, pose, tri, pnp = None, {}, None, None, None
+    a.pose = a.pose or a.pnp
     cam = (1000.0, 1000.0, 639.5, 359.5)
     for _ in range(a.calls or 10):
         res = fd.detect_points(kind, frames, 500, 15, THR[kind])
@@ -243,6 +248,18 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
                 fd.recover_pose(res.xy[:-1], res.xy[1:], given, cam, matches=out[0], counts=res.counts[:-1], out=pose)
                 fd.triangulate(res.xy[:-1], res.xy[1:], pose[0], cam, matches=out[0], counts=res.counts[:-1], inliers=given.inliers,
                                out=tri)
+                if a.pnp:
+                    if pnp is None:
+                        pnp = [tuple(torch.empty_like(x) for x in (pose[0], pose[3], pose[4], pose[1])) for _ in range(2)]
+                    pts = fd.PointsResult(pose[2], pose[3], pose[4])
+                    # the points are in units of the pair's baseline, a few of them deep: no conditioning
+                    solved = fd.solve_pnp(pts, res.xy[1:], cam, matches=out[0], counts=res.counts[:-1], hypotheses=256,
+                                          threshold=2.0, out=pnp[0])
+                    fd.refine_pnp(pts, res.xy[1:], solved, cam, matches=out[0], counts=res.counts[:-1], rounds=4, threshold=2.0,
+                                  out=pnp[1])
+    if a.pnp:
+        print("frames with a PnP pose:", int((pnp[0][3] >= 0).sum()), "PnP inliers (mean):", float(pnp[0][2].float().mean()),
+              "refined (mean):", float(pnp[1][2].float().mean()), "accepted rounds (mean):", float(pnp[1][3].float().mean()))
     if a.pose:
         print("frames with a pose:", int((pose[1] >= 0).sum()), "points in front per pair (mean):", float(pose[4].float().mean()),
               "triangulated (mean):", float(tri[2].float().mean()))
