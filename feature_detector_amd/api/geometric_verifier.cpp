@@ -243,4 +243,57 @@ bool GeometricVerifier::RefinePnP(const std::vector<std::array<float, 3>> &point
     return true;
 }
 
+bool GeometricVerifier::BundleAdjust(std::vector<std::array<double, 12>> &poses, std::vector<std::array<float, 3>> &points,
+                                     const std::vector<std::vector<Vec2>> &observations, const Camera &camera,
+                                     std::vector<std::vector<uint8_t>> &inlier,
+                                     const std::vector<std::vector<uint8_t>> *observation_valid,
+                                     const std::vector<uint8_t> *point_valid, const std::vector<uint8_t> *fixed,
+                                     std::array<double, 2> *cost, int32_t *accepted_rounds) {
+    const size_t cams = poses.size(), n = points.size();
+    if (accepted_rounds) *accepted_rounds = 0;
+    inlier.assign(cams, std::vector<uint8_t>(n, 0));
+    if (cams < 1 || cams > FD_BA_MAX_CAMS) return context_.Fail("BundleAdjust: 1 to 8 cameras are needed");
+    if (n == 0) return context_.Fail("BundleAdjust: no points");
+    if (observations.size() != cams) return context_.Fail("BundleAdjust: one observation vector per camera is needed");
+    if (observation_valid && observation_valid->size() != cams)
+        return context_.Fail("BundleAdjust: one observation_valid vector per camera is needed");
+    for (size_t c = 0; c < cams; ++c) {
+        if (observations[c].size() != n) return context_.Fail("BundleAdjust: every camera needs one observation per point");
+        if (observation_valid && (*observation_valid)[c].size() != n)
+            return context_.Fail("BundleAdjust: one observation_valid flag per observation is needed");
+    }
+    if (point_valid && point_valid->size() != n) return context_.Fail("BundleAdjust: one point_valid flag per point is needed");
+    if (fixed && fixed->size() != cams) return context_.Fail("BundleAdjust: one fixed flag per camera is needed");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    std::vector<float> obs;
+    std::vector<uint8_t> ov;
+    obs.reserve(2 * cams * n);
+    for (size_t c = 0; c < cams; ++c) {
+        const std::vector<float> row = Flatten(observations[c]);
+        obs.insert(obs.end(), row.begin(), row.end());
+        if (observation_valid) ov.insert(ov.end(), (*observation_valid)[c].begin(), (*observation_valid)[c].end());
+    }
+    const BundleOptions &b = bundle_options_;
+    const fd_ba_opts o{b.kRounds, b.kThreshold, camera.fx, camera.fy, camera.cx, camera.cy, b.kLambda, b.kUp, b.kDown};
+    std::vector<double> out_poses(12 * cams);
+    std::vector<float> out_points(3 * n);
+    std::vector<uint8_t> out_inlier(cams * n);
+    double out_cost[2] = {0.0, 0.0};
+    int32_t accepted = 0;
+    const int rc = fd_bundle_adjust(ctx, 1, static_cast<int>(cams), &o, poses[0].data(), fixed ? fixed->data() : nullptr,
+                                    points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr, static_cast<int32_t>(n),
+                                    obs.data(), observation_valid ? ov.data() : nullptr, static_cast<int32_t>(n), out_poses.data(),
+                                    out_points.data(), out_inlier.data(), nullptr, out_cost, &accepted, 0);
+    if (rc != FD_OK) return context_.FailCall("fd_bundle_adjust");
+    for (size_t c = 0; c < cams; ++c) {
+        std::copy(out_poses.begin() + 12 * c, out_poses.begin() + 12 * (c + 1), poses[c].begin());
+        inlier[c].assign(out_inlier.begin() + c * n, out_inlier.begin() + (c + 1) * n);
+    }
+    for (size_t i = 0; i < n; ++i) std::copy(out_points.begin() + 3 * i, out_points.begin() + 3 * (i + 1), points[i].begin());
+    if (cost) *cost = {out_cost[0], out_cost[1]};
+    if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
 }  // namespace feature_detector

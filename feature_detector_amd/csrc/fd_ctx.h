@@ -63,8 +63,8 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs), fd_pose_recover (7 and 5) and fd_pnp_refit (8 and 4)
-    static constexpr int kStaging = 12;
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs), fd_pose_recover (7 and 5), fd_pnp_refit (8 and 4) and fd_bundle_adjust (7 and 6)
+    static constexpr int kStaging = 13;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
     // fd_nn_match's norms of both sets ([batch][q_stride], then [batch][t_stride]); the model-gated matchers' gate
@@ -77,6 +77,9 @@ struct fd_ctx {
     // per-frame best-hypothesis words; fd_ransac_refit: the support sets by list position ([batch][2][q_stride] bytes).
     // fd_pnp_ransac and fd_pnp_refit use the same buffers with 5 doubles per correspondence and 12 per hypothesis
     fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best, g_member;
+    // fd_bundle_adjust: a trial's linearisation per observation ([batch][cams][p_stride][52] doubles) and per point
+    // ([batch][p_stride][15] doubles), and the observations' state bytes ([batch][cams][p_stride])
+    fdrt::DevBuf ba_obs, ba_pts, ba_act;
     // fd_frames_equalize: the tiles' LUTs ([batch][tiles_y][tiles_x][256] bytes), then the columns' and rows'
     // interpolation entries ([cols + rows] words)
     fdrt::DevBuf e_ws;

@@ -525,6 +525,33 @@ struct PnpRefitArgs {
     int32_t *out_rounds;         // [batch] or null
 };
 
+// Windowed bundle adjustment (fd_ba.hip; fd_bundle_adjust of include/fd_hip.h): k_bundle_adjust, one workgroup
+// per problem. The workspace holds what a trial's linearisation leaves for its system and update passes.
+constexpr int kBaObsDoubles = 52;    // per observation: jx[7], jy[7], W[6][3], Y[6][3], bx, by
+constexpr int kBaPointDoubles = 15;  // per point: X of the two states by turns, the inverse's six entries, g[3]
+struct BaArgs {
+    const double *in_poses;      // [batch][cams][12]; may be out_poses
+    const uint8_t *cam_fixed;    // [batch][cams] or null (camera 0 alone is held); a non-zero byte holds the camera
+    const float *p_xyz;          // [batch][p_stride][3]; may be out_points
+    const uint8_t *p_valid;      // [batch][p_stride] or null; only a byte equal to 1 takes part
+    const int32_t *counts;       // [batch] or null (= p_stride); bits 25..31 ignored
+    const float *obs_xy;         // [batch][cams][o_stride][2]
+    const uint8_t *obs_valid;    // [batch][cams][o_stride] or null; only a byte equal to 1 takes part
+    int batch, cams, p_stride, o_stride, rounds;
+    double cam[4];               // fx, fy, cx, cy
+    double tt;                   // (double)threshold squared
+    double lambda, up, down;
+    double *obs;                 // workspace [batch][cams][p_stride][kBaObsDoubles]
+    double *pts;                 // workspace [batch][p_stride][kBaPointDoubles]
+    uint8_t *act;                // workspace [batch][cams][p_stride]: an observation's exists / active / eliminated bits
+    double *out_poses;           // [batch][cams][12]
+    float *out_points;           // [batch][p_stride][3] or null
+    uint8_t *out_inlier;         // [batch][cams][o_stride] or null
+    int32_t *out_counts;         // [batch] or null
+    double *out_cost;            // [batch][2] or null
+    int32_t *out_rounds;         // [batch] or null
+};
+
 // Image warp (fd_warp.hip): every destination pixel of out [batch][out_rows][out_cols] sampled from the frames
 // [batch][rows][cols] at the position a per-frame model gives (fd_frames_warp of include/fd_hip.h).
 struct WarpArgs {
@@ -592,6 +619,8 @@ hipError_t launch_triangulate(const PoseArgs &a, hipStream_t s);
 hipError_t launch_pnp_ransac(const PnpArgs &a, hipStream_t s);
 // k_pnp_compact, then k_pnp_refit (all rounds in one launch)
 hipError_t launch_pnp_refit(const PnpRefitArgs &a, hipStream_t s);
+// k_bundle_adjust, every trial in one launch (p_stride >= 1)
+hipError_t launch_bundle_adjust(const BaArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it
 hipError_t launch_pyr_down(const uint8_t *src, uint8_t *dst, int batch, int rows, int cols, hipStream_t s);
 hipError_t launch_flow_lk(const FlowArgs &a, hipStream_t s);

@@ -15,8 +15,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
-from ._slots import outputs, positions, ptr, slot_arg
+from ._lib import fd_ba_opts, fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
+from ._slots import f32, outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
 MODELS = {"fundamental": _lib.FD_RANSAC_FUNDAMENTAL, "homography": _lib.FD_RANSAC_HOMOGRAPHY}
@@ -349,3 +349,100 @@ def refine_pnp(points, t_xy, result: PnpResult, K, matches=None, valid=None, poi
                                   ptr(ip), ptr(ii), ptr(oo), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return PnpRefineResult(oo, oi, oc, result.best, orr)
+
+
+@dataclass
+class BundleResult:
+    poses: object    # float64 [B, C, 12]: per camera R row-major, then t; a held camera's are the given ones bit for bit
+    points: object   # float32 [B, S, 3]: the refined points; slots without an observation keep the given bits
+    inliers: object  # uint8 [B, C, O]: 1 = an observation within `threshold` pixels of its reprojection at the final state
+    counts: object   # int32 [B]: inlier observations per problem
+    cost: object     # float64 [B, 2]: the truncated reprojection cost of the given and of the final state
+    rounds: object   # int32 [B]: accepted Levenberg-Marquardt trials; 0: poses and points are the given ones
+
+    def rotation(self, b=0, c=0):
+        """Camera c of problem b: its R as a [3, 3] view."""
+        return self.poses[b, c, :9].reshape(3, 3)
+
+    def translation(self, b=0, c=0):
+        return self.poses[b, c, 9:]
+
+
+def _stack_poses(poses, on_dev):
+    """poses as [B, C, 12]: an array or tensor, or a list with one entry per camera of PnpResult / PoseResult (their
+    pose [B, 12]) or [B, 12] arrays."""
+    if isinstance(poses, (list, tuple)):
+        each = [getattr(p, "pose", p) for p in poses]
+        if on_dev:
+            import torch
+
+            return torch.stack([e.to(torch.float64).reshape(-1, 12) for e in each], 1).contiguous()
+        return np.ascontiguousarray(np.stack([np.asarray(e, np.float64).reshape(-1, 12) for e in each], 1))
+    if len(poses.shape) == 2:
+        poses = poses[None]
+    return poses
+
+
+def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, counts=None, fixed=None, rounds: int = 8,
+                  threshold: float = 2.0, lam: float = 1e-3, up: float = 10.0, down: float = 0.1, out=None,
+                  ctx: Context | None = None) -> BundleResult:
+    """fd_bundle_adjust: the poses of up to 8 cameras and the 3-D points they share refined together, the local bundle
+    adjustment over the last few keyframes after recover_pose / solve_pnp / refine_pnp. Levenberg-Marquardt on the
+    reprojection cost truncated at `threshold` pixels, the points eliminated by the Schur complement.
+
+    poses: float64 [B, C, 12] (or [C, 12] for batch 1), per camera R row-major then t, X_c = R X + t; or a list with
+    one PnpResult / PoseResult / [B, 12] array per camera (the first camera of a two-view start is the identity).
+    points: float32 [B, S, 3], or a PointsResult / PoseResult as it is (its valid bytes then are point_valid).
+    obs_xy: float32 [B, C, O, 2] with O >= S, and obs_valid uint8 [B, C, O]: per camera track_lk's positions and
+    status; slot i of every camera observes point i (gather matched features into slot order first). K: the one
+    camera of all views, as in triangulate. fixed: uint8 [B, C] (a nested list will do), non-zero holds a camera (None: camera 0 alone; two
+    held cameras pin the scale). rounds (1..16) counts accepted and rejected trials; lam, up, down: the initial
+    damping, its factor after a rejected and after an accepted trial.
+
+    Returns a BundleResult. Host and device inputs and out= (poses float64 [B, C, 12], points float32 [B, S, 3],
+    inliers uint8 [B, C, O], counts int32 [B], cost float64 [B, 2], rounds int32 [B]) behave as in verify_geometry;
+    out= may hold the given poses and points tensors themselves.
+    """
+    if isinstance(points, PointsResult):
+        points, point_valid = points.points, (points.valid if point_valid is None else point_valid)
+    on_dev = _is_torch_device_tensor(obs_xy)
+    poses = _stack_poses(poses, on_dev)
+    if on_dev and isinstance(fixed, (list, tuple)):  # a few flags written out by hand
+        import torch
+
+        fixed = torch.tensor(fixed, dtype=torch.uint8, device=obs_xy.device)
+    sides = [_is_torch_device_tensor(points), _is_torch_device_tensor(poses)]
+    sides += [_is_torch_device_tensor(x) for x in (obs_valid, point_valid, counts, fixed) if x is not None]
+    if any(side != on_dev for side in sides):
+        raise ValueError("poses, points and the masks must be on the side (host / device) of obs_xy")
+    ctx = _resolve_ctx(ctx, obs_xy, points)
+    oshape = tuple(obs_xy.shape)
+    if len(oshape) == 3:
+        oshape = (1,) + oshape
+    if len(oshape) != 4 or oshape[3] != 2:
+        raise ValueError("obs_xy must be float32 [B, C, O, 2] (or [C, O, 2] for batch 1)")
+    b, c, o = int(oshape[0]), int(oshape[1]), int(oshape[2])
+    po = f32(obs_xy, "obs_xy", on_dev).reshape(oshape)
+    pshape = tuple(points.shape)
+    if len(pshape) == 2:
+        pshape = (1,) + pshape
+    if len(pshape) != 3 or pshape[2] != 3 or pshape[0] != b:
+        raise ValueError("points must be float32 [B, S, 3] (or [S, 3] for batch 1) with obs_xy's batch")
+    s = int(pshape[1])
+    if o < s:
+        raise ValueError("slot i of a camera observes point i: obs_xy needs at least as many slots as points")
+    if tuple(poses.shape) != (b, c, 12):
+        raise ValueError("poses must be float64 [B, C, 12] with obs_xy's batch and cameras")
+    pp = slot_arg(points, "float32", (b, s, 3), on_dev)
+    ip = slot_arg(poses, "float64", (b, c, 12), on_dev)
+    ov, pv = slot_arg(obs_valid, "uint8", (b, c, o), on_dev), slot_arg(point_valid, "uint8", (b, s), on_dev)
+    cn, fx = slot_arg(counts, "int32", (b,), on_dev), slot_arg(fixed, "uint8", (b, c), on_dev)
+    opts = fd_ba_opts(int(rounds), float(threshold), *intrinsics(K), float(lam), float(up), float(down))
+    oo, opn, oi, oc, ocs, orr = outputs((((b, c, 12), "float64", 0), ((b, s, 3), "float32", 0), ((b, c, o), "uint8", 0),
+                                         ((b,), "int32", 0), ((b, 2), "float64", 0), ((b,), "int32", 0)), out, on_dev,
+                                        po.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_bundle_adjust(ctx.ptr, b, c, ctypes.byref(opts), ptr(ip), ptr(fx), ptr(pp), ptr(pv), ptr(cn), s, ptr(po),
+                                      ptr(ov), o, ptr(oo), ptr(opn), ptr(oi), ptr(oc), ptr(ocs), ptr(orr), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return BundleResult(oo, opn, oi, oc, ocs, orr)

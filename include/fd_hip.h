@@ -1046,6 +1046,118 @@ int fd_pnp_refit(fd_ctx *ctx, int batch, const fd_pnp_opts *opts,
                  double *out_pose, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
                  int io_on_device);
 
+/* ---- Windowed bundle adjustment (MI355X extension) ------------------------------------------------------ */
+#define FD_BA_MAX_CAMS 8
+#define FD_BA_MAX_ROUNDS 16
+
+typedef struct fd_ba_opts {
+    int32_t rounds;        /* 1..16 LM trials (accepted + rejected) */
+    float   threshold;     /* pixels, finite, > 0: truncation of the cost and the inlier gate */
+    double  fx, fy, cx, cy;/* one zero-skew pinhole camera for all views, as fd_pnp_opts */
+    double  lambda, up, down; /* initial damping > 0, factor on reject > 1, factor on accept in (0, 1] */
+} fd_ba_opts;
+
+/*
+ * fd_bundle_adjust -- the poses of up to 8 cameras and the 3-D points they share, refined together: the local
+ * bundle adjustment over the last few keyframes that corrects what fd_pose_recover's two-view points and
+ * fd_pnp_refit's motion-only refinement leave. It minimises the truncated reprojection cost by Levenberg-Marquardt,
+ * the points eliminated by the Schur complement onto the free cameras. A definite sequence like fd_pnp_refit's, with
+ * its conventions: all floating point double, every operation rounded once, no contraction, f64 division correctly
+ * rounded; only + - * /. An expression written a + b + c is summed left to right; "from 0.0" means the sum starts at
+ * 0.0. tests/ba_ref.py restates it.
+ *
+ * in_poses double [batch][cams][12]: per camera fd_pnp_ransac's / fd_pnp_refit's out_pose as it is (R row-major,
+ * then t; X_c = R X + t); the first camera of a two-view start is the identity (1 0 0 0 1 0 0 0 1 0 0 0) and the
+ * second fd_pose_recover's out_pose. cam_fixed uint8 [batch][cams]: a non-zero byte holds the camera; NULL: camera 0
+ * alone is held. A problem with no free camera is legal (structure-only refinement), and so is one whose points are
+ * all held (below). p_xyz float [batch][p_stride][3] and p_valid uint8 [batch][p_stride] (NULL: all):
+ * fd_triangulate's / fd_pose_recover's out_points and out_valid as they are. counts int32 [batch] (NULL: p_stride;
+ * bits 25..31 ignored, at most p_stride). obs_xy float [batch][cams][o_stride][2] and obs_valid uint8
+ * [batch][cams][o_stride] (NULL: all): row c is the tracker's out_xy and out_status of frame c. Slot i of every
+ * camera observes point i: tracks are slot-aligned and there is no match_idx in this call; a caller with matched,
+ * not tracked, features gathers them into slot order first.
+ *
+ * Observation (c, i) of problem b exists iff i < counts[b], p_valid and obs_valid are each NULL or exactly 1 at the
+ * slot, and the three floats of the point and the two of obs_xy[c][i] are finite. Its ray is
+ *   bx = ((double)u - cx) / fx,  by = ((double)v - cy) / fy,  (u, v) = obs_xy[c][i],
+ * and the point starts as X = ((double)p.x, (double)p.y, (double)p.z). A point participates when it has an observation.
+ * A state is the poses of all cameras and the points. t = (double)threshold, tt = t*t.
+ *
+ * Cost of a state. Per observation, with (R, t) its camera's pose and X its point:
+ *   y_k = R[k][0]*X_0 + R[k][1]*X_1 + R[k][2]*X_2 + t[k]
+ *   if y_2 > 0:  a = y_0 / y_2;  b = y_1 / y_2;  dx = fx * (a - bx);  dy = fy * (b - by);  e = dx*dx + dy*dy;
+ *                the term is e if e <= tt, else tt;  otherwise (also for a NaN) the term is tt.
+ * The observation is active iff y_2 > 0 and e <= tt. The cost is the sum of the terms: 256 partials from 0.0, partial
+ * L over the slots i = L, L + 256, ... ascending and within a slot over the cameras ascending (existing observations
+ * only), then the tree P[L] = P[L] + P[L + step], step = 128..1.
+ *
+ * Trial r = 1..rounds, from the current state, damping lambda (first the option's) and D = 1.0 + lambda:
+ * 1. Rows. For each active observation: iz = 1.0 / y_2; a = y_0*iz; b = y_1*iz; fd_pnp_refit's rows of seven
+ *      jx = [fx * -(a*b), fx * (1.0 + a*a), fx * -b, fx * iz, 0.0, fx * -(a*iz), fx * (a - bx)]
+ *      jy = [fy * -(1.0 + b*b), fy * (a*b), fy * a, 0.0, fy * iz, fy * -(b*iz), fy * (b - by)]
+ *    (left perturbation of the camera; entry 6 is the residual) and the point rows, k = 0..2,
+ *      px[k] = fx*iz * (R[0][k] - a*R[2][k]);  py[k] = fy*iz * (R[1][k] - b*R[2][k]).
+ * 2. Point blocks. Per point, over the cameras ascending (active observations only), from 0.0:
+ *      V[k][l] (k <= l):  acc = acc + px[k]*px[l], then acc = acc + py[k]*py[l];
+ *      g[k]:              acc = acc + px[k]*jx[6], then acc = acc + py[k]*jy[6].
+ *    Damped diagonal d_k = V[k][k] * D. Adjugate and determinant:
+ *      c00 = d1*d2 - V12*V12;  c01 = V02*V12 - V01*d2;  c02 = V01*V12 - V02*d1;
+ *      c11 = d0*d2 - V02*V02;  c12 = V01*V02 - d0*V12;  c22 = d0*d1 - V01*V01;
+ *      det = d0*c00 + V01*c01 + V02*c02;   I[k][l] = ckl / det (symmetric).
+ *    The point is held for the trial when it has fewer than 2 active observations, or unless det is finite and
+ *    det > 1e-12 * (d0*d1*d2). A held point is not eliminated and does not move; its active observations still enter
+ *    U and g of their cameras, exactly as in fd_pnp_refit.
+ *    For an eliminated point and each free camera c that observes it actively:
+ *      W_c[r][k] = jx[r]*px[k] + jy[r]*py[k]  (r = 0..5);   Y_c[r][k] = W_c[r][0]*I[0][k] + W_c[r][1]*I[1][k] + W_c[r][2]*I[2][k].
+ * 3. Schur system. The free cameras in ascending order number 0..F-1; R = 6 F; row 6 f + r is entry r of free camera
+ *    f. For rows a = (c, r) <= b = (d, s), and for the right-hand column b = R (d = c, s = 6), two sums over the points
+ *    in ascending slot order, each from 0.0:
+ *      u: only if c == d, over the active observations (c, i):  u = u + jx[r]*jx[s], then u = u + jy[r]*jy[s];
+ *      e: over the eliminated points i with (c, i) and (d, i) active:
+ *         e = e + (Y_c[r][0]*W_d[s][0] + Y_c[r][1]*W_d[s][1] + Y_c[r][2]*W_d[s][2]),   for b = R with g[k] for W_d[s][k].
+ *    A[a][b] = (a == b ? u * D : u) - e, mirrored into A[b][a] for b < R: the R x (R + 1) system [S | rhs], S x + rhs = 0.
+ * 4. Elimination: fd_ransac's Gaussian elimination with complete pivoting at run-time size R (r = k..R-1 outer,
+ *    c = k..R inner, the same strict >, so the first of the largest magnitudes in that order wins and a NaN never
+ *    does; the same test best > 1e-12 * p0; row factor f = A[r][k] / A[k][k], A[r][c] = A[r][c] - f*A[k][c]). Back
+ *    substitution from y[R] = 1: y[k] = (0.0 - s) / A[k][k], s from 0.0 over c = R, R-1, ..., k+1 (descending, the one
+ *    difference from fd_ransac's text: row k's sum then takes each y[c] as it appears). The permutation is undone
+ *    giving x; the step is x[j] / x[R], j < R. The trial is invalid if a pivot fails the test or an entry of x or of
+ *    the step is not finite. R = 0: there is no system and this step is valid.
+ * 5. Update. Free camera f with w = step[6f..6f+2], delta = step[6f+3..6f+5]: fd_pnp_refit's Cayley transform
+ *    (its step 3) gives (R', t'); a held camera keeps its twelve doubles. Eliminated point:
+ *      v[k] = g[k], then over the free cameras ascending that observe it actively, r = 0..5: v[k] = v[k] + W_c[r][k]*step[6f+r];
+ *      X'[k] = X[k] - (I[k][0]*v[0] + I[k][1]*v[1] + I[k][2]*v[2]).
+ *    The trial is invalid unless every R', t' and X' is finite.
+ * 6. Accept rule: the trial is accepted iff it is valid and its state's cost' < cost. On accept the state and cost'
+ *    become current and lambda = lambda * down; otherwise lambda = lambda * up and the state of the last accepted
+ *    trial stands for the next trial. All `rounds` trials run.
+ *
+ * Outputs, from the final current state. out_poses double [batch][cams][12]: a held camera's twelve doubles bit for
+ * bit; with no accepted trial all of in_poses, bit for bit. out_points float [batch][p_stride][3] (NULL to skip):
+ * (float) of the final double for participating points; every other slot below counts[b] keeps the input bits; slots
+ * >= counts[b] are not written. out_inlier uint8 [batch][cams][o_stride] (NULL to skip): 1 for the observations active
+ * at the final state, 0 for every other slot below counts[b]; slots >= counts[b] are not written. out_counts int32
+ * [batch] (NULL to skip): the ones. out_cost double [batch][2] (NULL to skip): the cost of the given and of the
+ * final state. out_rounds int32 [batch] (NULL to skip): the accepted trials. out_poses may be in_poses and out_points
+ * may be p_xyz. p_stride 0: out_poses = in_poses, out_counts and out_rounds 0, both out_cost entries 0.0.
+ *
+ * Device pointers when io_on_device: asynchronous on the context's stream (one kernel, a workgroup per problem),
+ * graph-capturable once a first call of the shape has sized the workspace (417 bytes per observation slot and 120 per point slot). Host
+ * pointers otherwise: staged through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, in_poses, p_xyz, obs_xy or out_poses NULL; batch < 1; cams outside 1..8; a negative
+ * stride; o_stride < p_stride; rounds outside 1..16; threshold not finite or not > 0; a camera value not finite, fx
+ * or fy zero; lambda not finite or not > 0; up not finite or not > 1; down outside (0, 1].
+ * Not in this call, left for later: per-camera intrinsics, lens distortion (warp or undistort first), intrinsics
+ * refinement, more than 8 cameras, observation lists with a match index, Huber or other smooth robust losses,
+ * marginalisation priors.
+ */
+int fd_bundle_adjust(fd_ctx *ctx, int batch, int cams, const fd_ba_opts *opts,
+                     const double *in_poses, const uint8_t *cam_fixed,
+                     const float *p_xyz, const uint8_t *p_valid, const int32_t *counts, int32_t p_stride,
+                     const float *obs_xy, const uint8_t *obs_valid, int32_t o_stride,
+                     double *out_poses, float *out_points, uint8_t *out_inlier, int32_t *out_counts,
+                     double *out_cost, int32_t *out_rounds, int io_on_device);
+
 /* ---- Image warp by a homography or a camera model (MI355X extension) --------------------------------- */
 #define FD_WARP_HOMOGRAPHY 0 /* params: double[9], row-major 3 x 3, fd_ransac's out_model layout */
 #define FD_WARP_CAMERA 1     /* params: double[22], below */

@@ -150,6 +150,36 @@ public:
     PnpOptions &pnp_options() { return pnp_options_; }
     const PnpOptions &pnp_options() const { return pnp_options_; }
 
+    // Options of BundleAdjust.
+    struct BundleOptions {
+        int32_t kRounds = 8;         // 1..16 Levenberg-Marquardt trials, accepted and rejected
+        float kThreshold = 2.0f;     // pixels: truncation of the cost and the inlier gate
+        double kLambda = 1e-3;       // the initial damping, > 0
+        double kUp = 10.0;           // its factor after a rejected trial, > 1
+        double kDown = 0.1;          // its factor after an accepted trial, in (0, 1]
+    };
+
+    // Windowed bundle adjustment (fd_bundle_adjust of include/fd_hip.h): refines the poses of 1..8 cameras and the
+    // 3-D points they share, by Levenberg-Marquardt on the reprojection cost truncated at kThreshold pixels. poses[c]:
+    // R row-major, then t, X_c = R X + t (SolvePnP's / RefinePnP's / RecoverPose's; the first camera of a two-view
+    // start is the identity). observations[c][i] is camera c's image position of points[i]: tracks are slot-aligned
+    // (gather matched features first); observation_valid (optional, one vector per camera) and point_valid
+    // (optional): only the entries flagged exactly 1 take part. fixed (optional, one flag per camera): a non-zero flag
+    // holds the camera; without it camera 0 alone is held (hold two to pin the scale). No free camera is
+    // structure-only refinement. poses and points receive the result; inlier[c][i]: 1 if the observation is within
+    // kThreshold pixels at the final state. cost (optional): the cost before and after. accepted_rounds
+    // (optional): the accepted trials; with 0 poses and points keep their bits.
+    // False for no cameras or more than 8, no points, a vector of the wrong size, a camera or option out of range,
+    // or a libfdhip failure; poses and points are then left as given.
+    bool BundleAdjust(std::vector<std::array<double, 12>> &poses, std::vector<std::array<float, 3>> &points,
+                      const std::vector<std::vector<Vec2>> &observations, const Camera &camera,
+                      std::vector<std::vector<uint8_t>> &inlier, const std::vector<std::vector<uint8_t>> *observation_valid = nullptr,
+                      const std::vector<uint8_t> *point_valid = nullptr, const std::vector<uint8_t> *fixed = nullptr,
+                      std::array<double, 2> *cost = nullptr, int32_t *accepted_rounds = nullptr);
+
+    BundleOptions &bundle_options() { return bundle_options_; }
+    const BundleOptions &bundle_options() const { return bundle_options_; }
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -162,6 +192,7 @@ private:
     Options options_;
     PoseOptions pose_options_;
     PnpOptions pnp_options_;
+    BundleOptions bundle_options_;
     DeviceContext context_;
 };
 
