@@ -11,6 +11,28 @@
 
 namespace feature_detector {
 
+namespace {
+
+// The size checks of the calls on image pairs; nullptr when the arguments fit. inlier: nullptr where the call has none.
+const char *PairSizes(size_t n, size_t trains, const std::vector<uint8_t> *inlier, const std::vector<int32_t> *train_index,
+                      const std::vector<uint8_t> *valid) {
+    if (n == 0) return "no query points";
+    if (inlier && inlier->size() != n) return "one inlier flag per query point is needed";
+    if (train_index && train_index->size() != n) return "one train index per query point is needed";
+    if (valid && valid->size() != n) return "one valid flag per query point is needed";
+    if (!train_index && trains < n) return "without train_index every query point needs its train point";
+    return nullptr;
+}
+
+// The train (or image) positions as floats, with two floats of padding behind them.
+std::vector<float> FlattenPadded(const std::vector<Vec2> &uv) {
+    std::vector<float> t = Flatten(uv);
+    t.resize(t.size() + 2);
+    return t;
+}
+
+}  // namespace
+
 GeometricVerifier::~GeometricVerifier() = default;
 
 void GeometricVerifier::SetImageSize(int32_t rows, int32_t cols) {
@@ -26,16 +48,12 @@ bool GeometricVerifier::Verify(const std::vector<Vec2> &query_uv, const std::vec
     inlier.assign(n, 0);
     if (model) model->fill(0.0);
     if (best_hypothesis) *best_hypothesis = -1;
-    if (n == 0) return context_.Fail("Verify: no query points");
-    if (train_index && train_index->size() != n) return context_.Fail("Verify: one train index per query point is needed");
-    if (valid && valid->size() != n) return context_.Fail("Verify: one valid flag per query point is needed");
-    if (!train_index && train_uv.size() < n)
-        return context_.Fail("Verify: without train_index every query point needs its train point");
+    if (const char *why = PairSizes(n, train_uv.size(), nullptr, train_index, valid))
+        return context_.Fail(std::string("Verify: ") + why);
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
-    std::vector<float> t = Flatten(train_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const std::vector<float> t = FlattenPadded(train_uv);
     const fd_ransac_opts o{options_.kModel, options_.kHypotheses, options_.kSeed, options_.kThreshold,
                            options_.kCenterX, options_.kCenterY, options_.kScale};
     double m[9];
@@ -58,17 +76,12 @@ bool GeometricVerifier::Refit(const std::vector<Vec2> &query_uv, const std::vect
                               const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
     const size_t n = query_uv.size();
     if (accepted_rounds) *accepted_rounds = 0;
-    if (n == 0) return context_.Fail("Refit: no query points");
-    if (inlier.size() != n) return context_.Fail("Refit: one inlier flag per query point is needed");
-    if (train_index && train_index->size() != n) return context_.Fail("Refit: one train index per query point is needed");
-    if (valid && valid->size() != n) return context_.Fail("Refit: one valid flag per query point is needed");
-    if (!train_index && train_uv.size() < n)
-        return context_.Fail("Refit: without train_index every query point needs its train point");
+    if (const char *why = PairSizes(n, train_uv.size(), &inlier, train_index, valid))
+        return context_.Fail(std::string("Refit: ") + why);
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
-    std::vector<float> t = Flatten(train_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const std::vector<float> t = FlattenPadded(train_uv);
     const fd_refit_opts o{options_.kModel, rounds, options_.kThreshold, options_.kCenterX, options_.kCenterY, options_.kScale};
     std::vector<uint8_t> out_inlier(n);
     double m[9];
@@ -102,17 +115,12 @@ bool GeometricVerifier::RecoverPose(const std::vector<Vec2> &query_uv, const std
     points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
     point_valid.assign(n, 0);
     if (choice) *choice = -1;
-    if (n == 0) return context_.Fail("RecoverPose: no query points");
-    if (inlier.size() != n) return context_.Fail("RecoverPose: one inlier flag per query point is needed");
-    if (train_index && train_index->size() != n) return context_.Fail("RecoverPose: one train index per query point is needed");
-    if (valid && valid->size() != n) return context_.Fail("RecoverPose: one valid flag per query point is needed");
-    if (!train_index && train_uv.size() < n)
-        return context_.Fail("RecoverPose: without train_index every query point needs its train point");
+    if (const char *why = PairSizes(n, train_uv.size(), &inlier, train_index, valid))
+        return context_.Fail(std::string("RecoverPose: ") + why);
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
-    std::vector<float> t = Flatten(train_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const std::vector<float> t = FlattenPadded(train_uv);
     const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
     int32_t won = -1;
     const int rc = fd_pose_recover(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
@@ -139,17 +147,12 @@ bool GeometricVerifier::Triangulate(const std::vector<Vec2> &query_uv, const std
     points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
     point_valid.assign(n, 0);
     if (count) *count = 0;
-    if (n == 0) return context_.Fail("Triangulate: no query points");
-    if (inlier && inlier->size() != n) return context_.Fail("Triangulate: one inlier flag per query point is needed");
-    if (train_index && train_index->size() != n) return context_.Fail("Triangulate: one train index per query point is needed");
-    if (valid && valid->size() != n) return context_.Fail("Triangulate: one valid flag per query point is needed");
-    if (!train_index && train_uv.size() < n)
-        return context_.Fail("Triangulate: without train_index every query point needs its train point");
+    if (const char *why = PairSizes(n, train_uv.size(), inlier, train_index, valid))
+        return context_.Fail(std::string("Triangulate: ") + why);
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
-    std::vector<float> t = Flatten(train_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the train array
+    const std::vector<float> t = FlattenPadded(train_uv);
     const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
     int32_t found = 0;
     const int rc = fd_triangulate(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
@@ -197,8 +200,7 @@ bool GeometricVerifier::SolvePnP(const std::vector<std::array<float, 3>> &points
         return context_.Fail(std::string("SolvePnP: ") + why);
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
-    std::vector<float> t = Flatten(image_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the image positions
+    const std::vector<float> t = FlattenPadded(image_uv);
     const fd_pnp_opts o = PnpOpts(pnp_options_, camera, 1);
     int32_t best = -1;
     const int rc = fd_pnp_ransac(ctx, 1, &o, points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
@@ -226,8 +228,7 @@ bool GeometricVerifier::RefinePnP(const std::vector<std::array<float, 3>> &point
     if (inlier.size() != n) return context_.Fail("RefinePnP: one inlier flag per point is needed");
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
-    std::vector<float> t = Flatten(image_uv);
-    t.resize(t.size() + 2);  // two floats of padding behind the image positions
+    const std::vector<float> t = FlattenPadded(image_uv);
     const fd_pnp_opts o = PnpOpts(pnp_options_, camera, rounds);
     std::vector<uint8_t> out_inlier(n);
     double p[12];

@@ -231,8 +231,15 @@ class HostIo {
     std::vector<SlotArray> whole_, slots_;  // host-side outputs: {host, staged, bytes (whole_) or bytes per slot (slots_)}
 };
 
-// A call without slots (stride 0): every frame's count is 0, on the side of the outputs.
+// A call without slots (stride 0) launches nothing and writes its per-frame outputs on the side io_on_device
+// names: every byte of `out` set (0: zeros of any type; 0xFF: int32 -1), or `in` copied unless it is `out`
+// itself. A null `out` is skipped.
+int set_output(fd_ctx *c, void *out, int byte, size_t bytes, int io_on_device);
+int copy_output(fd_ctx *c, void *out, const void *in, size_t bytes, int io_on_device);
+// Every frame's count is 0.
 int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device);
+// n camera values (fx, fy, cx, cy per camera) into out: all finite, fx and fy non-zero.
+int check_camera(fd_ctx *c, const double *cam, int n, double *out);
 // k_flow_finish after zeroing its counts (fd_flow_lk, fd_points_refine).
 int finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin);
 

@@ -3,7 +3,8 @@
 // refinement of the reprojection error on its inliers. Every floating point operation is a double one, rounded
 // once (the build passes -ffp-contract=off), in the contract's order, so the result is a definite one that
 // tests/pnp_ref.py restates bit for bit. The sampler, the elimination and the Jacobi routine are fd_ransac's
-// (fd_solve.h).
+// (fd_solve.h), and so is the skeleton around them (fd_estimate.h: compaction, score and vote, the finish walk, the
+// refit's frame and slice tree): what stands here is the PnP problem's own arithmetic.
 //
 // k_pnp_compact, one workgroup per frame: the ordered list of the frame's correspondences (conditioned point
 // and ray, 40 bytes each) by a workgroup prefix over the take flags, and every slot's index in it.
@@ -17,7 +18,7 @@
 // one launch. The 27 sums of [J^T J | J^T r] stay in registers per thread (256 partials), an LDS tree combines
 // them in slices of 9, thread 0 solves the 6 x 7 system by the same elimination and updates the pose by the
 // Cayley transform, and every correspondence is classified again.
-#include "fd_solve.h"
+#include "fd_estimate.h"
 
 namespace fdk {
 namespace {
@@ -25,8 +26,7 @@ namespace {
 constexpr int kPnpRows = 11;                         // of the 12 rows of 6 picks
 constexpr int kPnpElems = kPnpRows * (kPnpRows + 1);  // 132 doubles per lane
 constexpr int kPnpSweeps = FD_POSE_SWEEPS;
-constexpr int kGn = 27;      // entries (i, j), i <= j, i < 6, of the 6 x 7 system [J^T J | J^T r], row-major
-constexpr int kGnSlice = 9;  // of them through the LDS tree at a time (18 KiB)
+constexpr int kGn = 27;  // entries (i, j), i <= j, i < 6, of the 6 x 7 system [J^T J | J^T r], row-major
 
 // A correspondence: the conditioned 3-D point and the normalised ray of its image point.
 struct Corr5 {
@@ -46,58 +46,32 @@ __device__ __forceinline__ bool pnp_inlier(const double (&P)[12], const Corr5 &p
 
 __global__ __launch_bounds__(kRansacThreads) void k_pnp_compact(PnpArgs a) {
     __shared__ uint32_t wsum[kRansacThreads / kWave];
-    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
-    const int nf = frame_count(a.q_counts, f, a.q_stride);
-    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
-    Corr5 *corr = reinterpret_cast<Corr5 *>(a.corr) + s0;
-    uint32_t base = 0;
-    for (int i0 = 0; i0 < nf; i0 += kRansacThreads) {
-        const int i = i0 + tid;
-        bool take = false;
-        Corr5 p = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (i < nf) {
-            take = !a.pair_valid || a.pair_valid[s0 + i] == 1;
-            take = take && (!a.p_valid || a.p_valid[s0 + i] == 1);
-            const int j = a.match_idx ? a.match_idx[s0 + i] : i;
-            take = take && j >= 0 && j < a.t_stride;
-            if (take) {
-                const float *q = a.p_xyz + 3 * (s0 + i);
-                const float qx = q[0], qy = q[1], qz = q[2];
-                const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[static_cast<int64_t>(f) * a.t_stride + j];
-                take = isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(t.x) && isfinite(t.y);
-                p.X = (static_cast<double>(qx) - a.center[0]) * a.scale;
-                p.Y = (static_cast<double>(qy) - a.center[1]) * a.scale;
-                p.Z = (static_cast<double>(qz) - a.center[2]) * a.scale;
-                p.bx = (static_cast<double>(t.x) - a.cam[2]) / a.cam[0];
-                p.by = (static_cast<double>(t.y) - a.cam[3]) / a.cam[1];
-            }
-        }
-        uint32_t tot;
-        const uint32_t pos = base + wg_excl_add<kRansacThreads>(take ? 1u : 0u, wsum, tot);
-        if (take) corr[pos] = p;  // pos < nf <= q_stride
-        if (i < nf) a.cidx[s0 + i] = take ? static_cast<int32_t>(pos) : -1;
-        base += tot;
-    }
-    if (tid == 0) {
-        a.n[f] = static_cast<int32_t>(base);
-        a.best[f] = 0ull;
-    }
+    compact_slots<Corr5>(a, wsum, [&](int64_t qi, int64_t ti, Corr5 &p) {
+        if (a.p_valid && a.p_valid[qi] != 1) return false;
+        const float *q = a.p_xyz + 3 * qi;
+        const float qx = q[0], qy = q[1], qz = q[2];
+        const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[ti];
+        p.X = (static_cast<double>(qx) - a.center[0]) * a.scale;
+        p.Y = (static_cast<double>(qy) - a.center[1]) * a.scale;
+        p.Z = (static_cast<double>(qz) - a.center[2]) * a.scale;
+        p.bx = (static_cast<double>(t.x) - a.cam[2]) / a.cam[0];
+        p.by = (static_cast<double>(t.y) - a.cam[3]) / a.cam[1];
+        return isfinite(qx) && isfinite(qy) && isfinite(qz) && isfinite(t.x) && isfinite(t.y);
+    });
 }
 
 __global__ __launch_bounds__(kWave) void k_pnp_hyp(PnpArgs a) {
     constexpr int M = 6;
     __shared__ double mat[kPnpElems * kWave];
     __shared__ Corr5 tile[kTile];
-    const int lane = lane_id();
-    const int groups = (a.hypotheses + kWave - 1) / kWave;
-    const int f = static_cast<int>(blockIdx.x) / groups;
-    const int h = (static_cast<int>(blockIdx.x) - f * groups) * kWave + lane;
+    int f, h;
+    hypothesis_index(a.hypotheses, f, h);
     const int n = a.n[f];
     const Corr5 *corr = reinterpret_cast<const Corr5 *>(a.corr) + static_cast<int64_t>(f) * a.q_stride;
     int pick[M];
     bool ok = h < a.hypotheses;
     ok = sample<M>(a.seed, f, h, n, pick) && ok;
-    double *A = mat + lane;
+    double *A = mat + lane_id();
 #pragma unroll
     for (int k = 0; k < M; ++k) {
         Corr5 p = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -129,24 +103,14 @@ __global__ __launch_bounds__(kWave) void k_pnp_hyp(PnpArgs a) {
         for (int c = 0; c < 12; ++c) x[c] = -x[c];
     }
 
-    int count = 0;
-    for (int base = 0; base < n; base += kTile) {  // n is the frame's: uniform over the workgroup
-        const int m = min(kTile, n - base);
-        __syncthreads();
-        for (int j = lane; j < m; j += kWave) tile[j] = corr[base + j];
-        __syncthreads();
-        for (int j = 0; j < m; ++j) count += pnp_inlier(x, tile[j], a.cam[0], a.cam[1], a.tt) ? 1 : 0;
-    }
+    const int count =
+        count_inliers(corr, n, tile, [&](const Corr5 &p) { return pnp_inlier(x, p, a.cam[0], a.cam[1], a.tt); });
     if (ok) {
-        double *dst = a.models + (static_cast<int64_t>(f) * a.hypotheses + h) * 12;
+        double *dst = model_at<12>(a.models, f, a.hypotheses, h);
 #pragma unroll
         for (int c = 0; c < 12; ++c) dst[c] = x[c];
     }
-    // valid hypotheses carry count + 1, so that a valid one with no inlier still beats "none" (0)
-    const uint32_t hi = ok ? static_cast<uint32_t>(count) + 1u : 0u;
-    const uint32_t top = wave_max_u32(hi);
-    const uint32_t lo = wave_max_u32(hi == top ? 0xFFFFFFFFu - static_cast<uint32_t>(h) : 0u);
-    if (lane == 0 && top) atomicMax(a.best + f, (static_cast<unsigned long long>(top) << 32) | lo);
+    vote_best(ok, count, h, a.best + f);
 }
 
 __global__ __launch_bounds__(kRansacThreads) void k_pnp_finish(PnpArgs a) {
@@ -156,27 +120,12 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_finish(PnpArgs a) {
     __shared__ int total;
     const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x), lane = lane_id();
     const int nf = frame_count(a.q_counts, f, a.q_stride);
-    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
-    const unsigned long long key = a.best[f];
-    const bool won = key != 0ull;
-    const int h = won ? static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key)) : -1;
+    int h;
     double P[12];
-#pragma unroll
-    for (int c = 0; c < 12; ++c) P[c] = won ? a.models[(static_cast<int64_t>(f) * a.hypotheses + h) * 12 + c] : 0.0;
+    const bool won = winner(a, f, h, P);
 
     if (tid < kWave) {  // winner to pose, on one wave
-        if (tid == 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) s = s + P[4 * k + i] * P[4 * k + j];
-                    mat3[3 * i + j] = s;
-                    mat3[9 + 3 * i + j] = i == j ? 1.0 : 0.0;
-                }
-        }
+        if (tid == 0) gram3_identity<4>(P, mat3);
         wave_lds_sync();
         jacobi<3, kPnpSweeps>(mat3, lane);
         wave_lds_sync();
@@ -217,27 +166,14 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_finish(PnpArgs a) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) pose_s[9 + c] = ok ? t[c] : 0.0;
             has_pose = ok ? 1 : 0;
-            total = 0;
         }
     }
     __syncthreads();
     const bool has = has_pose != 0;  // without a pose the frame is as one without a valid hypothesis
-    const Corr5 *corr = reinterpret_cast<const Corr5 *>(a.corr) + s0;
-    uint32_t mine = 0;
-    for (int i = tid; i < nf; i += kRansacThreads) {
-        bool in = false;
-        if (has) {
-            const int ci = a.cidx[s0 + i];
-            if (ci >= 0) in = pnp_inlier(P, corr[ci], a.cam[0], a.cam[1], a.tt);
-        }
-        if (a.out_inlier) a.out_inlier[s0 + i] = in ? 1 : 0;
-        mine += in ? 1u : 0u;
-    }
-    const uint32_t wave_n = wave_total_add(mine);
-    if (lane == 0 && wave_n) atomicAdd(&total, static_cast<int>(wave_n));
-    __syncthreads();
+    const int count = classify_slots<Corr5>(a, f, nf, has, &total,
+                                            [&](const Corr5 &p) { return pnp_inlier(P, p, a.cam[0], a.cam[1], a.tt); });
     if (tid != 0) return;
-    if (a.out_counts) a.out_counts[f] = total;
+    if (a.out_counts) a.out_counts[f] = count;
     if (a.out_best) a.out_best[f] = has ? h : -1;
     double *op = a.out_pose + static_cast<int64_t>(f) * 12;
 #pragma unroll
@@ -254,13 +190,12 @@ __device__ __forceinline__ void pose_matrix(const double *pose, double (&P)[12])
     }
 }
 
-// One workgroup per frame, all rounds. The support set lives in global memory by list position, the current
-// one and the round's candidate; thread t reads and writes the positions i = t (mod 256) only, which is also
-// the contract's partial t of the sums, so its 27 sums stay in registers over the frame.
+// One workgroup per frame, all rounds, in fd_estimate.h's refit frame: a thread's list positions i = t (mod 256)
+// are also the contract's partial t of the sums, so its 27 sums stay in registers over the frame.
 __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
-    __shared__ double red[kGnSlice * kRansacThreads];
+    __shared__ double red[kSlice * kRansacThreads];
     __shared__ double sys[6 * 7];
-    __shared__ double poses[2][12];  // the current pose and the round's candidate, by turns
+    __shared__ double poses[2][12];  // the current pose and the round's candidate, by turns with the support set's halves
     __shared__ int cand_ok;
     __shared__ int total;
     const PnpArgs &a = g.r;
@@ -270,31 +205,25 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
     const int n = a.n[f];
     const double fx = a.cam[0], fy = a.cam[1];
     const Corr5 *corr = reinterpret_cast<const Corr5 *>(a.corr) + s0;
-    uint8_t *mem = g.member + 2 * s0;
+    Support sup{g.member + 2 * s0, a.q_stride, 0};
     if (tid < 12) poses[0][tid] = g.in_pose[static_cast<int64_t>(f) * 12 + tid];
-    for (int s = tid; s < nf; s += kRansacThreads) {
-        const int ci = a.cidx[s0 + s];
-        if (ci >= 0) mem[ci] = g.in_inlier[s0 + s] == 1 ? 1 : 0;  // ci < n <= q_stride
-    }
-    __syncthreads();
+    load_members(a, f, nf, g.in_inlier, sup.mem);  // its barrier: the pose too
     double P[12];
     pose_matrix(poses[0], P);
     uint32_t mine = 0, mine0 = 0;
     for (int i = tid; i < n; i += kRansacThreads) {
-        mine0 += mem[i];
+        mine0 += sup.mem[i];
         mine += pnp_inlier(P, corr[i], fx, fy, a.tt) ? 1u : 0u;
     }
     const int members0 = wg_count(mine0, &total);
-    int count = wg_count(mine, &total);  // c_0: what in_pose classifies, not |S_0|
-    int cur = 0, pc = 0, done = 0;
+    sup.count = wg_count(mine, &total);  // c_0: what in_pose classifies, not |S_0|
 
     for (int round = 0; round < g.rounds; ++round) {  // every exit is uniform over the workgroup
         double pose[12];
 #pragma unroll
-        for (int c = 0; c < 12; ++c) pose[c] = poses[pc][c];
-        double *cand_s = poses[pc ^ 1];
-        const uint8_t *S = mem + cur * a.q_stride;
-        uint8_t *S2 = mem + (cur ^ 1) * a.q_stride;
+        for (int c = 0; c < 12; ++c) pose[c] = poses[sup.cur][c];
+        double *cand_s = poses[sup.cur ^ 1];
+        const uint8_t *S = sup.current();
         double acc[kGn];
 #pragma unroll
         for (int e = 0; e < kGn; ++e) acc[e] = 0.0;
@@ -317,32 +246,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
                     acc[e] = acc[e] + jy[r] * jy[c];
                 }
         }
-#pragma unroll
-        for (int sl = 0; sl < kGn / kGnSlice; ++sl) {
-#pragma unroll
-            for (int j = 0; j < kGnSlice; ++j) red[j * kRansacThreads + tid] = acc[sl * kGnSlice + j];
-            for (int step = kRansacThreads / 2; step >= 1; step >>= 1) {
-                __syncthreads();
-                if (tid < step) {
-#pragma unroll
-                    for (int j = 0; j < kGnSlice; ++j)
-                        red[j * kRansacThreads + tid] = red[j * kRansacThreads + tid] + red[j * kRansacThreads + tid + step];
-                }
-            }
-            __syncthreads();
-            if (tid < kGnSlice) {
-                int i = 0, rem = sl * kGnSlice + tid;  // entry (i, j) of the row-major upper part
-                while (rem >= 7 - i) {
-                    rem -= 7 - i;
-                    ++i;
-                }
-                const int j = i + rem;
-                const double v = red[tid * kRansacThreads];
-                sys[i * 7 + j] = v;
-                if (j < 6) sys[j * 7 + i] = v;
-            }
-            __syncthreads();
-        }
+        reduce_upper<kGn, 7, false>(acc, red, sys);
         if (tid == 0) {  // the step, and the pose it leads to
             double x[7];
             bool valid = null_vector<6, 1>(sys, x);
@@ -374,39 +278,20 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
         }
         __syncthreads();
         if (!cand_ok) break;
-        pose_matrix(poses[pc ^ 1], P);
-        mine = 0;
-        for (int i = tid; i < n; i += kRansacThreads) {
-            const bool in = pnp_inlier(P, corr[i], fx, fy, a.tt);
-            S2[i] = in ? 1 : 0;
-            mine += in ? 1u : 0u;
-        }
-        const int c = wg_count(mine, &total);
-        if (c < count) break;
-        count = c;
-        cur ^= 1;
-        pc ^= 1;
-        ++done;
+        pose_matrix(poses[sup.cur ^ 1], P);
+        const int c = reclassify(corr, n, sup.candidate(), &total, [&](const Corr5 &p) { return pnp_inlier(P, p, fx, fy, a.tt); });
+        if (!sup.accept(c)) break;
     }
 
-    __syncthreads();  // the members other threads wrote
-    const uint8_t *S = mem + cur * a.q_stride;
-    if (a.out_inlier)
-        for (int s = tid; s < nf; s += kRansacThreads) {
-            const int ci = a.cidx[s0 + s];
-            a.out_inlier[s0 + s] = ci >= 0 ? S[ci] : 0;
-        }
+    write_members(a, f, nf, sup.current());
     if (tid != 0) return;
-    if (a.out_counts) a.out_counts[f] = done ? count : members0;
-    if (g.out_rounds) g.out_rounds[f] = done;
-    // in_pose's bits as they are when no round was accepted (out_pose may be in_pose: read, then written)
-    const unsigned long long *ip = reinterpret_cast<const unsigned long long *>(g.in_pose) + static_cast<int64_t>(f) * 12;
-    unsigned long long *op = reinterpret_cast<unsigned long long *>(a.out_pose) + static_cast<int64_t>(f) * 12;
-    unsigned long long w[12];
-#pragma unroll
-    for (int c = 0; c < 12; ++c) w[c] = done ? static_cast<unsigned long long>(__double_as_longlong(poses[pc][c])) : ip[c];
-#pragma unroll
-    for (int c = 0; c < 12; ++c) op[c] = w[c];
+    if (a.out_counts) a.out_counts[f] = sup.done ? sup.count : members0;
+    if (g.out_rounds) g.out_rounds[f] = sup.done;
+    double *op = a.out_pose + static_cast<int64_t>(f) * 12;
+    if (sup.done)
+        copy_bits<12>(poses[sup.cur], op);
+    else  // in_pose's bits as they are (out_pose may be in_pose)
+        copy_bits<12>(g.in_pose + static_cast<int64_t>(f) * 12, op);
 }
 
 }  // namespace

@@ -26,8 +26,10 @@
 // writes the points. k_triangulate (fd_triangulate), one thread per slot, runs the same step for a given pose.
 // Neither needs k_ransac_compact: nothing in them depends on a correspondence's number in the list.
 //
-// The sampler, the elimination, the Jacobi routine and the small products are fd_solve.h's, shared with fd_pnp.hip.
-#include "fd_solve.h"
+// The sampler, the elimination, the Jacobi routine and the small products are fd_solve.h's, and the skeleton around
+// them (compaction, score and vote, the finish walk, the refit's frame and slice tree) is fd_estimate.h's, both
+// shared with fd_pnp.hip: what stands here is the two-view problem's own arithmetic.
+#include "fd_estimate.h"
 
 namespace fdk {
 namespace {
@@ -61,39 +63,15 @@ __device__ __forceinline__ bool inlier(const double (&h)[9], d4 p, double tt) {
 
 __global__ __launch_bounds__(kRansacThreads) void k_ransac_compact(RansacArgs a) {
     __shared__ uint32_t wsum[kRansacThreads / kWave];
-    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
-    const int nf = frame_count(a.q_counts, f, a.q_stride);
-    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
-    d4 *corr = reinterpret_cast<d4 *>(a.corr) + s0;
-    uint32_t base = 0;
-    for (int i0 = 0; i0 < nf; i0 += kRansacThreads) {
-        const int i = i0 + tid;
-        bool take = false;
-        d4 p = {0.0, 0.0, 0.0, 0.0};
-        if (i < nf) {
-            take = !a.pair_valid || a.pair_valid[s0 + i] == 1;
-            const int j = a.match_idx ? a.match_idx[s0 + i] : i;
-            take = take && j >= 0 && j < a.t_stride;
-            if (take) {
-                const float2 q = reinterpret_cast<const float2 *>(a.q_xy)[s0 + i];
-                const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[static_cast<int64_t>(f) * a.t_stride + j];
-                take = isfinite(q.x) && isfinite(q.y) && isfinite(t.x) && isfinite(t.y);
-                p.x = (static_cast<double>(q.x) - a.cx) * a.scale;
-                p.y = (static_cast<double>(q.y) - a.cy) * a.scale;
-                p.z = (static_cast<double>(t.x) - a.cx) * a.scale;
-                p.w = (static_cast<double>(t.y) - a.cy) * a.scale;
-            }
-        }
-        uint32_t tot;
-        const uint32_t pos = base + wg_excl_add<kRansacThreads>(take ? 1u : 0u, wsum, tot);
-        if (take) corr[pos] = p;  // pos < nf <= q_stride
-        if (i < nf) a.cidx[s0 + i] = take ? static_cast<int32_t>(pos) : -1;
-        base += tot;
-    }
-    if (tid == 0) {
-        a.n[f] = static_cast<int32_t>(base);
-        a.best[f] = 0ull;
-    }
+    compact_slots<d4>(a, wsum, [&](int64_t qi, int64_t ti, d4 &p) {
+        const float2 q = reinterpret_cast<const float2 *>(a.q_xy)[qi];
+        const float2 t = reinterpret_cast<const float2 *>(a.t_xy)[ti];
+        p.x = (static_cast<double>(q.x) - a.cx) * a.scale;
+        p.y = (static_cast<double>(q.y) - a.cy) * a.scale;
+        p.z = (static_cast<double>(t.x) - a.cx) * a.scale;
+        p.w = (static_cast<double>(t.y) - a.cy) * a.scale;
+        return isfinite(q.x) && isfinite(q.y) && isfinite(t.x) && isfinite(t.y);
+    });
 }
 
 template <int MODEL>
@@ -101,16 +79,14 @@ __global__ __launch_bounds__(kWave) void k_ransac_hyp(RansacArgs a) {
     constexpr int M = MODEL == kFundamental ? 8 : 4;
     __shared__ double mat[72 * kWave];
     __shared__ d4 tile[kTile];
-    const int lane = lane_id();
-    const int groups = (a.hypotheses + kWave - 1) / kWave;
-    const int f = static_cast<int>(blockIdx.x) / groups;
-    const int h = (static_cast<int>(blockIdx.x) - f * groups) * kWave + lane;
+    int f, h;
+    hypothesis_index(a.hypotheses, f, h);
     const int n = a.n[f];
     const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + static_cast<int64_t>(f) * a.q_stride;
     int pick[M];
     bool ok = h < a.hypotheses;
     ok = sample<M>(a.seed, f, h, n, pick) && ok;
-    double *A = mat + lane;
+    double *A = mat + lane_id();
 #pragma unroll
     for (int k = 0; k < M; ++k) {
         d4 p = {0.0, 0.0, 0.0, 0.0};
@@ -150,24 +126,13 @@ __global__ __launch_bounds__(kWave) void k_ransac_hyp(RansacArgs a) {
     double x[9];
     ok = null_vector<8, kWave>(A, x) && ok;
 
-    int count = 0;
-    for (int base = 0; base < n; base += kTile) {  // n is the frame's: uniform over the workgroup
-        const int m = min(kTile, n - base);
-        __syncthreads();
-        for (int j = lane; j < m; j += kWave) tile[j] = corr[base + j];
-        __syncthreads();
-        for (int j = 0; j < m; ++j) count += inlier<MODEL>(x, tile[j], a.tt) ? 1 : 0;
-    }
+    const int count = count_inliers(corr, n, tile, [&](const d4 &p) { return inlier<MODEL>(x, p, a.tt); });
     if (ok) {
-        double *dst = a.models + (static_cast<int64_t>(f) * a.hypotheses + h) * 9;
+        double *dst = model_at<9>(a.models, f, a.hypotheses, h);
 #pragma unroll
         for (int c = 0; c < 9; ++c) dst[c] = x[c];
     }
-    // valid hypotheses carry count + 1, so that a valid one with no inlier still beats "none" (0)
-    const uint32_t hi = ok ? static_cast<uint32_t>(count) + 1u : 0u;
-    const uint32_t top = wave_max_u32(hi);
-    const uint32_t lo = wave_max_u32(hi == top ? 0xFFFFFFFFu - static_cast<uint32_t>(h) : 0u);
-    if (lane == 0 && top) atomicMax(a.best + f, (static_cast<unsigned long long>(top) << 32) | lo);
+    vote_best(ok, count, h, a.best + f);
 }
 
 // The pixel-coordinate model of the conditioned one x, divided by its entry of largest magnitude, into om[9]
@@ -203,33 +168,14 @@ __device__ __forceinline__ void write_model(const double (&x)[9], double cx, dou
 template <int MODEL>
 __global__ __launch_bounds__(kRansacThreads) void k_ransac_finish(RansacArgs a) {
     __shared__ int total;
-    const int f = static_cast<int>(blockIdx.x), tid = static_cast<int>(threadIdx.x);
+    const int f = static_cast<int>(blockIdx.x);
     const int nf = frame_count(a.q_counts, f, a.q_stride);
-    const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
-    const unsigned long long key = a.best[f];
-    const bool has = key != 0ull;
-    const int h = has ? static_cast<int>(0xFFFFFFFFu - static_cast<uint32_t>(key)) : -1;
+    int h;
     double x[9];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) x[c] = has ? a.models[(static_cast<int64_t>(f) * a.hypotheses + h) * 9 + c] : 0.0;
-    if (tid == 0) total = 0;
-    __syncthreads();
-    const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + s0;
-    uint32_t mine = 0;
-    for (int i = tid; i < nf; i += kRansacThreads) {
-        bool in = false;
-        if (has) {
-            const int ci = a.cidx[s0 + i];
-            if (ci >= 0) in = inlier<MODEL>(x, corr[ci], a.tt);
-        }
-        if (a.out_inlier) a.out_inlier[s0 + i] = in ? 1 : 0;
-        mine += in ? 1u : 0u;
-    }
-    const uint32_t wave_n = wave_total_add(mine);
-    if (lane_id() == 0 && wave_n) atomicAdd(&total, static_cast<int>(wave_n));
-    __syncthreads();
-    if (tid != 0) return;
-    if (a.out_counts) a.out_counts[f] = total;
+    const bool has = winner(a, f, h, x);
+    const int count = classify_slots<d4>(a, f, nf, has, &total, [&](const d4 &p) { return inlier<MODEL>(x, p, a.tt); });
+    if (threadIdx.x != 0) return;
+    if (a.out_counts) a.out_counts[f] = count;
     if (a.out_best) a.out_best[f] = h;
     double *om = a.out_model + static_cast<int64_t>(f) * 9;
     if (!has) {
@@ -242,8 +188,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_finish(RansacArgs a) 
 
 // ---- fd_ransac_refit: the least-squares refit of a model on its inliers ------------------------------------
 constexpr int kSweeps = FD_REFIT_SWEEPS;
-constexpr int kNormal = 45;  // entries (a, b), a <= b, of the 9 x 9 normal matrix, row-major
-constexpr int kSlice = 9;    // of them through the LDS tree at a time: 9 * 256 * 8 B = 18 KiB (45 at once: 90 KiB)
+constexpr int kNormal = 45;  // entries (a, b), a <= b, of the 9 x 9 normal matrix, row-major (all at once through the tree: 90 KiB)
 
 // acc += row^T row, the 45 entries in order, each one product and one sum.
 __device__ __forceinline__ void add_row(double (&acc)[kNormal], const double (&r)[9]) {
@@ -254,9 +199,8 @@ __device__ __forceinline__ void add_row(double (&acc)[kNormal], const double (&r
         for (int j = i; j < 9; ++j, ++e) acc[e] = acc[e] + r[i] * r[j];
 }
 
-// One workgroup per frame, all rounds. The support set lives in global memory by list position, the current
-// one and the round's candidate; thread t reads and writes the positions i = t (mod 256) only, which is also
-// the contract's partial t of the normal matrix, so its 45 sums stay in registers over the frame.
+// One workgroup per frame, all rounds, in fd_estimate.h's refit frame: a thread's list positions i = t (mod 256)
+// are also the contract's partial t of the normal matrix, so its 45 sums stay in registers over the frame.
 template <int MODEL>
 __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
     constexpr int M = MODEL == kFundamental ? 8 : 4;
@@ -271,20 +215,14 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
     const int64_t s0 = static_cast<int64_t>(f) * a.q_stride;
     const int n = a.n[f];
     const d4 *corr = reinterpret_cast<const d4 *>(a.corr) + s0;
-    uint8_t *mem = g.member + 2 * s0;
-    for (int s = tid; s < nf; s += kRansacThreads) {
-        const int ci = a.cidx[s0 + s];
-        if (ci >= 0) mem[ci] = g.in_inlier[s0 + s] == 1 ? 1 : 0;  // ci < n <= q_stride
-    }
-    __syncthreads();
+    Support sup{g.member + 2 * s0, a.q_stride, 0};
+    load_members(a, f, nf, g.in_inlier, sup.mem);
     uint32_t mine = 0;
-    for (int i = tid; i < n; i += kRansacThreads) mine += mem[i];
-    int count = wg_count(mine, &total);
-    int cur = 0, done = 0;
+    for (int i = tid; i < n; i += kRansacThreads) mine += sup.mem[i];
+    sup.count = wg_count(mine, &total);
 
-    for (int round = 0; round < g.rounds && count >= M; ++round) {  // every exit is uniform over the workgroup
-        const uint8_t *S = mem + cur * a.q_stride;
-        uint8_t *S2 = mem + (cur ^ 1) * a.q_stride;
+    for (int round = 0; round < g.rounds && sup.count >= M; ++round) {  // every exit is uniform over the workgroup
+        const uint8_t *S = sup.current();
         double acc[kNormal];
 #pragma unroll
         for (int e = 0; e < kNormal; ++e) acc[e] = 0.0;
@@ -302,32 +240,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
                 add_row(acc, r1);
             }
         }
-#pragma unroll
-        for (int sl = 0; sl < kNormal / kSlice; ++sl) {
-#pragma unroll
-            for (int j = 0; j < kSlice; ++j) red[j * kRansacThreads + tid] = acc[sl * kSlice + j];
-            for (int step = kRansacThreads / 2; step >= 1; step >>= 1) {
-                __syncthreads();
-                if (tid < step) {
-#pragma unroll
-                    for (int j = 0; j < kSlice; ++j)
-                        red[j * kRansacThreads + tid] = red[j * kRansacThreads + tid] + red[j * kRansacThreads + tid + step];
-                }
-            }
-            __syncthreads();
-            if (tid < kSlice) {
-                int i = 0, rem = sl * kSlice + tid;  // entry (i, j) of the row-major upper triangle
-                while (rem >= 9 - i) {
-                    rem -= 9 - i;
-                    ++i;
-                }
-                const int j = i + rem;
-                const double v = red[tid * kRansacThreads];
-                mat[i * 9 + j] = v;
-                mat[j * 9 + i] = v;
-            }
-            __syncthreads();
-        }
+        reduce_upper<kNormal, 9, true>(acc, red, mat);
         if (tid < 81) mat[81 + tid] = tid / 9 == tid % 9 ? 1.0 : 0.0;
         __syncthreads();
         if (tid < kWave) jacobi<9, kSweeps>(mat, lane);
@@ -347,18 +260,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
         }
         valid = valid && d2 > 1e-12 * dmax;
         if (MODEL == kFundamental) {
-            if (tid == 0) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) s = s + x[3 * k + i] * x[3 * k + j];
-                        mat3[3 * i + j] = s;
-                        mat3[9 + 3 * i + j] = i == j ? 1.0 : 0.0;
-                    }
-            }
+            if (tid == 0) gram3_identity<3>(x, mat3);
             __syncthreads();
             if (tid < kWave) jacobi<3, kSweeps>(mat3, lane);
             __syncthreads();
@@ -381,31 +283,17 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
             }
         }
         if (!valid) break;
-        mine = 0;
-        for (int i = tid; i < n; i += kRansacThreads) {
-            const bool in = inlier<MODEL>(x, corr[i], a.tt);
-            S2[i] = in ? 1 : 0;
-            mine += in ? 1u : 0u;
-        }
-        const int c = wg_count(mine, &total);
-        if (c < count) break;
-        count = c;
-        cur ^= 1;
-        ++done;
+        const int c = reclassify(corr, n, sup.candidate(), &total, [&](const d4 &p) { return inlier<MODEL>(x, p, a.tt); });
+        if (!sup.accept(c)) break;
         if (tid == 0) {  // the accepted model: thread 0 writes it out at the end
 #pragma unroll
             for (int k = 0; k < 9; ++k) accepted[k] = x[k];
         }
     }
 
-    __syncthreads();  // the members other threads wrote
-    const uint8_t *S = mem + cur * a.q_stride;
-    if (a.out_inlier)
-        for (int s = tid; s < nf; s += kRansacThreads) {
-            const int ci = a.cidx[s0 + s];
-            a.out_inlier[s0 + s] = ci >= 0 ? S[ci] : 0;
-        }
+    write_members(a, f, nf, sup.current());
     if (tid != 0) return;
+    const int count = sup.count, done = sup.done;
     // What only this epilogue needs is read from the kernel argument segment here (the argument block is the
     // kernel's one parameter): named through `g`, the loads sit at the kernel's entry and their scalar
     // registers stay occupied over the rounds, two of them spilled.
@@ -416,12 +304,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_ransac_refit(RefitArgs g) {
     if (out_rounds) out_rounds[f] = done;
     double *om = e->r.out_model + static_cast<int64_t>(f) * 9;
     if (done == 0) {  // in_model's bits as they are
-        const unsigned long long *im = reinterpret_cast<const unsigned long long *>(e->in_model) + static_cast<int64_t>(f) * 9;
-        unsigned long long w[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) w[c] = im[c];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) reinterpret_cast<unsigned long long *>(om)[c] = w[c];
+        copy_bits<9>(e->in_model + static_cast<int64_t>(f) * 9, om);
         return;
     }
     double xa[9];
@@ -518,16 +401,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_pose_recover(PoseArgs a) {
             matmul3(KtT, FK, E);
 #pragma unroll
             for (int c = 0; c < 9; ++c) em[c] = E[c];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) s = s + E[3 * k + i] * E[3 * k + j];
-                    mat3[3 * i + j] = s;
-                    mat3[9 + 3 * i + j] = i == j ? 1.0 : 0.0;
-                }
+            gram3_identity<3>(E, mat3);
         }
         wave_lds_sync();
         jacobi<3, kPoseSweeps>(mat3, lane);

@@ -22,32 +22,21 @@ int fd_bundle_adjust(fd_ctx *c, int batch, int cams, const fd_ba_opts *opts, con
     if (!std::isfinite(opts->threshold) || !(opts->threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
     fdk::BaArgs a{};
     const double cam[4] = {opts->fx, opts->fy, opts->cx, opts->cy};
-    for (int k = 0; k < 4; ++k) {
-        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
-        a.cam[k] = cam[k];
-    }
-    if (cam[0] == 0.0 || cam[1] == 0.0) return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
+    int rc = check_camera(c, cam, 4, a.cam);
+    if (rc) return rc;
     if (!std::isfinite(opts->lambda) || !(opts->lambda > 0.0)) return fail(c, FD_ERR_INVALID, "lambda must be finite and > 0");
     if (!std::isfinite(opts->up) || !(opts->up > 1.0)) return fail(c, FD_ERR_INVALID, "up must be finite and > 1");
     if (!(opts->down > 0.0 && opts->down <= 1.0)) return fail(c, FD_ERR_INVALID, "down must be in (0, 1]");
     FD_HIP_TRY(c, hipSetDevice(c->device));
-    int rc = refuse_sync_under_capture(c, io_on_device);
+    rc = refuse_sync_under_capture(c, io_on_device);
     if (rc) return rc;
     const size_t poses = static_cast<size_t>(12) * cams * batch;
     if (p_stride == 0) {  // no slots: no trial is accepted
-        if (io_on_device) {
-            if (out_poses != in_poses)
-                FD_HIP_TRY(c, hipMemcpyAsync(out_poses, in_poses, sizeof(double) * poses, hipMemcpyDeviceToDevice, c->stream));
-            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_rounds) FD_HIP_TRY(c, hipMemsetAsync(out_rounds, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_cost) FD_HIP_TRY(c, hipMemsetAsync(out_cost, 0, sizeof(double) * 2 * batch, c->stream));
-        } else {
-            if (out_poses != in_poses) std::copy(in_poses, in_poses + poses, out_poses);
-            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
-            if (out_rounds) std::fill(out_rounds, out_rounds + batch, 0);
-            if (out_cost) std::fill(out_cost, out_cost + static_cast<size_t>(2) * batch, 0.0);
-        }
-        return FD_OK;
+        rc = copy_output(c, out_poses, in_poses, sizeof(double) * poses, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
+        if (!rc) rc = set_output(c, out_cost, 0, sizeof(double) * 2 * batch, io_on_device);
+        return rc;
     }
     a.batch = batch;
     a.cams = cams;

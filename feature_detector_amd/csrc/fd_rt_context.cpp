@@ -6,6 +6,7 @@
 // fd_rt_ransac.cpp (RANSAC); fd_ctx.h is their shared header. The keypoint stages' host-pointer calls all
 // go through one staging path, HostIo, below.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -176,9 +177,30 @@ int HostIo::finish(const int32_t *counts, int batch, int32_t stride) {
     return copy_back_written(c_, counts, batch, stride, slots_);  // synchronises
 }
 
+int set_output(fd_ctx *c, void *out, int byte, size_t bytes, int io_on_device) {
+    if (out && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out, byte, bytes, c->stream));
+    if (out && !io_on_device) std::memset(out, byte, bytes);
+    return FD_OK;
+}
+
+int copy_output(fd_ctx *c, void *out, const void *in, size_t bytes, int io_on_device) {
+    if (!out || out == in) return FD_OK;
+    if (io_on_device) FD_HIP_TRY(c, hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (!io_on_device) std::memcpy(out, in, bytes);
+    return FD_OK;
+}
+
 int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device) {
-    if (out_counts && io_on_device) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-    if (out_counts && !io_on_device) std::fill(out_counts, out_counts + batch, 0);
+    return set_output(c, out_counts, 0, sizeof(int32_t) * batch, io_on_device);
+}
+
+int check_camera(fd_ctx *c, const double *cam, int n, double *out) {
+    for (int k = 0; k < n; ++k) {
+        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
+        out[k] = cam[k];
+    }
+    for (int k = 0; k < n; k += 4)
+        if (cam[k] == 0.0 || cam[k + 1] == 0.0) return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
     return FD_OK;
 }
 

@@ -1,8 +1,8 @@
 // Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac), the least-squares
 // refit of its model (fd_ransac_refit), the pose of a fundamental matrix (fd_pose_recover) and triangulation
 // (fd_triangulate) over the kernels of fd_ransac.hip, and the absolute pose from 3-D points (fd_pnp_ransac,
-// fd_pnp_refit) over those of fd_pnp.hip.
-#include <algorithm>
+// fd_pnp_refit) over those of fd_pnp.hip. The six calls share their slot checks, the staging of the pair arrays,
+// the workspace of the compaction kernels and the outputs of a call without slots (fd_ctx.h).
 #include <cmath>
 
 #include "fd_ctx.h"
@@ -11,130 +11,129 @@ using namespace fdrt;
 
 namespace {
 
-// What fd_ransac and fd_ransac_refit ask of the arguments they share.
-int check_pairs(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx, int32_t model,
-                float threshold, float center_x, float center_y, float scale) {
+// What every call asks of its [batch][q_stride] slots and their partners among [batch][t_stride].
+int check_slots(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx) {
     if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
     if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
     if (!match_idx && t_stride < q_stride)
         return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    if (model != FD_RANSAC_FUNDAMENTAL && model != FD_RANSAC_HOMOGRAPHY)
-        return fail(c, FD_ERR_INVALID, "model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
-    if (!std::isfinite(threshold) || !(threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
-    if (!std::isfinite(center_x) || !std::isfinite(center_y))
-        return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
     return FD_OK;
 }
 
-// The fields both calls fill alike, and the workspace of k_ransac_compact.
-int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_t t_stride, int32_t model, float threshold,
-              float center_x, float center_y, float scale) {
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
+// The slot fields of an argument block (RansacArgs, PoseArgs, PnpArgs).
+template <class A>
+void slot_fields(A &a, int batch, int32_t q_stride, int32_t t_stride) {
     a.batch = batch;
     a.q_stride = q_stride;
     a.t_stride = t_stride;
-    a.model = model;
-    a.cx = static_cast<double>(center_x);
-    a.cy = static_cast<double>(center_y);
-    a.scale = static_cast<double>(scale);
-    const double t = static_cast<double>(threshold) * a.scale;
-    a.tt = t * t;
-    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 4 * qs, a.corr));
-    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
-    FD_HIP_TRY(c, ensure_as(c, c->g_n, batch, a.n));
-    FD_HIP_TRY(c, ensure_as(c, c->g_best, batch, a.best));
-    return FD_OK;
 }
 
-// What fd_triangulate and fd_pose_recover ask of the arguments they share, and the option fields of the kernels'
-// argument block.
-int pose_args(fd_ctx *c, fdk::PoseArgs &a, int batch, const fd_pose_opts *o, int32_t q_stride, int32_t t_stride,
-              const int32_t *match_idx) {
-    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
-    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
-    if (!match_idx && t_stride < q_stride)
-        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    const double cam[8] = {o->fx_q, o->fy_q, o->cx_q, o->cy_q, o->fx_t, o->fy_t, o->cx_t, o->cy_t};
-    for (int k = 0; k < 8; ++k) {
-        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
-        a.cam[k] = cam[k];
-    }
-    if (cam[0] == 0.0 || cam[1] == 0.0 || cam[4] == 0.0 || cam[5] == 0.0)
-        return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
-    if (!(o->max_depth > 0.0f)) return fail(c, FD_ERR_INVALID, "max_depth must be > 0");
-    if (!(o->min_parallax >= 0.0f && o->min_parallax <= 1.0f)) return fail(c, FD_ERR_INVALID, "min_parallax must be in [0, 1]");
-    a.batch = batch;
-    a.q_stride = q_stride;
-    a.t_stride = t_stride;
-    const double m = static_cast<double>(o->min_parallax);
-    a.mm = m * m;
-    a.D = static_cast<double>(o->max_depth);
-    return FD_OK;
-}
-
-// The pair arrays of both calls, staged or handed on.
-int pose_pairs(fd_ctx *c, HostIo &io, fdk::PoseArgs &a, const float *q_xy, const int32_t *q_counts, const float *t_xy,
-               const int32_t *match_idx, const uint8_t *pair_valid, const uint8_t *in_inlier) {
-    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride, ts = static_cast<size_t>(a.batch) * a.t_stride;
-    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, a.q_xy));
-    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
-    FD_HIP_TRY(c, io.in(q_counts, a.batch, a.q_counts));
-    FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
-    FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
-    FD_HIP_TRY(c, io.in(in_inlier, qs, a.in_inlier));
-    return FD_OK;
-}
-
-// What fd_pnp_ransac and fd_pnp_refit ask of the arguments they share, the fields both fill alike, and the
-// workspace of k_pnp_compact. The conditioning is the caller's (fd_pnp_ransac) or none (fd_pnp_refit).
-int pnp_args(fd_ctx *c, fdk::PnpArgs &a, int batch, const fd_pnp_opts *o, int32_t q_stride, int32_t t_stride,
-             const int32_t *match_idx, bool conditioned) {
-    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
-    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
-    if (!match_idx && t_stride < q_stride)
-        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    if (!std::isfinite(o->threshold) || !(o->threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
-    const double cam[4] = {o->fx, o->fy, o->cx, o->cy};
-    for (int k = 0; k < 4; ++k) {
-        if (!std::isfinite(cam[k])) return fail(c, FD_ERR_INVALID, "camera values must be finite");
-        a.cam[k] = cam[k];
-    }
-    if (cam[0] == 0.0 || cam[1] == 0.0) return fail(c, FD_ERR_INVALID, "fx and fy must be non-zero");
-    for (int k = 0; k < 3; ++k) {
-        if (conditioned && !std::isfinite(o->center[k])) return fail(c, FD_ERR_INVALID, "center must be finite");
-        a.center[k] = conditioned ? o->center[k] : 0.0;
-    }
-    if (conditioned && (!std::isfinite(o->scale) || !(o->scale > 0.0))) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
-    a.scale = conditioned ? o->scale : 1.0;
-    a.batch = batch;
-    a.q_stride = q_stride;
-    a.t_stride = t_stride;
-    const double t = static_cast<double>(o->threshold);
-    a.tt = t * t;
-    return FD_OK;
-}
-
-int pnp_workspace(fd_ctx *c, fdk::PnpArgs &a) {
+// The workspace of a compaction kernel (RansacArgs, PnpArgs): the frames' lists of `doubles` per correspondence,
+// every slot's index in them, their lengths and the frames' vote words.
+template <class A>
+int list_workspace(fd_ctx *c, A &a, size_t doubles) {
     const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
-    FD_HIP_TRY(c, ensure_as(c, c->g_corr, 5 * qs, a.corr));
+    FD_HIP_TRY(c, ensure_as(c, c->g_corr, doubles * qs, a.corr));
     FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
     FD_HIP_TRY(c, ensure_as(c, c->g_n, a.batch, a.n));
     FD_HIP_TRY(c, ensure_as(c, c->g_best, a.batch, a.best));
     return FD_OK;
 }
 
-// The input arrays of both calls, staged or handed on.
-int pnp_inputs(fd_ctx *c, HostIo &io, fdk::PnpArgs &a, const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts,
-               const float *t_xy, const int32_t *match_idx, const uint8_t *pair_valid) {
+// The pair arrays every call has behind its query side's own (q_xy, or p_xyz and p_valid), staged or handed on.
+template <class A>
+int stage_pairs(fd_ctx *c, HostIo &io, A &a, const float *t_xy, const int32_t *q_counts, const int32_t *match_idx,
+                const uint8_t *pair_valid) {
     const size_t qs = static_cast<size_t>(a.batch) * a.q_stride, ts = static_cast<size_t>(a.batch) * a.t_stride;
-    FD_HIP_TRY(c, io.in(p_xyz, 3 * qs, a.p_xyz));
-    FD_HIP_TRY(c, io.in(p_valid, qs, a.p_valid));
     FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
     FD_HIP_TRY(c, io.in(q_counts, a.batch, a.q_counts));
     FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
     FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
     return FD_OK;
+}
+
+// What fd_ransac and fd_ransac_refit ask of the arguments they share (o: fd_ransac_opts or fd_refit_opts).
+template <class O>
+int check_pairs(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx, const O &o) {
+    const int rc = check_slots(c, batch, q_stride, t_stride, match_idx);
+    if (rc) return rc;
+    if (o.model != FD_RANSAC_FUNDAMENTAL && o.model != FD_RANSAC_HOMOGRAPHY)
+        return fail(c, FD_ERR_INVALID, "model must be FD_RANSAC_FUNDAMENTAL or FD_RANSAC_HOMOGRAPHY");
+    if (!std::isfinite(o.threshold) || !(o.threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    if (!std::isfinite(o.center_x) || !std::isfinite(o.center_y))
+        return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
+    if (!std::isfinite(o.scale) || !(o.scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    return FD_OK;
+}
+
+// The pair arrays of the two-view calls (RansacArgs, PoseArgs), staged or handed on.
+template <class A>
+int pair_inputs(fd_ctx *c, HostIo &io, A &a, const float *q_xy, const int32_t *q_counts, const float *t_xy,
+                const int32_t *match_idx, const uint8_t *pair_valid) {
+    FD_HIP_TRY(c, io.in(q_xy, 2 * static_cast<size_t>(a.batch) * a.q_stride, a.q_xy));
+    return stage_pairs(c, io, a, t_xy, q_counts, match_idx, pair_valid);
+}
+
+// The fields both calls fill alike, and the workspace of k_ransac_compact.
+template <class O>
+int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_t t_stride, const O &o) {
+    slot_fields(a, batch, q_stride, t_stride);
+    a.model = o.model;
+    a.cx = static_cast<double>(o.center_x);
+    a.cy = static_cast<double>(o.center_y);
+    a.scale = static_cast<double>(o.scale);
+    const double t = static_cast<double>(o.threshold) * a.scale;
+    a.tt = t * t;
+    return list_workspace(c, a, 4);
+}
+
+// What fd_triangulate and fd_pose_recover ask of the arguments they share, and the option fields of the kernels'
+// argument block.
+int pose_args(fd_ctx *c, fdk::PoseArgs &a, int batch, const fd_pose_opts *o, int32_t q_stride, int32_t t_stride,
+              const int32_t *match_idx) {
+    int rc = check_slots(c, batch, q_stride, t_stride, match_idx);
+    if (rc) return rc;
+    const double cam[8] = {o->fx_q, o->fy_q, o->cx_q, o->cy_q, o->fx_t, o->fy_t, o->cx_t, o->cy_t};
+    rc = check_camera(c, cam, 8, a.cam);
+    if (rc) return rc;
+    if (!(o->max_depth > 0.0f)) return fail(c, FD_ERR_INVALID, "max_depth must be > 0");
+    if (!(o->min_parallax >= 0.0f && o->min_parallax <= 1.0f)) return fail(c, FD_ERR_INVALID, "min_parallax must be in [0, 1]");
+    slot_fields(a, batch, q_stride, t_stride);
+    const double m = static_cast<double>(o->min_parallax);
+    a.mm = m * m;
+    a.D = static_cast<double>(o->max_depth);
+    return FD_OK;
+}
+
+// What fd_pnp_ransac and fd_pnp_refit ask of the arguments they share, and the fields both fill alike. The
+// conditioning is the caller's (fd_pnp_ransac) or none (fd_pnp_refit).
+int pnp_args(fd_ctx *c, fdk::PnpArgs &a, int batch, const fd_pnp_opts *o, int32_t q_stride, int32_t t_stride,
+             const int32_t *match_idx, bool conditioned) {
+    int rc = check_slots(c, batch, q_stride, t_stride, match_idx);
+    if (rc) return rc;
+    if (!std::isfinite(o->threshold) || !(o->threshold > 0.0f)) return fail(c, FD_ERR_INVALID, "threshold must be finite and > 0");
+    const double cam[4] = {o->fx, o->fy, o->cx, o->cy};
+    rc = check_camera(c, cam, 4, a.cam);
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) {
+        if (conditioned && !std::isfinite(o->center[k])) return fail(c, FD_ERR_INVALID, "center must be finite");
+        a.center[k] = conditioned ? o->center[k] : 0.0;
+    }
+    if (conditioned && (!std::isfinite(o->scale) || !(o->scale > 0.0))) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    a.scale = conditioned ? o->scale : 1.0;
+    slot_fields(a, batch, q_stride, t_stride);
+    const double t = static_cast<double>(o->threshold);
+    a.tt = t * t;
+    return FD_OK;
+}
+
+// The workspace of k_pnp_compact and the input arrays of both calls, staged or handed on.
+int pnp_inputs(fd_ctx *c, HostIo &io, fdk::PnpArgs &a, const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts,
+               const float *t_xy, const int32_t *match_idx, const uint8_t *pair_valid) {
+    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
+    FD_HIP_TRY(c, io.in(p_xyz, 3 * qs, a.p_xyz));
+    FD_HIP_TRY(c, io.in(p_valid, qs, a.p_valid));
+    return stage_pairs(c, io, a, t_xy, q_counts, match_idx, pair_valid);
 }
 
 }  // namespace
@@ -157,21 +156,15 @@ int fd_pnp_ransac(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_
     if (rc) return rc;
     const size_t poses = static_cast<size_t>(12) * batch;
     if (q_stride == 0) {  // no slots: no frame has a pose
-        if (io_on_device) {
-            FD_HIP_TRY(c, hipMemsetAsync(out_pose, 0, sizeof(double) * poses, c->stream));
-            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_best) FD_HIP_TRY(c, hipMemsetAsync(out_best, 0xFF, sizeof(int32_t) * batch, c->stream));
-        } else {
-            std::fill(out_pose, out_pose + poses, 0.0);
-            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
-            if (out_best) std::fill(out_best, out_best + batch, -1);
-        }
-        return FD_OK;
+        rc = set_output(c, out_pose, 0, sizeof(double) * poses, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        if (!rc) rc = set_output(c, out_best, 0xFF, sizeof(int32_t) * batch, io_on_device);
+        return rc;
     }
     const size_t qs = static_cast<size_t>(batch) * q_stride;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
-    rc = pnp_workspace(c, a);
+    rc = list_workspace(c, a, 5);
     if (rc) return rc;
     FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 12, a.models));
     HostIo io(c, io_on_device);
@@ -200,21 +193,14 @@ int fd_pnp_refit(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_x
     if (rc) return rc;
     const size_t poses = static_cast<size_t>(12) * batch;
     if (q_stride == 0) {  // no slots: no round is accepted
-        if (io_on_device) {
-            if (out_pose != in_pose)
-                FD_HIP_TRY(c, hipMemcpyAsync(out_pose, in_pose, sizeof(double) * poses, hipMemcpyDeviceToDevice, c->stream));
-            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_rounds) FD_HIP_TRY(c, hipMemsetAsync(out_rounds, 0, sizeof(int32_t) * batch, c->stream));
-        } else {
-            if (out_pose != in_pose) std::copy(in_pose, in_pose + poses, out_pose);
-            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
-            if (out_rounds) std::fill(out_rounds, out_rounds + batch, 0);
-        }
-        return FD_OK;
+        rc = copy_output(c, out_pose, in_pose, sizeof(double) * poses, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
+        return rc;
     }
     const size_t qs = static_cast<size_t>(batch) * q_stride;
     g.rounds = opts->rounds;
-    rc = pnp_workspace(c, g.r);
+    rc = list_workspace(c, g.r, 5);
     if (rc) return rc;
     FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
     HostIo io(c, io_on_device);  // 8 inputs and 4 outputs: the whole staging pool
@@ -230,46 +216,36 @@ int fd_pnp_refit(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_x
     return io.finish(q_counts, batch, q_stride);
 }
 
-
 int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_xy, const int32_t *q_counts,
               int32_t q_stride, const float *t_xy, int32_t t_stride, const int32_t *match_idx, const uint8_t *pair_valid,
               double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xy || !t_xy || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
-    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, opts->model, opts->threshold, opts->center_x,
-                         opts->center_y, opts->scale);
+    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, *opts);
     if (rc) return rc;
     if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
         return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
     FD_HIP_TRY(c, hipSetDevice(c->device));
     rc = refuse_sync_under_capture(c, io_on_device);
     if (rc) return rc;
+    const size_t models = static_cast<size_t>(9) * batch;
     if (q_stride == 0) {  // no slots: no frame has a model
-        if (io_on_device) {
-            FD_HIP_TRY(c, hipMemsetAsync(out_model, 0, sizeof(double) * 9 * batch, c->stream));
-            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_best) FD_HIP_TRY(c, hipMemsetAsync(out_best, 0xFF, sizeof(int32_t) * batch, c->stream));
-        } else {
-            std::fill(out_model, out_model + static_cast<size_t>(9) * batch, 0.0);
-            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
-            if (out_best) std::fill(out_best, out_best + batch, -1);
-        }
-        return FD_OK;
+        rc = set_output(c, out_model, 0, sizeof(double) * models, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        if (!rc) rc = set_output(c, out_best, 0xFF, sizeof(int32_t) * batch, io_on_device);
+        return rc;
     }
-    const size_t qs = static_cast<size_t>(batch) * q_stride, ts = static_cast<size_t>(batch) * t_stride;
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
     fdk::RansacArgs a{};
-    rc = pair_args(c, a, batch, q_stride, t_stride, opts->model, opts->threshold, opts->center_x, opts->center_y, opts->scale);
+    rc = pair_args(c, a, batch, q_stride, t_stride, *opts);
     if (rc) return rc;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
     FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 9, a.models));
     HostIo io(c, io_on_device);
-    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, a.q_xy));
-    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, a.t_xy));
-    FD_HIP_TRY(c, io.in(q_counts, batch, a.q_counts));
-    FD_HIP_TRY(c, io.in(match_idx, qs, a.match_idx));
-    FD_HIP_TRY(c, io.in(pair_valid, qs, a.pair_valid));
-    FD_HIP_TRY(c, io.out(out_model, static_cast<size_t>(9) * batch, a.out_model));
+    rc = pair_inputs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid);
+    if (rc) return rc;
+    FD_HIP_TRY(c, io.out(out_model, models, a.out_model));
     FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
     FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
     FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
@@ -283,8 +259,7 @@ int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float
                     uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xy || !t_xy || !in_model || !in_inlier || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
-    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, opts->model, opts->threshold, opts->center_x,
-                         opts->center_y, opts->scale);
+    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, *opts);
     if (rc) return rc;
     if (opts->rounds < 1 || opts->rounds > FD_REFIT_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 4]");
     FD_HIP_TRY(c, hipSetDevice(c->device));
@@ -292,30 +267,20 @@ int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float
     if (rc) return rc;
     const size_t models = static_cast<size_t>(9) * batch;
     if (q_stride == 0) {  // no slots: no round is accepted
-        if (io_on_device) {
-            if (out_model != in_model)
-                FD_HIP_TRY(c, hipMemcpyAsync(out_model, in_model, sizeof(double) * models, hipMemcpyDeviceToDevice, c->stream));
-            if (out_counts) FD_HIP_TRY(c, hipMemsetAsync(out_counts, 0, sizeof(int32_t) * batch, c->stream));
-            if (out_rounds) FD_HIP_TRY(c, hipMemsetAsync(out_rounds, 0, sizeof(int32_t) * batch, c->stream));
-        } else {
-            if (out_model != in_model) std::copy(in_model, in_model + models, out_model);
-            if (out_counts) std::fill(out_counts, out_counts + batch, 0);
-            if (out_rounds) std::fill(out_rounds, out_rounds + batch, 0);
-        }
-        return FD_OK;
+        rc = copy_output(c, out_model, in_model, sizeof(double) * models, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
+        return rc;
     }
-    const size_t qs = static_cast<size_t>(batch) * q_stride, ts = static_cast<size_t>(batch) * t_stride;
+    const size_t qs = static_cast<size_t>(batch) * q_stride;
     fdk::RefitArgs g{};
-    rc = pair_args(c, g.r, batch, q_stride, t_stride, opts->model, opts->threshold, opts->center_x, opts->center_y, opts->scale);
+    rc = pair_args(c, g.r, batch, q_stride, t_stride, *opts);
     if (rc) return rc;
     g.rounds = opts->rounds;
     FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
     HostIo io(c, io_on_device);  // 7 inputs and 4 outputs: the whole staging pool
-    FD_HIP_TRY(c, io.in(q_xy, 2 * qs, g.r.q_xy));
-    FD_HIP_TRY(c, io.in(t_xy, 2 * ts, g.r.t_xy));
-    FD_HIP_TRY(c, io.in(q_counts, batch, g.r.q_counts));
-    FD_HIP_TRY(c, io.in(match_idx, qs, g.r.match_idx));
-    FD_HIP_TRY(c, io.in(pair_valid, qs, g.r.pair_valid));
+    rc = pair_inputs(c, io, g.r, q_xy, q_counts, t_xy, match_idx, pair_valid);
+    if (rc) return rc;
     FD_HIP_TRY(c, io.in(in_model, models, g.in_model));
     FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
     FD_HIP_TRY(c, io.out(out_model, models, g.r.out_model));
@@ -338,11 +303,12 @@ int fd_triangulate(fd_ctx *c, int batch, const fd_pose_opts *opts, const float *
     FD_HIP_TRY(c, hipSetDevice(c->device));
     rc = refuse_sync_under_capture(c, io_on_device);
     if (rc) return rc;
-    if (q_stride == 0) return out_counts ? zero_counts(c, out_counts, batch, io_on_device) : FD_OK;
+    if (q_stride == 0) return zero_counts(c, out_counts, batch, io_on_device);
     const size_t qs = static_cast<size_t>(batch) * q_stride;
     HostIo io(c, io_on_device);
-    rc = pose_pairs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid, in_inlier);
+    rc = pair_inputs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid);
     if (rc) return rc;
+    FD_HIP_TRY(c, io.in(in_inlier, qs, a.in_inlier));
     FD_HIP_TRY(c, io.in(in_pose, static_cast<size_t>(12) * batch, a.in_model));
     FD_HIP_TRY(c, io.out_slots(out_points, qs, 3, a.out_points));
     FD_HIP_TRY(c, io.out_slots(out_valid, qs, 1, a.out_valid));
@@ -365,19 +331,16 @@ int fd_pose_recover(fd_ctx *c, int batch, const fd_pose_opts *opts, const float 
     if (rc) return rc;
     const size_t poses = static_cast<size_t>(12) * batch;
     if (q_stride == 0) {  // no slots: no frame has a pose
-        if (io_on_device) {
-            if (out_pose) FD_HIP_TRY(c, hipMemsetAsync(out_pose, 0, sizeof(double) * poses, c->stream));
-            if (out_choice) FD_HIP_TRY(c, hipMemsetAsync(out_choice, 0xFF, sizeof(int32_t) * batch, c->stream));
-        } else {
-            if (out_pose) std::fill(out_pose, out_pose + poses, 0.0);
-            if (out_choice) std::fill(out_choice, out_choice + batch, -1);
-        }
-        return out_counts ? zero_counts(c, out_counts, batch, io_on_device) : FD_OK;
+        rc = set_output(c, out_pose, 0, sizeof(double) * poses, io_on_device);
+        if (!rc) rc = set_output(c, out_choice, 0xFF, sizeof(int32_t) * batch, io_on_device);
+        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
+        return rc;
     }
     const size_t qs = static_cast<size_t>(batch) * q_stride;
     HostIo io(c, io_on_device);  // 7 inputs and 5 outputs: the whole staging pool
-    rc = pose_pairs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid, in_inlier);
+    rc = pair_inputs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid);
     if (rc) return rc;
+    FD_HIP_TRY(c, io.in(in_inlier, qs, a.in_inlier));
     FD_HIP_TRY(c, io.in(in_model, static_cast<size_t>(9) * batch, a.in_model));
     FD_HIP_TRY(c, io.out(out_pose, poses, a.out_pose));
     FD_HIP_TRY(c, io.out(out_choice, batch, a.out_choice));

@@ -2,7 +2,8 @@
 // fd_pnp.hip: fd_pnp_ransac, fd_pnp_refit): the counter-based sampler, the null vector of an R x (R + 1)
 // system by Gaussian elimination with complete pivoting, the cyclic Jacobi on one wave, and the small
 // products and counts around them. Every floating point operation is a double one, rounded once (the build
-// passes -ffp-contract=off), in the order include/fd_hip.h states.
+// passes -ffp-contract=off), in the order include/fd_hip.h states. This file is the maths; the skeleton of an
+// estimator around it (compaction, score and vote, finish walk, refit frame, slice tree) is fd_estimate.h.
 #pragma once
 
 #include "fd_hip.h"

@@ -38,6 +38,28 @@ def conditioning(image_size=None):
     return ((cols - 1) / 2, (rows - 1) / 2), 2.0 / (rows + cols)
 
 
+def _slots(on_dev, b, s, ts, first, matches, valid, counts):
+    """The slot arguments every wrapper shares, checked (`first`: the array slot i pairs with): matches, valid, counts."""
+    if matches is None and ts < s:
+        raise ValueError(f"without matches slot i pairs with slot i: t_xy needs at least as many slots as {first}")
+    return (slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev),
+            slot_arg(counts, "int32", (b,), on_dev))
+
+
+def _pairs(q_xy, t_xy, others, side_error, matches, valid, counts, ctx):
+    """What the wrappers on image pairs share: the side of the call (q_xy's; t_xy and `others` must be on it), the
+    context, the checked positions and their sizes, and the slot arguments."""
+    on_dev = _is_torch_device_tensor(q_xy)
+    if any(_is_torch_device_tensor(x) != on_dev for x in (t_xy, *others)):
+        raise ValueError(side_error)
+    ctx = _resolve_ctx(ctx, q_xy, t_xy)
+    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
+    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
+    if int(pt.shape[0]) != b:
+        raise ValueError("q_xy and t_xy must have the same batch")
+    return (ctx, on_dev, pq, pt, b, s, ts, *_slots(on_dev, b, s, ts, "q_xy", matches, valid, counts))
+
+
 def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: str = "fundamental", hypotheses: int = 256,
                     seed: int = 0, threshold: float = 1.0, image_size=None, out=None,
                     ctx: Context | None = None) -> GeometryResult:
@@ -61,19 +83,8 @@ def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: st
     """
     if model not in MODELS:
         raise ValueError(f"model must be one of {sorted(MODELS)}")
-    on_dev = _is_torch_device_tensor(q_xy)
-    if _is_torch_device_tensor(t_xy) != on_dev:
-        raise ValueError("t_xy must be on the side (host / device) of q_xy")
-    ctx = _resolve_ctx(ctx, q_xy, t_xy)
-
-    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
-    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
-    if int(pt.shape[0]) != b:
-        raise ValueError("q_xy and t_xy must have the same batch")
-    if matches is None and ts < s:
-        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
-    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
-    cn = slot_arg(counts, "int32", (b,), on_dev)
+    ctx, on_dev, pq, pt, b, s, ts, mi, v, cn = _pairs(
+        q_xy, t_xy, (), "t_xy must be on the side (host / device) of q_xy", matches, valid, counts, ctx)
     om, oi, oc, ob = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
                              on_dev, pq.device if on_dev else None)
     (cx, cy), scale = conditioning(image_size)
@@ -109,20 +120,9 @@ def refit_geometry(q_xy, t_xy, result: GeometryResult, matches=None, valid=None,
     """
     if model not in MODELS:
         raise ValueError(f"model must be one of {sorted(MODELS)}")
-    on_dev = _is_torch_device_tensor(q_xy)
-    if _is_torch_device_tensor(t_xy) != on_dev or _is_torch_device_tensor(result.model) != on_dev or \
-            _is_torch_device_tensor(result.inliers) != on_dev:
-        raise ValueError("t_xy and result must be on the side (host / device) of q_xy")
-    ctx = _resolve_ctx(ctx, q_xy, t_xy)
-
-    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
-    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
-    if int(pt.shape[0]) != b:
-        raise ValueError("q_xy and t_xy must have the same batch")
-    if matches is None and ts < s:
-        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
-    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
-    cn = slot_arg(counts, "int32", (b,), on_dev)
+    ctx, on_dev, pq, pt, b, s, ts, mi, v, cn = _pairs(
+        q_xy, t_xy, (result.model, result.inliers), "t_xy and result must be on the side (host / device) of q_xy",
+        matches, valid, counts, ctx)
     im, ii = slot_arg(result.model, "float64", (b, 9), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
     om, oi, oc, orr = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
                               on_dev, pq.device if on_dev else None)
@@ -172,26 +172,14 @@ def intrinsics(K, name="K"):
 
 def _pose_call(q_xy, t_xy, given, given_name, given_width, K, K_t, matches, valid, counts, inliers, max_depth, min_parallax, ctx):
     """What recover_pose and triangulate share: the checked arguments of the two entry points."""
-    on_dev = _is_torch_device_tensor(q_xy)
-    sides = [_is_torch_device_tensor(t_xy), _is_torch_device_tensor(given)]
-    if inliers is not None:
-        sides.append(_is_torch_device_tensor(inliers))
-    if any(side != on_dev for side in sides):
-        raise ValueError(f"t_xy, {given_name} and the inliers must be on the side (host / device) of q_xy")
-    ctx = _resolve_ctx(ctx, q_xy, t_xy)
-    pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
-    b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
-    if int(pt.shape[0]) != b:
-        raise ValueError("q_xy and t_xy must have the same batch")
-    if matches is None and ts < s:
-        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as q_xy")
+    ctx, on_dev, pq, pt, b, s, ts, mi, v, cn = _pairs(
+        q_xy, t_xy, (given,) if inliers is None else (given, inliers),
+        f"t_xy, {given_name} and the inliers must be on the side (host / device) of q_xy", matches, valid, counts, ctx)
     if not (max_depth > 0) or not 0.0 <= min_parallax <= 1.0 or math.isnan(min_parallax):
         raise ValueError("max_depth must be > 0 and min_parallax in [0, 1]")
     cam_q = intrinsics(K)
     cam_t = cam_q if K_t is None else intrinsics(K_t, "K_t")
     opts = fd_pose_opts(*cam_q, *cam_t, float(max_depth), float(min_parallax))
-    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
-    cn = slot_arg(counts, "int32", (b,), on_dev)
     gm, ii = slot_arg(given, "float64", (b, given_width), on_dev), slot_arg(inliers, "uint8", (b, s), on_dev)
     return ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii
 
@@ -290,10 +278,8 @@ def _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, extra, ctx):
         raise ValueError("points must be float32 [B, S, 3] (or [S, 3] for batch 1) with t_xy's batch")
     s = int(shape[1])
     pp = slot_arg(points, "float32", (b, s, 3), on_dev)
-    if matches is None and ts < s:
-        raise ValueError("without matches slot i pairs with slot i: t_xy needs at least as many slots as points")
-    mi, v = slot_arg(matches, "int32", (b, s), on_dev), slot_arg(valid, "uint8", (b, s), on_dev)
-    pv, cn = slot_arg(point_valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev)
+    mi, v, cn = _slots(on_dev, b, s, ts, "points", matches, valid, counts)
+    pv = slot_arg(point_valid, "uint8", (b, s), on_dev)
     return ctx, on_dev, pp, pv, pt, b, s, ts, intrinsics(K), mi, v, cn
 
 
