@@ -19,7 +19,7 @@ EXPORTS = (
     "fd_ctx_get_stream",
     "fd_ctx_synchronize", "fd_ctx_reserve", "fd_ctx_stage", "fd_ctx_set_tie_order", "fd_ctx_frame_status", "fd_points_detect", "fd_points_candidates", "fd_points_response",
     "fd_points_response_append", "fd_points_select",
-    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_brief_match_model", "fd_nn_match_model", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_triangulate", "fd_pose_recover", "fd_pnp_ransac", "fd_pnp_refit", "fd_bundle_adjust", "fd_frames_warp", "fd_frames_equalize", "fd_blur_taps", "fd_frames_blur", "fd_pyr_build_gauss", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
+    "fd_lsd_map", "fd_lsd_map_pitched", "fd_lsd_lines", "fd_lsd_lines_state", "fd_brief_compute", "fd_brief_match", "fd_nn_match", "fd_brief_match_guided", "fd_nn_match_guided", "fd_brief_match_model", "fd_nn_match_model", "fd_pyr_layout", "fd_pyr_build", "fd_flow_lk", "fd_points_refine", "fd_ransac", "fd_ransac_refit", "fd_triangulate", "fd_pose_recover", "fd_pnp_ransac", "fd_pnp_refit", "fd_align_ransac", "fd_align_refit", "fd_align_apply", "fd_bundle_adjust", "fd_frames_warp", "fd_frames_equalize", "fd_blur_taps", "fd_frames_blur", "fd_pyr_build_gauss", "fd_lines_describe", "fd_nn_select", "fd_nn_select_list", "fd_nn_descriptors",
     "fd_nn_bias_relu", "fd_nn_conv3x3_c1", "fd_nn_conv3x3_c64",
     "fd_nn_heat_softmax", "fd_nn_desc_normalize",
     "fd_build_info", "fd_abi_version", "fd_png_info", "fd_png_decode", "fd_png_frames",
@@ -111,6 +111,15 @@ class fd_pnp_opts(ctypes.Structure):
     _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("rounds", ctypes.c_int32),
                 ("threshold", ctypes.c_float), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double),
                 ("cy", ctypes.c_double), ("center", ctypes.c_double * 3), ("scale", ctypes.c_double)]
+
+
+FD_ALIGN_SIMILARITY, FD_ALIGN_RIGID = 0, 1
+FD_ALIGN_MAX_ROUNDS = 8
+
+
+class fd_align_opts(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("rounds", ctypes.c_int32),
+                ("threshold", ctypes.c_float)]
 
 
 FD_BA_MAX_CAMS, FD_BA_MAX_ROUNDS = 8, 16
@@ -209,6 +218,9 @@ def load() -> ctypes.CDLL:
         "fd_pose_recover": (i32, [P, i32, ctypes.POINTER(fd_pose_opts), P, P, i32, P, i32, P, P, P, P, P, P, P, P, P, i32]),
         "fd_pnp_ransac": (i32, [P, i32, ctypes.POINTER(fd_pnp_opts), P, P, P, i32, P, i32, P, P, P, P, P, P, i32]),
         "fd_pnp_refit": (i32, [P, i32, ctypes.POINTER(fd_pnp_opts), P, P, P, i32, P, i32, P, P, P, P, P, P, P, P, i32]),
+        "fd_align_ransac": (i32, [P, i32, ctypes.POINTER(fd_align_opts), P, P, P, i32, P, P, i32, P, P, P, P, P, P, i32]),
+        "fd_align_refit": (i32, [P, i32, ctypes.POINTER(fd_align_opts), P, P, P, i32, P, P, i32, P, P, P, P, P, P, P, P, i32]),
+        "fd_align_apply": (i32, [P, i32, P, P, P, P, i32, P, i32]),
         "fd_bundle_adjust": (i32, [P, i32, i32, ctypes.POINTER(fd_ba_opts), P, P, P, P, P, i32, P, P, i32, P, P, P, P, P, P, i32]),
         "fd_frames_warp": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_warp_opts), P, i32, i32, i32, P, P, i32]),
         "fd_frames_equalize": (i32, [P, P, i32, i32, i32, i32, ctypes.POINTER(fd_equalize_opts), P, i32]),

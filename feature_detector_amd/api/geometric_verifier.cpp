@@ -1,7 +1,7 @@
 // GeometricVerifier over libfdhip.so (fd_ransac): an MI355X extension, the reference has no such stage.
 // One host-pointer call per Verify: the positions go up, three kernels run, the mask and the model come back.
 // Refit, RecoverPose and Triangulate are one host-pointer call each as well (fd_ransac_refit, fd_pose_recover,
-// fd_triangulate).
+// fd_triangulate), and so are SolvePnP, RefinePnP, BundleAdjust, AlignPoints, RefineAlignment and TransformPoints.
 #include "feature_detector/geometric_verifier.h"
 
 #include <algorithm>
@@ -294,6 +294,100 @@ bool GeometricVerifier::BundleAdjust(std::vector<std::array<double, 12>> &poses,
     for (size_t i = 0; i < n; ++i) std::copy(out_points.begin() + 3 * i, out_points.begin() + 3 * (i + 1), points[i].begin());
     if (cost) *cost = {out_cost[0], out_cost[1]};
     if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
+namespace {
+
+// The size checks AlignPoints and RefineAlignment share; nullptr when the arguments fit.
+const char *AlignSizes(size_t n, size_t targets, const std::vector<uint8_t> *source_valid, const std::vector<uint8_t> *target_valid,
+                       const std::vector<int32_t> *target_index, const std::vector<uint8_t> *valid) {
+    if (n == 0) return "no source points";
+    if (source_valid && source_valid->size() != n) return "one source_valid flag per source point is needed";
+    if (target_valid && target_valid->size() != targets) return "one target_valid flag per target point is needed";
+    if (target_index && target_index->size() != n) return "one target index per source point is needed";
+    if (valid && valid->size() != n) return "one valid flag per source point is needed";
+    if (!target_index && targets < n) return "without target_index every source point needs its target point";
+    return nullptr;
+}
+
+// The target points, or one zero point where there are none (an index may still be given: no entry is in range).
+const float *TargetData(const std::vector<std::array<float, 3>> &target) {
+    static const float none[3] = {0.0f, 0.0f, 0.0f};
+    return target.empty() ? none : target[0].data();
+}
+
+}  // namespace
+
+bool GeometricVerifier::AlignPoints(const std::vector<std::array<float, 3>> &source, const std::vector<std::array<float, 3>> &target,
+                                    std::array<double, 13> &model, std::vector<uint8_t> &inlier,
+                                    const std::vector<uint8_t> *source_valid, const std::vector<uint8_t> *target_valid,
+                                    const std::vector<int32_t> *target_index, const std::vector<uint8_t> *valid,
+                                    int32_t *best_hypothesis) {
+    const size_t n = source.size();
+    model.fill(0.0);
+    inlier.assign(n, 0);
+    if (best_hypothesis) *best_hypothesis = -1;
+    if (const char *why = AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid))
+        return context_.Fail(std::string("AlignPoints: ") + why);
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    const fd_align_opts o{align_options_.kKind, align_options_.kHypotheses, align_options_.kSeed, 1, align_options_.kThreshold};
+    int32_t best = -1;
+    const int rc = fd_align_ransac(ctx, 1, &o, source[0].data(), source_valid ? source_valid->data() : nullptr, nullptr,
+                                   static_cast<int32_t>(n), TargetData(target), target_valid ? target_valid->data() : nullptr,
+                                   static_cast<int32_t>(target.size()), target_index ? target_index->data() : nullptr,
+                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), nullptr, &best, 0);
+    if (rc != FD_OK) {
+        model.fill(0.0);
+        inlier.assign(n, 0);
+        return context_.FailCall("fd_align_ransac");
+    }
+    if (best < 0) return context_.Fail("AlignPoints: no model (fewer than 3 correspondences, or every sample degenerate)");
+    if (best_hypothesis) *best_hypothesis = best;
+    return true;
+}
+
+bool GeometricVerifier::RefineAlignment(const std::vector<std::array<float, 3>> &source,
+                                        const std::vector<std::array<float, 3>> &target, std::array<double, 13> &model,
+                                        std::vector<uint8_t> &inlier, int32_t rounds, const std::vector<uint8_t> *source_valid,
+                                        const std::vector<uint8_t> *target_valid, const std::vector<int32_t> *target_index,
+                                        const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
+    const size_t n = source.size();
+    if (accepted_rounds) *accepted_rounds = 0;
+    if (const char *why = AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid))
+        return context_.Fail(std::string("RefineAlignment: ") + why);
+    if (inlier.size() != n) return context_.Fail("RefineAlignment: one inlier flag per source point is needed");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    const fd_align_opts o{align_options_.kKind, 1, 0, rounds, align_options_.kThreshold};
+    std::vector<uint8_t> out_inlier(n);
+    double m[13];
+    int32_t accepted = 0;
+    const int rc = fd_align_refit(ctx, 1, &o, source[0].data(), source_valid ? source_valid->data() : nullptr, nullptr,
+                                  static_cast<int32_t>(n), TargetData(target), target_valid ? target_valid->data() : nullptr,
+                                  static_cast<int32_t>(target.size()), target_index ? target_index->data() : nullptr,
+                                  valid ? valid->data() : nullptr, model.data(), inlier.data(), m, out_inlier.data(), nullptr,
+                                  &accepted, 0);
+    if (rc != FD_OK) return context_.FailCall("fd_align_refit");
+    inlier.swap(out_inlier);
+    std::copy(m, m + 13, model.begin());
+    if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
+
+bool GeometricVerifier::TransformPoints(const std::array<double, 13> &model, std::vector<std::array<float, 3>> &points,
+                                        const std::vector<uint8_t> *point_valid) {
+    const size_t n = points.size();
+    if (n == 0) return context_.Fail("TransformPoints: no points");
+    if (point_valid && point_valid->size() != n) return context_.Fail("TransformPoints: one point_valid flag per point is needed");
+    fd_ctx *ctx = context_.Acquire();
+    if (!ctx) return false;
+    std::vector<std::array<float, 3>> out(points);  // the call fails as a whole: points are then left as given
+    const int rc = fd_align_apply(ctx, 1, model.data(), points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
+                                  static_cast<int32_t>(n), out[0].data(), 0);
+    if (rc != FD_OK) return context_.FailCall("fd_align_apply");
+    points.swap(out);
     return true;
 }
 

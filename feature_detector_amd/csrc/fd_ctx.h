@@ -63,7 +63,7 @@ struct fd_ctx {
     fdrt::DevBuf seg_cnt, seg, resp_map, c_resp, c_x, c_y, c_counts;
     fdrt::DevBuf l_norm, l_angle, l_valid, l_cnt, l_base, l_idx, l_counts, l_bits;
     // host-pointer calls of the keypoint stages (BRIEF, matchers, tracker, refinement, RANSAC, NN descriptors) and
-    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs), fd_pose_recover (7 and 5), fd_pnp_refit (8 and 4) and fd_bundle_adjust (7 and 6)
+    // of fd_frames_warp stage their arrays here, in call order (fdrt::HostIo); the widest calls are a model-gated match (9 inputs, 3 outputs), fd_pose_recover (7 and 5), fd_pnp_refit (8 and 4), fd_align_refit (9 and 4) and fd_bundle_adjust (7 and 6)
     static constexpr int kStaging = 13;
     fdrt::DevBuf staging[kStaging];
     // the matchers' cross-check reverse table ([batch][t_stride] best query of every train descriptor) and
@@ -75,7 +75,8 @@ struct fd_ctx {
     // fd_ransac: the frames' correspondence lists ([batch][q_stride] conditioned (x, y, u, v) doubles), every
     // slot's index in them, their lengths, the hypotheses' models ([batch][hypotheses][9] doubles) and the
     // per-frame best-hypothesis words; fd_ransac_refit: the support sets by list position ([batch][2][q_stride] bytes).
-    // fd_pnp_ransac and fd_pnp_refit use the same buffers with 5 doubles per correspondence and 12 per hypothesis
+    // fd_pnp_ransac and fd_pnp_refit use the same buffers with 5 doubles per correspondence and 12 per hypothesis,
+    // fd_align_ransac and fd_align_refit with 6 and 13
     fdrt::DevBuf g_corr, g_cidx, g_n, g_models, g_best, g_member;
     // fd_bundle_adjust: a trial's linearisation per observation ([batch][cams][p_stride][52] doubles) and per point
     // ([batch][p_stride][15] doubles), and the observations' state bytes ([batch][cams][p_stride])
@@ -240,6 +241,37 @@ int copy_output(fd_ctx *c, void *out, const void *in, size_t bytes, int io_on_de
 int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device);
 // n camera values (fx, fy, cx, cy per camera) into out: all finite, fx and fy non-zero.
 int check_camera(fd_ctx *c, const double *cam, int n, double *out);
+
+// What the estimators (fd_rt_ransac.cpp, fd_rt_align.cpp) ask of their [batch][q_stride] slots and the partners
+// among [batch][t_stride].
+inline int check_slots(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx) {
+    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
+    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
+    if (!match_idx && t_stride < q_stride)
+        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
+    return FD_OK;
+}
+
+// The slot fields of an argument block (RansacArgs, PoseArgs, PnpArgs, AlignArgs).
+template <class A>
+void slot_fields(A &a, int batch, int32_t q_stride, int32_t t_stride) {
+    a.batch = batch;
+    a.q_stride = q_stride;
+    a.t_stride = t_stride;
+}
+
+// The workspace of a compaction kernel (RansacArgs, PnpArgs, AlignArgs): the frames' lists of `doubles` per
+// correspondence, every slot's index in them, their lengths and the frames' vote words.
+template <class A>
+int list_workspace(fd_ctx *c, A &a, size_t doubles) {
+    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
+    FD_HIP_TRY(c, ensure_as(c, c->g_corr, doubles * qs, a.corr));
+    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
+    FD_HIP_TRY(c, ensure_as(c, c->g_n, a.batch, a.n));
+    FD_HIP_TRY(c, ensure_as(c, c->g_best, a.batch, a.best));
+    return FD_OK;
+}
+
 // k_flow_finish after zeroing its counts (fd_flow_lk, fd_points_refine).
 int finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin);
 

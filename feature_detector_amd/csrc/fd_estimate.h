@@ -1,13 +1,14 @@
 // The skeleton around the maths of fd_solve.h that the estimators share (fd_ransac.hip over 32-byte
-// correspondences d4, fd_pnp.hip over 40-byte ones Corr5): the compaction of a frame's slots into its ordered
+// correspondences d4, fd_pnp.hip over 40-byte ones Corr5, fd_align.hip over 48-byte ones Corr6): the compaction of a frame's slots into its ordered
 // list, the broadcast-tile score of a hypothesis, the vote for the frame's best and its decoding, the finish
 // walk, the frame of a refit (members by list position in a double buffer, reclassified every round), the slice
 // tree of the refits' sums, and M^T M beside the identity for the 3 x 3 Jacobi. A new estimator supplies its
 // correspondence type, how a slot is loaded and conditioned, and its inlier test, as functors.
 //
-// `A` is a kernel's argument block (RansacArgs, PnpArgs): the helpers read the fields both have under one name
-// (q_counts, match_idx, pair_valid, q_stride, t_stride, corr, cidx, n, best, out_inlier). No helper holds a
-// floating point operation of its own but reduce_upper and gram3_identity, whose sums keep the contract's order.
+// `A` is a kernel's argument block (RansacArgs, PnpArgs, AlignArgs): the helpers read the fields all have under one
+// name (q_counts, match_idx, pair_valid, q_stride, t_stride, corr, cidx, n, best, out_inlier). No helper holds a
+// floating point operation of its own but reduce_upper, reduce_sums and gram3_identity, whose sums keep the
+// contract's order.
 #pragma once
 
 #include "fd_solve.h"
@@ -215,6 +216,26 @@ __device__ __forceinline__ void reduce_upper(const double (&acc)[ENTRIES], doubl
         }
         __syncthreads();
     }
+}
+
+// The same tree for ENTRIES plain sums at once (ENTRIES <= 10: 20 KiB), left in out[0..ENTRIES) for every thread to
+// read. red: LDS [ENTRIES * kRansacThreads]. Ends with a barrier.
+template <int ENTRIES>
+__device__ __forceinline__ void reduce_sums(const double (&acc)[ENTRIES], double *red, double *out) {
+    const int tid = static_cast<int>(threadIdx.x);
+#pragma unroll
+    for (int j = 0; j < ENTRIES; ++j) red[j * kRansacThreads + tid] = acc[j];
+    for (int step = kRansacThreads / 2; step >= 1; step >>= 1) {
+        __syncthreads();
+        if (tid < step) {
+#pragma unroll
+            for (int j = 0; j < ENTRIES; ++j)
+                red[j * kRansacThreads + tid] = red[j * kRansacThreads + tid] + red[j * kRansacThreads + tid + step];
+        }
+    }
+    __syncthreads();
+    if (tid < ENTRIES) out[tid] = red[tid * kRansacThreads];
+    __syncthreads();
 }
 
 // G = M^T M of the 3 x 3 matrix in the first three columns of M's rows (LD doubles apart), each sum from 0.0

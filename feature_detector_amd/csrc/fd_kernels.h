@@ -525,6 +525,51 @@ struct PnpRefitArgs {
     int32_t *out_rounds;         // [batch] or null
 };
 
+// 3-D point-set alignment (fd_align.hip; fd_align_ransac and fd_align_refit of include/fd_hip.h): one block for its
+// kernels. k_align_compact fills corr, cidx, n and zeroes best; k_align_hyp fills models and raises best;
+// k_align_finish writes the outputs.
+struct AlignArgs {
+    const float *q_xyz, *t_xyz;  // [batch][q_stride][3], [batch][t_stride][3]
+    const uint8_t *q_valid;      // [batch][q_stride] or null; only a byte equal to 1 takes part
+    const uint8_t *t_valid;      // [batch][t_stride] or null; only a byte equal to 1 takes part
+    const int32_t *q_counts;     // [batch] or null (= q_stride); bits 25..31 ignored
+    const int32_t *match_idx;    // [batch][q_stride] or null (slot i pairs with slot i)
+    const uint8_t *pair_valid;   // [batch][q_stride] or null; only a byte equal to 1 takes part
+    int batch, q_stride, t_stride;
+    int kind, hypotheses;        // FD_ALIGN_*; 1..4096
+    uint32_t seed;
+    double tt;                   // (double)threshold squared
+    double *corr;                // [batch][q_stride][6] (X, Y) of the correspondences, in slot order
+    int32_t *cidx;               // [batch][q_stride] a slot's index in corr, or -1
+    int32_t *n;                  // [batch] correspondences
+    double *models;              // [batch][hypotheses][13] R, t, s
+    unsigned long long *best;    // [batch] as RansacArgs::best
+    double *out_model;           // [batch][13]
+    uint8_t *out_inlier;         // [batch][q_stride] or null
+    int32_t *out_counts, *out_best;  // [batch] or null
+};
+
+// k_align_compact runs on `r` (hypotheses, seed, models, out_best unused); k_align_refit reads r's lists and writes
+// r.out_model, r.out_inlier, r.out_counts.
+struct AlignRefitArgs {
+    AlignArgs r;
+    const double *in_model;      // [batch][13]; may be r.out_model
+    const uint8_t *in_inlier;    // [batch][q_stride]; only a byte equal to 1 is a member; may be r.out_inlier
+    uint8_t *member;             // [batch][2][q_stride] workspace: membership by list position, current and candidate
+    int rounds;                  // 1..8
+    int32_t *out_rounds;         // [batch] or null
+};
+
+// fd_align_apply: k_align_apply, one thread per point slot.
+struct AlignApplyArgs {
+    const double *model;         // [batch][13]
+    const float *xyz_in;         // [batch][stride][3]; may be xyz_out
+    const uint8_t *valid;        // [batch][stride] or null; only a byte equal to 1 is written
+    const int32_t *counts;       // [batch] or null (= stride); bits 25..31 ignored
+    int batch, stride;
+    float *xyz_out;              // [batch][stride][3]
+};
+
 // Windowed bundle adjustment (fd_ba.hip; fd_bundle_adjust of include/fd_hip.h): k_bundle_adjust, one workgroup
 // per problem. The workspace holds what a trial's linearisation leaves for its system and update passes.
 constexpr int kBaObsDoubles = 52;    // per observation: jx[7], jy[7], W[6][3], Y[6][3], bx, by
@@ -619,6 +664,12 @@ hipError_t launch_triangulate(const PoseArgs &a, hipStream_t s);
 hipError_t launch_pnp_ransac(const PnpArgs &a, hipStream_t s);
 // k_pnp_compact, then k_pnp_refit (all rounds in one launch)
 hipError_t launch_pnp_refit(const PnpRefitArgs &a, hipStream_t s);
+// k_align_compact, k_align_hyp, k_align_finish
+hipError_t launch_align_ransac(const AlignArgs &a, hipStream_t s);
+// k_align_compact, then k_align_refit (all rounds in one launch)
+hipError_t launch_align_refit(const AlignRefitArgs &a, hipStream_t s);
+// k_align_apply (stride >= 1)
+hipError_t launch_align_apply(const AlignApplyArgs &a, hipStream_t s);
 // k_bundle_adjust, every trial in one launch (p_stride >= 1)
 hipError_t launch_bundle_adjust(const BaArgs &a, hipStream_t s);
 // one pyramid level [batch][rows >> 1][cols >> 1] from the level [batch][rows][cols] below it

@@ -1,8 +1,9 @@
 // Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac), the least-squares
 // refit of its model (fd_ransac_refit), the pose of a fundamental matrix (fd_pose_recover) and triangulation
 // (fd_triangulate) over the kernels of fd_ransac.hip, and the absolute pose from 3-D points (fd_pnp_ransac,
-// fd_pnp_refit) over those of fd_pnp.hip. The six calls share their slot checks, the staging of the pair arrays,
-// the workspace of the compaction kernels and the outputs of a call without slots (fd_ctx.h).
+// fd_pnp_refit) over those of fd_pnp.hip. The six calls share the staging of the pair arrays here, and with
+// fd_rt_align.cpp their slot checks, the workspace of the compaction kernels and the outputs of a call without slots
+// (fd_ctx.h).
 #include <cmath>
 
 #include "fd_ctx.h"
@@ -10,35 +11,6 @@
 using namespace fdrt;
 
 namespace {
-
-// What every call asks of its [batch][q_stride] slots and their partners among [batch][t_stride].
-int check_slots(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx) {
-    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
-    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
-    if (!match_idx && t_stride < q_stride)
-        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    return FD_OK;
-}
-
-// The slot fields of an argument block (RansacArgs, PoseArgs, PnpArgs).
-template <class A>
-void slot_fields(A &a, int batch, int32_t q_stride, int32_t t_stride) {
-    a.batch = batch;
-    a.q_stride = q_stride;
-    a.t_stride = t_stride;
-}
-
-// The workspace of a compaction kernel (RansacArgs, PnpArgs): the frames' lists of `doubles` per correspondence,
-// every slot's index in them, their lengths and the frames' vote words.
-template <class A>
-int list_workspace(fd_ctx *c, A &a, size_t doubles) {
-    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
-    FD_HIP_TRY(c, ensure_as(c, c->g_corr, doubles * qs, a.corr));
-    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
-    FD_HIP_TRY(c, ensure_as(c, c->g_n, a.batch, a.n));
-    FD_HIP_TRY(c, ensure_as(c, c->g_best, a.batch, a.best));
-    return FD_OK;
-}
 
 // The pair arrays every call has behind its query side's own (q_xy, or p_xyz and p_valid), staged or handed on.
 template <class A>

@@ -1,5 +1,7 @@
 """RANSAC verification of matches and tracks over the C ABI (fd_ransac), the refit of its model
-(fd_ransac_refit), the relative pose of a fundamental matrix (fd_pose_recover) and triangulation (fd_triangulate).
+(fd_ransac_refit), the relative pose of a fundamental matrix (fd_pose_recover) and triangulation (fd_triangulate),
+the absolute pose from 3-D points (fd_pnp_ransac, fd_pnp_refit), bundle adjustment (fd_bundle_adjust) and the alignment
+of two 3-D point sets (fd_align_ransac, fd_align_refit, fd_align_apply).
 
 An MI355X extension (the reference has no such stage): the step after brief_match / nn_match or track_lk
 in a VIO / SLAM front end, on their [batch][stride] layouts, so detect -> describe -> match -> verify and
@@ -15,7 +17,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import fd_ba_opts, fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
+from ._lib import fd_align_opts, fd_ba_opts, fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
 from ._slots import f32, outputs, positions, ptr, slot_arg
 from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
 
@@ -432,3 +434,179 @@ def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, co
                                       ptr(ov), o, ptr(oo), ptr(opn), ptr(oi), ptr(oc), ptr(ocs), ptr(orr), 1 if on_dev else 0)
     _lib.check(ctx.ptr, rc)
     return BundleResult(oo, opn, oi, oc, ocs, orr)
+
+
+ALIGN_KINDS = {"similarity": _lib.FD_ALIGN_SIMILARITY, "rigid": _lib.FD_ALIGN_RIGID}
+MODEL_SPECS = lambda b, s: (((b, 13), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0))  # noqa: E731
+
+
+@dataclass
+class AlignResult:
+    model: object    # float64 [B, 13]: R row-major, then t, then s, Y = s R X + t; zeros: no model
+    inliers: object  # uint8 [B, S]: 1 = a correspondence within `threshold` of its mapped point, in the target's units
+    counts: object   # int32 [B]: inliers per frame
+    best: object     # int32 [B]: the winning hypothesis, -1: no model
+
+    def rotation(self, b=0):
+        """Frame b's R as a [3, 3] view."""
+        return self.model[b, :9].reshape(3, 3)
+
+    def translation(self, b=0):
+        return self.model[b, 9:12]
+
+    def scale(self, b=0):
+        return self.model[b, 12]
+
+
+@dataclass
+class AlignRefineResult(AlignResult):
+    rounds: object = None  # int32 [B]: accepted refit rounds; 0: model and inliers are the given ones
+
+
+def _xyz(x, name, b=None):
+    """The [B, S, 3] shape of a point array ([S, 3]: batch 1), checked against the batch b."""
+    shape = tuple(x.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[2] != 3 or (b is not None and shape[0] != b):
+        raise ValueError(f"{name} must be float32 [B, S, 3] (or [S, 3] for batch 1)" + ("" if b is None else " with the call's batch"))
+    return shape
+
+
+def _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind, extra, ctx):
+    """What align_points and refine_alignment share: the checked arguments of the two entry points. `extra`: further
+    arrays that must be on the side of q_xyz."""
+    if kind not in ALIGN_KINDS:
+        raise ValueError(f"kind must be one of {sorted(ALIGN_KINDS)}")
+    if isinstance(q_xyz, PointsResult):
+        q_xyz, q_valid = q_xyz.points, (q_xyz.valid if q_valid is None else q_valid)
+    if isinstance(t_xyz, PointsResult):
+        t_xyz, t_valid = t_xyz.points, (t_xyz.valid if t_valid is None else t_valid)
+    on_dev = _is_torch_device_tensor(q_xyz)
+    others = [t_xyz, *extra] + [x for x in (q_valid, t_valid) if x is not None]
+    if any(_is_torch_device_tensor(x) != on_dev for x in others):
+        raise ValueError("t_xyz, the masks and the given result must be on the side (host / device) of q_xyz")
+    ctx = _resolve_ctx(ctx, q_xyz, t_xyz)
+    qs, ts = _xyz(q_xyz, "q_xyz"), _xyz(t_xyz, "t_xyz")
+    b, s, t = int(qs[0]), int(qs[1]), int(ts[1])
+    if ts[0] != b:
+        raise ValueError("q_xyz and t_xyz must have the same batch")
+    pq, pt = f32(q_xyz, "q_xyz", on_dev).reshape(qs), f32(t_xyz, "t_xyz", on_dev).reshape(ts)
+    mi, v, cn = _slots(on_dev, b, s, t, "q_xyz", matches, valid, counts)
+    qv, tv = slot_arg(q_valid, "uint8", (b, s), on_dev), slot_arg(t_valid, "uint8", (b, t), on_dev)
+    return ctx, on_dev, pq, qv, pt, tv, b, s, t, mi, v, cn
+
+
+def align_points(q_xyz, t_xyz, matches=None, valid=None, q_valid=None, t_valid=None, counts=None, kind: str = "similarity",
+                 hypotheses: int = 256, seed: int = 0, threshold: float = 0.1, out=None, ctx: Context | None = None) -> AlignResult:
+    """fd_align_ransac: the similarity ("similarity": Y = s R X + t) or rigid ("rigid": s = 1) transform between two
+    sets of 3-D points with the most inliers among `hypotheses` 3-point samples: what joins a keyframe window to the
+    map before it, closes a loop at a drifted scale, or registers recover_pose's points against metric ones.
+
+    q_xyz: float32 [B, S, 3] (or [S, 3] for batch 1) and t_xyz: float32 [B, T, 3], or a PointsResult / PoseResult as
+    it is on either side (its valid bytes then are q_valid / t_valid). matches, valid, counts: verify_geometry's.
+    q_valid uint8 [B, S], t_valid uint8 [B, T]: a point takes part only where its byte is 1 (None: all). threshold is
+    the distance |Y - (s R X + t)| in the target's units, absolute: choose it for the target's scale. Planar point sets
+    are fine; duplicate and collinear samples are rejected.
+
+    Returns an AlignResult. Host and device inputs and out= (model float64 [B, 13], inliers uint8 [B, S], counts
+    int32 [B], best int32 [B]) behave as in verify_geometry.
+    """
+    ctx, on_dev, pq, qv, pt, tv, b, s, t, mi, v, cn = _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind,
+                                                                  (), ctx)
+    opts = fd_align_opts(ALIGN_KINDS[kind], int(hypotheses), int(seed) & 0xFFFFFFFF, 1, float(threshold))
+    om, oi, oc, ob = outputs(MODEL_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_align_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(qv), ptr(cn), s, ptr(pt), ptr(tv), t, ptr(mi),
+                                     ptr(v), ptr(om), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return AlignResult(om, oi, oc, ob)
+
+
+def refine_alignment(q_xyz, t_xyz, result: AlignResult, matches=None, valid=None, q_valid=None, t_valid=None, counts=None,
+                     kind: str = "similarity", rounds: int = 4, threshold: float = 0.1, out=None,
+                     ctx: Context | None = None) -> AlignRefineResult:
+    """fd_align_refit: the closed-form least-squares transform (Horn's quaternion method) on align_points' inliers, the
+    inliers classified again, up to `rounds` (1..8) times while their number does not fall.
+
+    q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind and threshold are align_points': pass the same ones.
+    result: what align_points returned (its model float64 [B, 13] and inliers uint8 [B, S], on the side of q_xyz). A
+    frame whose first round is rejected (fewer than 3 members, fewer inliers than before) keeps its model bit for bit
+    and has rounds 0. Collinear members leave the roll about their line arbitrary.
+
+    Returns an AlignRefineResult: model, inliers, counts as align_points', best as given, and rounds int32 [B]. Host
+    and device inputs and out= (model float64 [B, 13], inliers uint8 [B, S], counts int32 [B], rounds int32 [B])
+    behave as in verify_geometry; out= may hold result's own model and inliers tensors.
+    """
+    ctx, on_dev, pq, qv, pt, tv, b, s, t, mi, v, cn = _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind,
+                                                                  (result.model, result.inliers), ctx)
+    im, ii = slot_arg(result.model, "float64", (b, 13), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
+    opts = fd_align_opts(ALIGN_KINDS[kind], 1, 0, int(rounds), float(threshold))
+    om, oi, oc, orr = outputs(MODEL_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_align_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(qv), ptr(cn), s, ptr(pt), ptr(tv), t, ptr(mi),
+                                    ptr(v), ptr(im), ptr(ii), ptr(om), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return AlignRefineResult(om, oi, oc, result.best, orr)
+
+
+def transform_points(model, xyz, valid=None, counts=None, out=None, ctx: Context | None = None):
+    """fd_align_apply: (float32)(s R X + t) of every valid point, so that a merged point set stays on the device.
+
+    model: an AlignResult / AlignRefineResult, or float64 [B, 13] (or [13] for batch 1). xyz: float32 [B, S, 3] (or
+    [S, 3]), or a PointsResult / PoseResult as it is (its valid bytes then are `valid`). valid uint8 [B, S] (None: all)
+    and counts int32 [B] (None: S each): a slot is transformed where its byte is 1 and it lies below its frame's count.
+
+    Returns float32 [B, S, 3] on xyz's side: a copy of xyz with the transformed slots replaced. Device path only: out =
+    a preallocated contiguous float32 [B, S, 3] tensor, of which the transformed slots alone are written; out may be
+    xyz itself (in place; kernels only, graph-capturable).
+    """
+    if isinstance(xyz, PointsResult):
+        xyz, valid = xyz.points, (xyz.valid if valid is None else valid)
+    model = getattr(model, "model", model)
+    on_dev = _is_torch_device_tensor(xyz)
+    if _is_torch_device_tensor(model) != on_dev or any(_is_torch_device_tensor(x) != on_dev for x in (valid, counts) if x is not None):
+        raise ValueError("model, valid and counts must be on the side (host / device) of xyz")
+    ctx = _resolve_ctx(ctx, xyz, xyz)
+    shape = _xyz(xyz, "xyz")
+    b, s = int(shape[0]), int(shape[1])
+    px = f32(xyz, "xyz", on_dev).reshape(shape)
+    pm = slot_arg(model, "float64", (b, 13), on_dev)
+    pv, cn = slot_arg(valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev)
+    if out is None:
+        res = px.clone() if on_dev else px.copy()
+    else:
+        (res,) = outputs(((shape, "float32", 0),), (out,), on_dev)
+    _bind_stream(ctx, on_dev)
+    rc = _lib.load().fd_align_apply(ctx.ptr, b, ptr(pm), ptr(px), ptr(pv), ptr(cn), s, ptr(res), 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return res
+
+
+def transform_poses(model, poses):
+    """The window's cameras after its points moved by a model (host arithmetic, numpy float64): a camera X_c = R_c X + t_c
+    of the source frame becomes R_c' = R_c R^T, t_c' = s t_c - R_c' t in the target frame. The camera's depth unit scales
+    by s with it: a point X has the camera coordinates s X_c under the new pose, so its image position is unchanged.
+
+    model: float64 [13] or [B, 13] (an AlignResult passes; device tensors are copied to the host). poses: float64
+    [B, 12] or [B, C, 12] (or [12]), R row-major then t, as solve_pnp / recover_pose / bundle_adjust return them.
+    Returns the new poses as a numpy float64 array of poses' shape.
+    """
+    host = lambda x: np.asarray(x.cpu() if hasattr(x, "cpu") else x, np.float64)  # noqa: E731
+    model, poses = host(getattr(model, "model", model)), host(getattr(poses, "pose", poses))
+    shape = poses.shape
+    if shape[-1] != 12 or model.shape[-1] != 13:
+        raise ValueError("poses must be [..., 12] and model [13] or [B, 13]")
+    model = model.reshape(-1, 13)
+    p = poses.reshape((1, 1, 12) if poses.ndim == 1 else (shape[0], -1, 12))
+    if model.shape[0] not in (1, p.shape[0]):
+        raise ValueError("model must be [13] or have the poses' batch")
+    out = np.empty_like(p)
+    for b in range(p.shape[0]):
+        m = model[b if model.shape[0] > 1 else 0]
+        R, t, s = m[:9].reshape(3, 3), m[9:12], m[12]
+        for c in range(p.shape[1]):
+            Rn = p[b, c, :9].reshape(3, 3) @ R.T
+            out[b, c, :9] = Rn.reshape(9)
+            out[b, c, 9:] = s * p[b, c, 9:] - Rn @ t
+    return out.reshape(shape)

@@ -1046,6 +1046,131 @@ int fd_pnp_refit(fd_ctx *ctx, int batch, const fd_pnp_opts *opts,
                  double *out_pose, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
                  int io_on_device);
 
+/* ---- 3-D point-set alignment: similarity / rigid RANSAC, refit and apply (MI355X extension) ------------- */
+#define FD_ALIGN_SIMILARITY 0 /* Y = s R X + t, 7 degrees of freedom */
+#define FD_ALIGN_RIGID      1 /* s is exactly 1.0 everywhere, 6 degrees of freedom */
+#define FD_ALIGN_MAX_ROUNDS 8
+/* Jacobi sweeps of fd_align_refit. Found on the CPU with the restatement (tests/align_ref.py) by FD_REFIT_SWEEPS's
+ * rule: over every scene of tests/test_align_host.py and tests/test_gpu_align.py the diagonal of Horn's 4 x 4 matrix
+ * and the quaternion q change no bit after 5 sweeps; the rule adds 2 (tests/test_align_host.py::test_sweep_count_rule). */
+#define FD_ALIGN_SWEEPS 7
+
+typedef struct fd_align_opts {
+    int32_t kind;       /* FD_ALIGN_SIMILARITY or FD_ALIGN_RIGID */
+    int32_t hypotheses; /* 1..4096, all evaluated (fd_align_ransac; fd_align_refit ignores it) */
+    uint32_t seed;      /* fd_align_ransac */
+    int32_t rounds;     /* 1..8 (fd_align_refit; fd_align_ransac ignores it) */
+    float threshold;    /* finite, > 0: the distance |Y - (s R X + t)| in the target's units */
+} fd_align_opts;
+
+/*
+ * fd_align_ransac, fd_align_refit and fd_align_apply -- the similarity (or rigid) transform Y = s R X + t between two
+ * sets of 3-D points with known correspondences, and its application: what joins a new keyframe window to the map
+ * before it, closes a loop whose landmarks were triangulated twice at drifted scales, or registers fd_pose_recover's
+ * points (in units of the first baseline) against metric ones. Definite sequences like fd_pnp_ransac's, with its
+ * conventions: all floating point double, every operation rounded once, no contraction, f64 division and square root
+ * correctly rounded; only + - * / sqrt. An expression written a + b + c is summed left to right; "from 0.0" means the
+ * sum starts at 0.0; a.b of two 3-vectors is a0*b0 + a1*b1 + a2*b2; a x b has the components a1*b2 - a2*b1,
+ * a2*b0 - a0*b2, a0*b1 - a1*b0, both products rounded first. tests/align_ref.py restates the three calls.
+ *
+ * q_xyz float [batch][q_stride][3] and t_xyz float [batch][t_stride][3]; q_valid uint8 [batch][q_stride] and t_valid
+ * uint8 [batch][t_stride] (each NULL: all): fd_triangulate's / fd_pose_recover's out_points and out_valid as they are.
+ * q_counts, match_idx, pair_valid: fd_pnp_ransac's.
+ * Correspondences of frame b: slot i is one when i < q_counts[b], q_valid and pair_valid are each NULL or exactly 1
+ * at i, j = match_idx ? match_idx[i] : i satisfies 0 <= j < t_stride, t_valid is NULL or exactly 1 at j, and the six
+ * coordinates are finite. They are taken in ascending i and numbered 0..n-1, with X = (double)q_xyz[i] and
+ * Y = (double)t_xyz[j] (six doubles; no conditioning: every formula below works on differences or centred values).
+ *
+ * Model: 13 doubles, R row-major, then t, then s. FD_ALIGN_RIGID: s is exactly 1.0 wherever a model is computed.
+ * Inlier test of a model on a correspondence, with th = (double)threshold:
+ *   z_i = s * (R[i][0]*X0 + R[i][1]*X1 + R[i][2]*X2) + t[i];  e_i = Y_i - z_i
+ *   inlier iff e0*e0 + e1*e1 + e2*e2 <= th*th  (a NaN fails).
+ *
+ * fd_align_ransac: fixed-count RANSAC over 3-point samples, m = 3 picks a, b, c by fd_ransac's sampler unchanged.
+ * 1. u = Xb - Xa, v = Xc - Xa, U = Yb - Ya, V = Yc - Ya.
+ * 2. Frame of (u, v): uu = u.u; e1 = u / sqrt(uu) (each component divided by the one square root); d = v.e1;
+ *    w = v - d*e1; ww = w.w; e2 = w / sqrt(ww); e3 = e1 x e2. The frame is valid iff uu > 0 and ww > 1e-12 * (v.v):
+ *    duplicate and collinear picks fail. The same of (U, V) gives f1, f2, f3.
+ * 3. R[i][j] = f1[i]*e1[j] + f2[i]*e2[j] + f3[i]*e3[j].
+ * 4. FD_ALIGN_SIMILARITY: s = sqrt((U.U + V.V + G.G) / (u.u + v.v + g.g)) with G = V - U and g = v - u (the ratio of
+ *    the triangles' summed squared side lengths). FD_ALIGN_RIGID: s = 1.0.
+ * 5. Xm = Xa + (u + v) / 3.0, Ym = Ya + (U + V) / 3.0, per component.
+ * 6. t[i] = Ym[i] - s * (R[i][0]*Xm0 + R[i][1]*Xm1 + R[i][2]*Xm2).
+ * 7. The hypothesis is invalid unless both frames are valid, all 13 values are finite and s > 0.
+ * Score: the inlier test over the frame's correspondences. The best hypothesis is the valid one with the most
+ * inliers, the lowest index among equals. n < 3: no hypothesis is valid.
+ * Outputs. out_model double [batch][13]: the winner's; thirteen zeros without one. out_inlier uint8
+ * [batch][q_stride] (NULL to skip): 1 for a correspondence the winner classifies as an inlier, 0 for every other slot
+ * below q_counts[b]; slots >= q_counts[b] are not written. out_counts [batch] (NULL to skip): the ones. out_best
+ * [batch] (NULL to skip): the winning hypothesis, or -1. q_stride 0: nothing but out_counts = 0, out_best = -1 and a
+ * zero model.
+ *
+ * fd_align_refit: closed-form least squares (Horn's quaternion method) on the members, the list classified again.
+ * in_model double [batch][13] and in_inlier uint8 [batch][q_stride]: fd_align_ransac's out_model and out_inlier.
+ * Start: S_0 = the correspondences whose in_inlier byte is exactly 1; c_0 = the number of correspondences of the
+ * whole list that in_model classifies as inliers. Round r = 1..rounds, on S_(r-1) with m members:
+ * 1. The six sums of X and Y over the members, in fd_ransac_refit's order: 256 partials from 0.0 over the list
+ *    positions L, L + 256, ... ascending (members only), then the tree P[L] = P[L] + P[L + step], step = 128..1.
+ *    Xb = sum / (double)m, Yb likewise. The round is invalid for m < 3.
+ * 2. A second pass in the same order, with xc = X - Xb and yc = Y - Yb: the nine A[i][j] = A[i][j] + xc[i]*yc[j]
+ *    (i the source row, j the target column, row-major), then Sx = Sx + (xc0*xc0 + xc1*xc1 + xc2*xc2).
+ * 3. With Sxx = A[0][0], Sxy = A[0][1], ..., Szz = A[2][2], the symmetric matrix
+ *      N = [[ Sxx+Syy+Szz, Syz-Szy,      Szx-Sxz,      Sxy-Syx     ],
+ *           [ Syz-Szy,     Sxx-Syy-Szz,  Sxy+Syx,      Szx+Sxz     ],
+ *           [ Szx-Sxz,     Sxy+Syx,     -Sxx+Syy-Szz,  Syz+Szy     ],
+ *           [ Sxy-Syx,     Szx+Sxz,      Syz+Szy,     -Sxx-Syy+Szz ]]
+ *    (a leading -Sxx is the negation, then the two further terms left to right); fd_ransac_refit's cyclic Jacobi on N
+ *    (n = 4, V = identity), FD_ALIGN_SWEEPS sweeps; k = the index of the largest diagonal entry (strict > from entry
+ *    0); (a, b, c, d) = V[:, k]; qq = a*a + b*b + c*c + d*d;
+ *      R00 = (a*a+b*b-c*c-d*d)/qq   R01 = (2.0*(b*c-a*d))/qq     R02 = (2.0*(b*d+a*c))/qq
+ *      R10 = (2.0*(b*c+a*d))/qq     R11 = (a*a-b*b+c*c-d*d)/qq   R12 = (2.0*(c*d-a*b))/qq
+ *      R20 = (2.0*(b*d-a*c))/qq     R21 = (2.0*(c*d+a*b))/qq     R22 = (a*a-b*b-c*c+d*d)/qq
+ *    always a proper rotation, for planar member sets too (collinear members leave the roll about their line free).
+ * 4. FD_ALIGN_SIMILARITY: s = (the sum over i, j row-major from 0.0 of R[i][j]*A[j][i]) / Sx. FD_ALIGN_RIGID:
+ *    s = 1.0. The round is invalid unless Sx > 0, the 13 values are finite and s > 0.
+ * 5. t[i] = Yb[i] - s * (R[i][0]*Xb0 + R[i][1]*Xb1 + R[i][2]*Xb2).
+ * 6. Classify every correspondence of the list: S_r, c_r = |S_r|. Guard: the round is accepted iff it is valid and
+ *    c_r >= c_(r-1); otherwise the loop stops and the state of the last accepted round stands.
+ * Outputs. out_model: the model of the last accepted round; with none the thirteen doubles of in_model, bit for bit.
+ * out_inlier (NULL to skip): 1 for the members of the last accepted round's S (of S_0 with none), 0 for every other
+ * slot below q_counts[b]; slots >= q_counts[b] are not written. out_counts (NULL to skip): the ones of out_inlier.
+ * out_rounds int32 [batch] (NULL to skip): the accepted rounds, 0..rounds. out_model may be in_model and out_inlier
+ * may be in_inlier. q_stride 0: out_model = in_model, out_counts = 0, out_rounds = 0.
+ *
+ * fd_align_apply: a model applied to points, so that the merged set stays on the device. model double [batch][13];
+ * xyz_in float [batch][stride][3]; valid uint8 [batch][stride] (NULL: all); counts int32 [batch] (NULL: stride; bits
+ * 25..31 ignored, at most stride). For every slot i < counts[b] whose valid byte is NULL or exactly 1:
+ * xyz_out[i] = (float)z, z the inlier test's expression with X = (double)xyz_in[i], each component rounded once to
+ * float. Every other slot is not written. xyz_out may be xyz_in. stride 0: nothing is written.
+ *
+ * Device pointers when io_on_device: asynchronous on the context's stream (three kernels; fd_align_refit: two;
+ * fd_align_apply: one, no workspace), graph-capturable once a first call of the shape has sized the workspace. Host
+ * pointers otherwise: staged through context buffers, complete on return.
+ * FD_ERR_INVALID: ctx, opts, q_xyz, t_xyz or out_model NULL (fd_align_refit: in_model or in_inlier too); batch < 1; a
+ * negative stride; match_idx NULL with t_stride < q_stride; threshold not finite or not > 0; kind neither constant;
+ * fd_align_ransac: hypotheses outside 1..4096; fd_align_refit: rounds outside 1..8. fd_align_apply: ctx, model,
+ * xyz_in or xyz_out NULL; batch < 1; a negative stride.
+ * The threshold is absolute, in the target's units: a threshold that grows with depth is not in this call.
+ */
+int fd_align_ransac(fd_ctx *ctx, int batch, const fd_align_opts *opts,
+                    const float *q_xyz, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                    const float *t_xyz, const uint8_t *t_valid, int32_t t_stride,
+                    const int32_t *match_idx, const uint8_t *pair_valid,
+                    double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best,
+                    int io_on_device);
+
+int fd_align_refit(fd_ctx *ctx, int batch, const fd_align_opts *opts,
+                   const float *q_xyz, const uint8_t *q_valid, const int32_t *q_counts, int32_t q_stride,
+                   const float *t_xyz, const uint8_t *t_valid, int32_t t_stride,
+                   const int32_t *match_idx, const uint8_t *pair_valid,
+                   const double *in_model, const uint8_t *in_inlier,
+                   double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds,
+                   int io_on_device);
+
+int fd_align_apply(fd_ctx *ctx, int batch, const double *model,
+                   const float *xyz_in, const uint8_t *valid, const int32_t *counts, int32_t stride,
+                   float *xyz_out, int io_on_device);
+
 /* ---- Windowed bundle adjustment (MI355X extension) ------------------------------------------------------ */
 #define FD_BA_MAX_CAMS 8
 #define FD_BA_MAX_ROUNDS 16

@@ -7,6 +7,7 @@
 // all evaluated, one solve in double each), are those of fd_ransac (include/fd_hip.h): the model is the
 // best minimal-sample model, not a refit. Refit refits it (fd_ransac_refit); RecoverPose and Triangulate turn a
 // fundamental matrix into the relative camera pose and the inliers' 3-D points (fd_pose_recover, fd_triangulate).
+// AlignPoints, RefineAlignment and TransformPoints put two such point sets into one frame (fd_align_*).
 #ifndef FEATURE_DETECTOR_GEOMETRIC_VERIFIER_H_
 #define FEATURE_DETECTOR_GEOMETRIC_VERIFIER_H_
 
@@ -180,6 +181,50 @@ public:
     BundleOptions &bundle_options() { return bundle_options_; }
     const BundleOptions &bundle_options() const { return bundle_options_; }
 
+    // Options of AlignPoints and RefineAlignment.
+    enum AlignKind : int32_t { kSimilarity = 0, kRigid = 1 };  // Y = s R X + t; rigid: s = 1
+    struct AlignOptions {
+        AlignKind kKind = kSimilarity;
+        int32_t kHypotheses = 256;   // 1..4096, all evaluated
+        uint32_t kSeed = 0;
+        float kThreshold = 0.1f;     // the distance |Y - (s R X + t)| in the target's units, absolute
+    };
+
+    // The similarity (or rigid) transform between two sets of 3-D points (fd_align_ransac of include/fd_hip.h): of
+    // kHypotheses 3-point samples the one with the most inliers. source[i] <-> target[target_index[i]] (or target[i]
+    // without target_index); RecoverPose's / Triangulate's points and point_valid pass as they are on either side
+    // (source_valid, target_valid and valid optional: only the entries flagged exactly 1 take part). model: R
+    // row-major, then t, then s, target = s R source + t. inlier[i]: 1 if source point i maps within kThreshold of
+    // its target. Planar point sets are fine; duplicate and collinear samples are rejected.
+    // False, with a zero model and inlier all 0, when there is no model (fewer than 3 correspondences, every sample
+    // degenerate), for no source points, a mask or index of the wrong size, fewer target than source points without
+    // target_index, an option out of range, or a libfdhip failure.
+    bool AlignPoints(const std::vector<std::array<float, 3>> &source, const std::vector<std::array<float, 3>> &target,
+                     std::array<double, 13> &model, std::vector<uint8_t> &inlier, const std::vector<uint8_t> *source_valid = nullptr,
+                     const std::vector<uint8_t> *target_valid = nullptr, const std::vector<int32_t> *target_index = nullptr,
+                     const std::vector<uint8_t> *valid = nullptr, int32_t *best_hypothesis = nullptr);
+
+    // Refits AlignPoints' model on its inliers in closed form (fd_align_refit): up to `rounds` (1..8) times, the
+    // inliers classified again after each, while their number does not fall. The other arguments are what AlignPoints
+    // took; model and inlier are what it returned and receive the result. accepted_rounds (optional): the rounds taken;
+    // with 0 model keeps its bits and inlier its members. Collinear inliers leave the roll about their line arbitrary.
+    // False for the size and range errors of AlignPoints, rounds out of range, or a libfdhip failure; model and inlier
+    // are then left as given.
+    bool RefineAlignment(const std::vector<std::array<float, 3>> &source, const std::vector<std::array<float, 3>> &target,
+                         std::array<double, 13> &model, std::vector<uint8_t> &inlier, int32_t rounds = 4,
+                         const std::vector<uint8_t> *source_valid = nullptr, const std::vector<uint8_t> *target_valid = nullptr,
+                         const std::vector<int32_t> *target_index = nullptr, const std::vector<uint8_t> *valid = nullptr,
+                         int32_t *accepted_rounds = nullptr);
+
+    // points[i] = (float)(s R points[i] + t) for every point (fd_align_apply), or with point_valid for those flagged
+    // exactly 1 (the others keep their bits). False for no points, a point_valid of the wrong size, or a libfdhip
+    // failure; points are then left as given.
+    bool TransformPoints(const std::array<double, 13> &model, std::vector<std::array<float, 3>> &points,
+                         const std::vector<uint8_t> *point_valid = nullptr);
+
+    AlignOptions &align_options() { return align_options_; }
+    const AlignOptions &align_options() const { return align_options_; }
+
     // Reference for member variables.
     Options &options() { return options_; }
     const Options &options() const { return options_; }
@@ -193,6 +238,7 @@ private:
     PoseOptions pose_options_;
     PnpOptions pnp_options_;
     BundleOptions bundle_options_;
+    AlignOptions align_options_;
     DeviceContext context_;
 };
 

@@ -21,7 +21,8 @@ fixed number of times, on seeded uniform-noise frames generated on the GPU.
                      fundamental matrix and then the homography, 10 calls (--refit: fd_ransac_refit, rounds 2, after each;
                      --pose: fd_pose_recover and fd_triangulate on the fundamental matrix; --pnp: with --pose, fd_pnp_ransac
                      (256 hypotheses, threshold 2 px) and fd_pnp_refit (rounds 4) of frame i + 1 against the points
-                     fd_pose_recover left; --ba: with --pnp, fd_bundle_adjust (rounds 8, threshold 2 px) of every pair as a
+                     fd_pose_recover left; --align: with --pose, fd_align_ransac (256 hypotheses), fd_align_refit (rounds 4)
+                     and fd_align_apply of fd_pose_recover's points against fd_triangulate's of the same slots; --ba: with --pnp, fd_bundle_adjust (rounds 8, threshold 2 px) of every pair as a
                      two-camera window: the first frame held at the identity, the second at fd_pnp_refit's pose, the
                      matched positions gathered into slot order, the points fd_pose_recover's)
   --shape warp       fd_frames_warp with a mask, on device tensors: a rotation by 3 degrees with scale 1.02 and a mild
@@ -74,6 +75,8 @@ p.add_argument("--fb", action="store_true", help="fastflow: track with the forwa
 p.add_argument("--refit", action="store_true", help="fastverify: fd_ransac_refit (rounds 2) on each model after fd_ransac")
 p.add_argument("--pnp", action="store_true",
                help="fastverify: implies --pose; fd_pnp_ransac and fd_pnp_refit of the pair's second frame against fd_pose_recover's points")
+p.add_argument("--align", action="store_true",
+               help="fastverify: implies --pose; fd_align_ransac, fd_align_refit and fd_align_apply of fd_pose_recover's points against fd_triangulate's")
 p.add_argument("--ba", action="store_true", help="fastverify: implies --pnp; fd_bundle_adjust of each pair's two cameras and its points")
 p.add_argument("--pose", action="store_true",
                help="fastverify: fd_pose_recover on the fundamental matrix (the refit one with --refit), then fd_triangulate with its pose")
@@ -219,9 +222,9 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
     base = torch.nn.functional.avg_pool2d(noise(1, 720 + 64, 1280 + 128).float()[None], 3, 1, 1)[0, 0]
     base = ((base - base.mean()) * 2.5 + 128.0).clamp(0, 255).to(torch.uint8)
     frames = torch.stack([base[i:i + 720, 2 * i:2 * i + 1280] for i in range(64)]).contiguous()
-    out, refit, pose, tri, pnp, ba = None, {}, None, None, None, None
+    out, refit, pose, tri, pnp, ba, ali = None, {}, None, None, None, None, None
     a.pnp = a.pnp or a.ba
-    a.pose = a.pose or a.pnp
+    a.pose = a.pose or a.pnp or a.align
     cam = (1000.0, 1000.0, 639.5, 359.5)
     for _ in range(a.calls or 10):
         res = fd.detect_points(kind, frames, 500, 15, THR[kind])
@@ -261,6 +264,16 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
                                           threshold=2.0, out=pnp[0])
                     fd.refine_pnp(pts, res.xy[1:], solved, cam, matches=out[0], counts=res.counts[:-1], rounds=4, threshold=2.0,
                                   out=pnp[1])
+                if a.align:
+                    if ali is None:
+                        ali = [(torch.empty((63, 13), dtype=torch.float64, device="cuda"), torch.empty_like(pose[3]),
+                                torch.empty_like(pose[4]), torch.empty_like(pose[1])) for _ in range(2)]
+                        moved = torch.empty_like(pose[2])
+                    # the same slots triangulated twice: the list is fd_pnp_ransac's (the points in front), the model the identity
+                    src, dst = fd.PointsResult(pose[2], pose[3], pose[4]), fd.PointsResult(*tri)
+                    joined = fd.align_points(src, dst, counts=res.counts[:-1], hypotheses=256, threshold=0.05, out=ali[0])
+                    fitted = fd.refine_alignment(src, dst, joined, counts=res.counts[:-1], rounds=4, threshold=0.05, out=ali[1])
+                    fd.transform_points(fitted, src, counts=res.counts[:-1], out=moved)
                 if a.ba:
                     if ba is None:
                         ident = torch.tensor([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0, 0, 0], dtype=torch.float64, device="cuda").repeat(63, 1)
@@ -276,6 +289,9 @@ elif a.shape == "fastverify":  # detect -> describe -> match -> verify on consec
     if a.ba:
         print("bundle adjustment: accepted trials (mean):", float(ba[5].float().mean()), "inlier observations (mean):",
               float(ba[3].float().mean()), "cost before / after (mean):", float(ba[4][:, 0].mean()), float(ba[4][:, 1].mean()))
+    if a.align:
+        print("frames with an alignment:", int((ali[0][3] >= 0).sum()), "alignment inliers (mean):", float(ali[0][2].float().mean()),
+              "refined (mean):", float(ali[1][2].float().mean()), "accepted rounds (mean):", float(ali[1][3].float().mean()))
     if a.pnp:
         print("frames with a PnP pose:", int((pnp[0][3] >= 0).sum()), "PnP inliers (mean):", float(pnp[0][2].float().mean()),
               "refined (mean):", float(pnp[1][2].float().mean()), "accepted rounds (mean):", float(pnp[1][3].float().mean()))
