@@ -2,6 +2,8 @@
 // One host-pointer call per Verify: the positions go up, three kernels run, the mask and the model come back.
 // Refit, RecoverPose and Triangulate are one host-pointer call each as well (fd_ransac_refit, fd_pose_recover,
 // fd_triangulate), and so are SolvePnP, RefinePnP, BundleAdjust, AlignPoints, RefineAlignment and TransformPoints.
+// A method is its size checks, its options struct and its call; what the three RANSAC methods and the three refit
+// methods do before and after their call is written once (Begin, NoModel, RansacDone, RefitDone).
 #include "feature_detector/geometric_verifier.h"
 
 #include <algorithm>
@@ -12,6 +14,55 @@
 namespace feature_detector {
 
 namespace {
+
+// An optional array's data, or nullptr.
+template <class T>
+const T *Data(const std::vector<T> *v) {
+    return v ? v->data() : nullptr;
+}
+
+// After a method's size checks (why: what does not fit, or nullptr): the context, or nullptr with the failure reported.
+fd_ctx *Begin(DeviceContext &context, const char *method, const char *why) {
+    if (why) {
+        context.Fail(std::string(method) + ": " + why);
+        return nullptr;
+    }
+    return context.Acquire();
+}
+
+// The outputs of Verify, SolvePnP and AlignPoints before their call and after one that failed: no inlier, a zero model,
+// no hypothesis.
+template <size_t W>
+void NoModel(size_t n, std::vector<uint8_t> &inlier, std::array<double, W> *model, int32_t *best_hypothesis) {
+    inlier.assign(n, 0);
+    if (model) model->fill(0.0);
+    if (best_hypothesis) *best_hypothesis = -1;
+}
+
+// What those three do with their call's status rc and its winner `best`.
+template <size_t W>
+bool RansacDone(DeviceContext &context, int rc, const char *call, const char *no_model, int32_t best, std::vector<uint8_t> &inlier,
+                std::array<double, W> *model, int32_t *best_hypothesis) {
+    if (rc != FD_OK) {
+        NoModel(inlier.size(), inlier, model, best_hypothesis);
+        return context.FailCall(call);
+    }
+    if (best < 0) return context.Fail(no_model);
+    if (best_hypothesis) *best_hypothesis = best;
+    return true;
+}
+
+// What Refit, RefinePnP and RefineAlignment do with their call's status rc: a failed call leaves the inliers and the
+// model as given; otherwise both are replaced by the call's (out_inlier, m) and the accepted rounds are reported.
+template <size_t W>
+bool RefitDone(DeviceContext &context, int rc, const char *call, std::vector<uint8_t> &inlier, std::vector<uint8_t> &out_inlier,
+               std::array<double, W> &model, const std::array<double, W> &m, int32_t accepted, int32_t *accepted_rounds) {
+    if (rc != FD_OK) return context.FailCall(call);
+    inlier.swap(out_inlier);
+    model = m;
+    if (accepted_rounds) *accepted_rounds = accepted;
+    return true;
+}
 
 // The size checks of the calls on image pairs; nullptr when the arguments fit. inlier: nullptr where the call has none.
 const char *PairSizes(size_t n, size_t trains, const std::vector<uint8_t> *inlier, const std::vector<int32_t> *train_index,
@@ -45,29 +96,21 @@ bool GeometricVerifier::Verify(const std::vector<Vec2> &query_uv, const std::vec
                                std::vector<uint8_t> &inlier, const std::vector<int32_t> *train_index,
                                const std::vector<uint8_t> *valid, std::array<double, 9> *model, int32_t *best_hypothesis) {
     const size_t n = query_uv.size();
-    inlier.assign(n, 0);
-    if (model) model->fill(0.0);
-    if (best_hypothesis) *best_hypothesis = -1;
-    if (const char *why = PairSizes(n, train_uv.size(), nullptr, train_index, valid))
-        return context_.Fail(std::string("Verify: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    NoModel(n, inlier, model, best_hypothesis);
+    fd_ctx *ctx = Begin(context_, "Verify", PairSizes(n, train_uv.size(), nullptr, train_index, valid));
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
     const std::vector<float> t = FlattenPadded(train_uv);
     const fd_ransac_opts o{options_.kModel, options_.kHypotheses, options_.kSeed, options_.kThreshold,
                            options_.kCenterX, options_.kCenterY, options_.kScale};
-    double m[9];
+    std::array<double, 9> m{};  // the model is optional: a failed call or one without a winner leaves *model zero
     int32_t best = -1;
-    const int rc = fd_ransac(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
-                             static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
-                             valid ? valid->data() : nullptr, m, inlier.data(), nullptr, &best, 0);
-    if (rc != FD_OK) {
-        inlier.assign(n, 0);
-        return context_.FailCall("fd_ransac");
-    }
-    if (best < 0) return context_.Fail("Verify: no model (too few correspondences, or every sample degenerate)");
-    if (model) std::copy(m, m + 9, model->begin());
-    if (best_hypothesis) *best_hypothesis = best;
+    const int rc = fd_ransac(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(), static_cast<int32_t>(train_uv.size()),
+                             Data(train_index), Data(valid), m.data(), inlier.data(), nullptr, &best, 0);
+    if (!RansacDone<9>(context_, rc, "fd_ransac", "Verify: no model (too few correspondences, or every sample degenerate)", best,
+                       inlier, nullptr, best_hypothesis))
+        return false;
+    if (model) *model = m;
     return true;
 }
 
@@ -76,25 +119,18 @@ bool GeometricVerifier::Refit(const std::vector<Vec2> &query_uv, const std::vect
                               const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
     const size_t n = query_uv.size();
     if (accepted_rounds) *accepted_rounds = 0;
-    if (const char *why = PairSizes(n, train_uv.size(), &inlier, train_index, valid))
-        return context_.Fail(std::string("Refit: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    fd_ctx *ctx = Begin(context_, "Refit", PairSizes(n, train_uv.size(), &inlier, train_index, valid));
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
     const std::vector<float> t = FlattenPadded(train_uv);
     const fd_refit_opts o{options_.kModel, rounds, options_.kThreshold, options_.kCenterX, options_.kCenterY, options_.kScale};
     std::vector<uint8_t> out_inlier(n);
-    double m[9];
+    std::array<double, 9> m;
     int32_t accepted = 0;
     const int rc = fd_ransac_refit(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
-                                   static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
-                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), m, out_inlier.data(), nullptr,
-                                   &accepted, 0);
-    if (rc != FD_OK) return context_.FailCall("fd_ransac_refit");
-    inlier.swap(out_inlier);
-    std::copy(m, m + 9, model.begin());
-    if (accepted_rounds) *accepted_rounds = accepted;
-    return true;
+                                   static_cast<int32_t>(train_uv.size()), Data(train_index), Data(valid), model.data(),
+                                   inlier.data(), m.data(), out_inlier.data(), nullptr, &accepted, 0);
+    return RefitDone(context_, rc, "fd_ransac_refit", inlier, out_inlier, model, m, accepted, accepted_rounds);
 }
 
 namespace {
@@ -115,18 +151,15 @@ bool GeometricVerifier::RecoverPose(const std::vector<Vec2> &query_uv, const std
     points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
     point_valid.assign(n, 0);
     if (choice) *choice = -1;
-    if (const char *why = PairSizes(n, train_uv.size(), &inlier, train_index, valid))
-        return context_.Fail(std::string("RecoverPose: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    fd_ctx *ctx = Begin(context_, "RecoverPose", PairSizes(n, train_uv.size(), &inlier, train_index, valid));
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
     const std::vector<float> t = FlattenPadded(train_uv);
     const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
     int32_t won = -1;
     const int rc = fd_pose_recover(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
-                                   static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
-                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), pose.data(), &won,
-                                   points[0].data(), point_valid.data(), nullptr, 0);
+                                   static_cast<int32_t>(train_uv.size()), Data(train_index), Data(valid), model.data(),
+                                   inlier.data(), pose.data(), &won, points[0].data(), point_valid.data(), nullptr, 0);
     if (rc != FD_OK) {
         pose.fill(0.0);
         points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
@@ -147,17 +180,14 @@ bool GeometricVerifier::Triangulate(const std::vector<Vec2> &query_uv, const std
     points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
     point_valid.assign(n, 0);
     if (count) *count = 0;
-    if (const char *why = PairSizes(n, train_uv.size(), inlier, train_index, valid))
-        return context_.Fail(std::string("Triangulate: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    fd_ctx *ctx = Begin(context_, "Triangulate", PairSizes(n, train_uv.size(), inlier, train_index, valid));
     if (!ctx) return false;
     const std::vector<float> q = Flatten(query_uv);
     const std::vector<float> t = FlattenPadded(train_uv);
     const fd_pose_opts o = PoseOpts(query_camera, train_camera, pose_options_);
     int32_t found = 0;
     const int rc = fd_triangulate(ctx, 1, &o, q.data(), nullptr, static_cast<int32_t>(n), t.data(),
-                                  static_cast<int32_t>(train_uv.size()), train_index ? train_index->data() : nullptr,
-                                  valid ? valid->data() : nullptr, pose.data(), inlier ? inlier->data() : nullptr,
+                                  static_cast<int32_t>(train_uv.size()), Data(train_index), Data(valid), pose.data(), Data(inlier),
                                   points[0].data(), point_valid.data(), &found, 0);
     if (rc != FD_OK) {
         points.assign(n, std::array<float, 3>{0.0f, 0.0f, 0.0f});
@@ -170,14 +200,15 @@ bool GeometricVerifier::Triangulate(const std::vector<Vec2> &query_uv, const std
 
 namespace {
 
-// The size checks SolvePnP and RefinePnP share; nullptr when the arguments fit.
+// The size checks SolvePnP and RefinePnP share; nullptr when the arguments fit. inlier: nullptr where the call has none.
 const char *PnpSizes(size_t n, size_t images, const std::vector<uint8_t> *point_valid, const std::vector<int32_t> *image_index,
-                     const std::vector<uint8_t> *valid) {
+                     const std::vector<uint8_t> *valid, const std::vector<uint8_t> *inlier) {
     if (n == 0) return "no points";
     if (point_valid && point_valid->size() != n) return "one point_valid flag per point is needed";
     if (image_index && image_index->size() != n) return "one image index per point is needed";
     if (valid && valid->size() != n) return "one valid flag per point is needed";
     if (!image_index && images < n) return "without image_index every point needs its image position";
+    if (inlier && inlier->size() != n) return "one inlier flag per point is needed";
     return nullptr;
 }
 
@@ -193,28 +224,17 @@ bool GeometricVerifier::SolvePnP(const std::vector<std::array<float, 3>> &points
                                  const std::vector<uint8_t> *point_valid, const std::vector<int32_t> *image_index,
                                  const std::vector<uint8_t> *valid, int32_t *best_hypothesis) {
     const size_t n = points.size();
-    pose.fill(0.0);
-    inlier.assign(n, 0);
-    if (best_hypothesis) *best_hypothesis = -1;
-    if (const char *why = PnpSizes(n, image_uv.size(), point_valid, image_index, valid))
-        return context_.Fail(std::string("SolvePnP: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    NoModel(n, inlier, &pose, best_hypothesis);
+    fd_ctx *ctx = Begin(context_, "SolvePnP", PnpSizes(n, image_uv.size(), point_valid, image_index, valid, nullptr));
     if (!ctx) return false;
     const std::vector<float> t = FlattenPadded(image_uv);
     const fd_pnp_opts o = PnpOpts(pnp_options_, camera, 1);
     int32_t best = -1;
-    const int rc = fd_pnp_ransac(ctx, 1, &o, points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
-                                 static_cast<int32_t>(n), t.data(), static_cast<int32_t>(image_uv.size()),
-                                 image_index ? image_index->data() : nullptr, valid ? valid->data() : nullptr, pose.data(),
-                                 inlier.data(), nullptr, &best, 0);
-    if (rc != FD_OK) {
-        pose.fill(0.0);
-        inlier.assign(n, 0);
-        return context_.FailCall("fd_pnp_ransac");
-    }
-    if (best < 0) return context_.Fail("SolvePnP: no pose (fewer than 6 correspondences, or every sample degenerate)");
-    if (best_hypothesis) *best_hypothesis = best;
-    return true;
+    const int rc = fd_pnp_ransac(ctx, 1, &o, points[0].data(), Data(point_valid), nullptr, static_cast<int32_t>(n), t.data(),
+                                 static_cast<int32_t>(image_uv.size()), Data(image_index), Data(valid), pose.data(), inlier.data(),
+                                 nullptr, &best, 0);
+    return RansacDone(context_, rc, "fd_pnp_ransac", "SolvePnP: no pose (fewer than 6 correspondences, or every sample degenerate)",
+                      best, inlier, &pose, best_hypothesis);
 }
 
 bool GeometricVerifier::RefinePnP(const std::vector<std::array<float, 3>> &points, const std::vector<Vec2> &image_uv,
@@ -223,25 +243,17 @@ bool GeometricVerifier::RefinePnP(const std::vector<std::array<float, 3>> &point
                                   const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
     const size_t n = points.size();
     if (accepted_rounds) *accepted_rounds = 0;
-    if (const char *why = PnpSizes(n, image_uv.size(), point_valid, image_index, valid))
-        return context_.Fail(std::string("RefinePnP: ") + why);
-    if (inlier.size() != n) return context_.Fail("RefinePnP: one inlier flag per point is needed");
-    fd_ctx *ctx = context_.Acquire();
+    fd_ctx *ctx = Begin(context_, "RefinePnP", PnpSizes(n, image_uv.size(), point_valid, image_index, valid, &inlier));
     if (!ctx) return false;
     const std::vector<float> t = FlattenPadded(image_uv);
     const fd_pnp_opts o = PnpOpts(pnp_options_, camera, rounds);
     std::vector<uint8_t> out_inlier(n);
-    double p[12];
+    std::array<double, 12> p;
     int32_t accepted = 0;
-    const int rc = fd_pnp_refit(ctx, 1, &o, points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
-                                static_cast<int32_t>(n), t.data(), static_cast<int32_t>(image_uv.size()),
-                                image_index ? image_index->data() : nullptr, valid ? valid->data() : nullptr, pose.data(),
-                                inlier.data(), p, out_inlier.data(), nullptr, &accepted, 0);
-    if (rc != FD_OK) return context_.FailCall("fd_pnp_refit");
-    inlier.swap(out_inlier);
-    std::copy(p, p + 12, pose.begin());
-    if (accepted_rounds) *accepted_rounds = accepted;
-    return true;
+    const int rc = fd_pnp_refit(ctx, 1, &o, points[0].data(), Data(point_valid), nullptr, static_cast<int32_t>(n), t.data(),
+                                static_cast<int32_t>(image_uv.size()), Data(image_index), Data(valid), pose.data(), inlier.data(),
+                                p.data(), out_inlier.data(), nullptr, &accepted, 0);
+    return RefitDone(context_, rc, "fd_pnp_refit", inlier, out_inlier, pose, p, accepted, accepted_rounds);
 }
 
 bool GeometricVerifier::BundleAdjust(std::vector<std::array<double, 12>> &poses, std::vector<std::array<float, 3>> &points,
@@ -282,9 +294,9 @@ bool GeometricVerifier::BundleAdjust(std::vector<std::array<double, 12>> &poses,
     std::vector<uint8_t> out_inlier(cams * n);
     double out_cost[2] = {0.0, 0.0};
     int32_t accepted = 0;
-    const int rc = fd_bundle_adjust(ctx, 1, static_cast<int>(cams), &o, poses[0].data(), fixed ? fixed->data() : nullptr,
-                                    points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr, static_cast<int32_t>(n),
-                                    obs.data(), observation_valid ? ov.data() : nullptr, static_cast<int32_t>(n), out_poses.data(),
+    const int rc = fd_bundle_adjust(ctx, 1, static_cast<int>(cams), &o, poses[0].data(), Data(fixed), points[0].data(),
+                                    Data(point_valid), nullptr, static_cast<int32_t>(n), obs.data(),
+                                    observation_valid ? ov.data() : nullptr, static_cast<int32_t>(n), out_poses.data(),
                                     out_points.data(), out_inlier.data(), nullptr, out_cost, &accepted, 0);
     if (rc != FD_OK) return context_.FailCall("fd_bundle_adjust");
     for (size_t c = 0; c < cams; ++c) {
@@ -299,15 +311,18 @@ bool GeometricVerifier::BundleAdjust(std::vector<std::array<double, 12>> &poses,
 
 namespace {
 
-// The size checks AlignPoints and RefineAlignment share; nullptr when the arguments fit.
+// The size checks AlignPoints and RefineAlignment share; nullptr when the arguments fit. inlier: nullptr where the call
+// has none.
 const char *AlignSizes(size_t n, size_t targets, const std::vector<uint8_t> *source_valid, const std::vector<uint8_t> *target_valid,
-                       const std::vector<int32_t> *target_index, const std::vector<uint8_t> *valid) {
+                       const std::vector<int32_t> *target_index, const std::vector<uint8_t> *valid,
+                       const std::vector<uint8_t> *inlier) {
     if (n == 0) return "no source points";
     if (source_valid && source_valid->size() != n) return "one source_valid flag per source point is needed";
     if (target_valid && target_valid->size() != targets) return "one target_valid flag per target point is needed";
     if (target_index && target_index->size() != n) return "one target index per source point is needed";
     if (valid && valid->size() != n) return "one valid flag per source point is needed";
     if (!target_index && targets < n) return "without target_index every source point needs its target point";
+    if (inlier && inlier->size() != n) return "one inlier flag per source point is needed";
     return nullptr;
 }
 
@@ -325,27 +340,16 @@ bool GeometricVerifier::AlignPoints(const std::vector<std::array<float, 3>> &sou
                                     const std::vector<int32_t> *target_index, const std::vector<uint8_t> *valid,
                                     int32_t *best_hypothesis) {
     const size_t n = source.size();
-    model.fill(0.0);
-    inlier.assign(n, 0);
-    if (best_hypothesis) *best_hypothesis = -1;
-    if (const char *why = AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid))
-        return context_.Fail(std::string("AlignPoints: ") + why);
-    fd_ctx *ctx = context_.Acquire();
+    NoModel(n, inlier, &model, best_hypothesis);
+    fd_ctx *ctx = Begin(context_, "AlignPoints", AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid, nullptr));
     if (!ctx) return false;
     const fd_align_opts o{align_options_.kKind, align_options_.kHypotheses, align_options_.kSeed, 1, align_options_.kThreshold};
     int32_t best = -1;
-    const int rc = fd_align_ransac(ctx, 1, &o, source[0].data(), source_valid ? source_valid->data() : nullptr, nullptr,
-                                   static_cast<int32_t>(n), TargetData(target), target_valid ? target_valid->data() : nullptr,
-                                   static_cast<int32_t>(target.size()), target_index ? target_index->data() : nullptr,
-                                   valid ? valid->data() : nullptr, model.data(), inlier.data(), nullptr, &best, 0);
-    if (rc != FD_OK) {
-        model.fill(0.0);
-        inlier.assign(n, 0);
-        return context_.FailCall("fd_align_ransac");
-    }
-    if (best < 0) return context_.Fail("AlignPoints: no model (fewer than 3 correspondences, or every sample degenerate)");
-    if (best_hypothesis) *best_hypothesis = best;
-    return true;
+    const int rc = fd_align_ransac(ctx, 1, &o, source[0].data(), Data(source_valid), nullptr, static_cast<int32_t>(n),
+                                   TargetData(target), Data(target_valid), static_cast<int32_t>(target.size()), Data(target_index),
+                                   Data(valid), model.data(), inlier.data(), nullptr, &best, 0);
+    return RansacDone(context_, rc, "fd_align_ransac", "AlignPoints: no model (fewer than 3 correspondences, or every sample degenerate)",
+                      best, inlier, &model, best_hypothesis);
 }
 
 bool GeometricVerifier::RefineAlignment(const std::vector<std::array<float, 3>> &source,
@@ -355,25 +359,16 @@ bool GeometricVerifier::RefineAlignment(const std::vector<std::array<float, 3>> 
                                         const std::vector<uint8_t> *valid, int32_t *accepted_rounds) {
     const size_t n = source.size();
     if (accepted_rounds) *accepted_rounds = 0;
-    if (const char *why = AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid))
-        return context_.Fail(std::string("RefineAlignment: ") + why);
-    if (inlier.size() != n) return context_.Fail("RefineAlignment: one inlier flag per source point is needed");
-    fd_ctx *ctx = context_.Acquire();
+    fd_ctx *ctx = Begin(context_, "RefineAlignment", AlignSizes(n, target.size(), source_valid, target_valid, target_index, valid, &inlier));
     if (!ctx) return false;
     const fd_align_opts o{align_options_.kKind, 1, 0, rounds, align_options_.kThreshold};
     std::vector<uint8_t> out_inlier(n);
-    double m[13];
+    std::array<double, 13> m;
     int32_t accepted = 0;
-    const int rc = fd_align_refit(ctx, 1, &o, source[0].data(), source_valid ? source_valid->data() : nullptr, nullptr,
-                                  static_cast<int32_t>(n), TargetData(target), target_valid ? target_valid->data() : nullptr,
-                                  static_cast<int32_t>(target.size()), target_index ? target_index->data() : nullptr,
-                                  valid ? valid->data() : nullptr, model.data(), inlier.data(), m, out_inlier.data(), nullptr,
-                                  &accepted, 0);
-    if (rc != FD_OK) return context_.FailCall("fd_align_refit");
-    inlier.swap(out_inlier);
-    std::copy(m, m + 13, model.begin());
-    if (accepted_rounds) *accepted_rounds = accepted;
-    return true;
+    const int rc = fd_align_refit(ctx, 1, &o, source[0].data(), Data(source_valid), nullptr, static_cast<int32_t>(n),
+                                  TargetData(target), Data(target_valid), static_cast<int32_t>(target.size()), Data(target_index),
+                                  Data(valid), model.data(), inlier.data(), m.data(), out_inlier.data(), nullptr, &accepted, 0);
+    return RefitDone(context_, rc, "fd_align_refit", inlier, out_inlier, model, m, accepted, accepted_rounds);
 }
 
 bool GeometricVerifier::TransformPoints(const std::array<double, 13> &model, std::vector<std::array<float, 3>> &points,
@@ -384,8 +379,8 @@ bool GeometricVerifier::TransformPoints(const std::array<double, 13> &model, std
     fd_ctx *ctx = context_.Acquire();
     if (!ctx) return false;
     std::vector<std::array<float, 3>> out(points);  // the call fails as a whole: points are then left as given
-    const int rc = fd_align_apply(ctx, 1, model.data(), points[0].data(), point_valid ? point_valid->data() : nullptr, nullptr,
-                                  static_cast<int32_t>(n), out[0].data(), 0);
+    const int rc = fd_align_apply(ctx, 1, model.data(), points[0].data(), Data(point_valid), nullptr, static_cast<int32_t>(n),
+                                  out[0].data(), 0);
     if (rc != FD_OK) return context_.FailCall("fd_align_apply");
     points.swap(out);
     return true;

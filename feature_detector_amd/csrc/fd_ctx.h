@@ -242,36 +242,6 @@ int zero_counts(fd_ctx *c, int32_t *out_counts, int batch, int io_on_device);
 // n camera values (fx, fy, cx, cy per camera) into out: all finite, fx and fy non-zero.
 int check_camera(fd_ctx *c, const double *cam, int n, double *out);
 
-// What the estimators (fd_rt_ransac.cpp, fd_rt_align.cpp) ask of their [batch][q_stride] slots and the partners
-// among [batch][t_stride].
-inline int check_slots(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx) {
-    if (batch < 1) return fail(c, FD_ERR_INVALID, "batch must be >= 1");
-    if (q_stride < 0 || t_stride < 0) return fail(c, FD_ERR_INVALID, "strides must be >= 0");
-    if (!match_idx && t_stride < q_stride)
-        return fail(c, FD_ERR_INVALID, "without match_idx slot i pairs with slot i: t_stride must be >= q_stride");
-    return FD_OK;
-}
-
-// The slot fields of an argument block (RansacArgs, PoseArgs, PnpArgs, AlignArgs).
-template <class A>
-void slot_fields(A &a, int batch, int32_t q_stride, int32_t t_stride) {
-    a.batch = batch;
-    a.q_stride = q_stride;
-    a.t_stride = t_stride;
-}
-
-// The workspace of a compaction kernel (RansacArgs, PnpArgs, AlignArgs): the frames' lists of `doubles` per
-// correspondence, every slot's index in them, their lengths and the frames' vote words.
-template <class A>
-int list_workspace(fd_ctx *c, A &a, size_t doubles) {
-    const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
-    FD_HIP_TRY(c, ensure_as(c, c->g_corr, doubles * qs, a.corr));
-    FD_HIP_TRY(c, ensure_as(c, c->g_cidx, qs, a.cidx));
-    FD_HIP_TRY(c, ensure_as(c, c->g_n, a.batch, a.n));
-    FD_HIP_TRY(c, ensure_as(c, c->g_best, a.batch, a.best));
-    return FD_OK;
-}
-
 // k_flow_finish after zeroing its counts (fd_flow_lk, fd_points_refine).
 int finish_counts(fd_ctx *c, const fdk::FlowFinishArgs &fin);
 

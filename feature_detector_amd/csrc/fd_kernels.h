@@ -509,16 +509,16 @@ struct PnpArgs {
     int32_t *n;                  // [batch] correspondences
     double *models;              // [batch][hypotheses][12] camera matrices of the conditioned points
     unsigned long long *best;    // [batch] as RansacArgs::best
-    double *out_pose;            // [batch][12]
+    double *out_model;           // [batch][12]
     uint8_t *out_inlier;         // [batch][q_stride] or null
     int32_t *out_counts, *out_best;  // [batch] or null
 };
 
 // k_pnp_compact runs on `r` (hypotheses, seed, models, out_best unused); k_pnp_refit reads r's lists and writes
-// r.out_pose, r.out_inlier, r.out_counts.
+// r.out_model, r.out_inlier, r.out_counts.
 struct PnpRefitArgs {
     PnpArgs r;
-    const double *in_pose;       // [batch][12]; may be r.out_pose
+    const double *in_model;      // [batch][12]; may be r.out_model
     const uint8_t *in_inlier;    // [batch][q_stride]; only a byte equal to 1 is a member; may be r.out_inlier
     uint8_t *member;             // [batch][2][q_stride] workspace: membership by list position, current and candidate
     int rounds;                  // 1..8

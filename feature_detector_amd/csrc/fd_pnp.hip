@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_finish(PnpArgs a) {
     if (tid != 0) return;
     if (a.out_counts) a.out_counts[f] = count;
     if (a.out_best) a.out_best[f] = has ? h : -1;
-    double *op = a.out_pose + static_cast<int64_t>(f) * 12;
+    double *op = a.out_model + static_cast<int64_t>(f) * 12;
 #pragma unroll
     for (int c = 0; c < 12; ++c) op[c] = pose_s[c];
 }
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
     const double fx = a.cam[0], fy = a.cam[1];
     const Corr5 *corr = reinterpret_cast<const Corr5 *>(a.corr) + s0;
     Support sup{g.member + 2 * s0, a.q_stride, 0};
-    if (tid < 12) poses[0][tid] = g.in_pose[static_cast<int64_t>(f) * 12 + tid];
+    if (tid < 12) poses[0][tid] = g.in_model[static_cast<int64_t>(f) * 12 + tid];
     load_members(a, f, nf, g.in_inlier, sup.mem);  // its barrier: the pose too
     double P[12];
     pose_matrix(poses[0], P);
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
         mine += pnp_inlier(P, corr[i], fx, fy, a.tt) ? 1u : 0u;
     }
     const int members0 = wg_count(mine0, &total);
-    sup.count = wg_count(mine, &total);  // c_0: what in_pose classifies, not |S_0|
+    sup.count = wg_count(mine, &total);  // c_0: what in_model classifies, not |S_0|
 
     for (int round = 0; round < g.rounds; ++round) {  // every exit is uniform over the workgroup
         double pose[12];
@@ -287,11 +287,11 @@ __global__ __launch_bounds__(kRansacThreads) void k_pnp_refit(PnpRefitArgs g) {
     if (tid != 0) return;
     if (a.out_counts) a.out_counts[f] = sup.done ? sup.count : members0;
     if (g.out_rounds) g.out_rounds[f] = sup.done;
-    double *op = a.out_pose + static_cast<int64_t>(f) * 12;
+    double *op = a.out_model + static_cast<int64_t>(f) * 12;
     if (sup.done)
         copy_bits<12>(poses[sup.cur], op);
-    else  // in_pose's bits as they are (out_pose may be in_pose)
-        copy_bits<12>(g.in_pose + static_cast<int64_t>(f) * 12, op);
+    else  // in_model's bits as they are (out_model may be in_model)
+        copy_bits<12>(g.in_model + static_cast<int64_t>(f) * 12, op);
 }
 
 }  // namespace

@@ -1,16 +1,15 @@
 // Host runtime of libfdhip.so: the alignment of two 3-D point sets (fd_align_ransac, fd_align_refit) and its
-// application (fd_align_apply) over the kernels of fd_align.hip. The slot checks, the workspace of the compaction
-// kernel, the staging of host arrays and the outputs of a call without slots are the ones fd_rt_ransac.cpp uses
-// (fd_ctx.h).
+// application (fd_align_apply) over the kernels of fd_align.hip. The two estimator calls keep their checks and hand on
+// to the drivers they share with fd_rt_ransac.cpp (fd_rt_estimate.h).
 #include <cmath>
 
-#include "fd_ctx.h"
+#include "fd_rt_estimate.h"
 
 using namespace fdrt;
 
 namespace {
 
-constexpr size_t kModel = 13;  // R row-major, t, s
+constexpr size_t kModel = 13, kCorr = 6;  // doubles per model (R row-major, t, s) and per correspondence (X, Y)
 
 // What fd_align_ransac and fd_align_refit ask of the arguments they share, and the fields both fill alike.
 int align_args(fd_ctx *c, fdk::AlignArgs &a, int batch, const fd_align_opts *o, int32_t q_stride, int32_t t_stride,
@@ -52,35 +51,17 @@ int fd_align_ransac(fd_ctx *c, int batch, const fd_align_opts *opts, const float
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xyz || !t_xyz || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
     fdk::AlignArgs a{};
-    int rc = align_args(c, a, batch, opts, q_stride, t_stride, match_idx);
+    const int rc = align_args(c, a, batch, opts, q_stride, t_stride, match_idx);
     if (rc) return rc;
     if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
         return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t models = kModel * batch;
-    if (q_stride == 0) {  // no slots: no frame has a model
-        rc = set_output(c, out_model, 0, sizeof(double) * models, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = set_output(c, out_best, 0xFF, sizeof(int32_t) * batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
-    rc = list_workspace(c, a, 6);
-    if (rc) return rc;
-    FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * kModel, a.models));
-    HostIo io(c, io_on_device);
-    rc = align_inputs(c, io, a, q_xyz, q_valid, q_counts, t_xyz, t_valid, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.out(out_model, models, a.out_model));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
-    FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
-    FD_HIP_TRY(c, fdk::launch_align_ransac(a, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::AlignArgs &r) {
+        return align_inputs(c, io, r, q_xyz, q_valid, q_counts, t_xyz, t_valid, match_idx, pair_valid);
+    };
+    return ransac_call(c, a, kModel, kCorr, stage, fdk::launch_align_ransac,
+                       {q_counts, nullptr, nullptr, out_model, out_inlier, out_counts, out_best, io_on_device});
 }
 
 int fd_align_refit(fd_ctx *c, int batch, const fd_align_opts *opts, const float *q_xyz, const uint8_t *q_valid,
@@ -90,35 +71,16 @@ int fd_align_refit(fd_ctx *c, int batch, const fd_align_opts *opts, const float 
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xyz || !t_xyz || !in_model || !in_inlier || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
     fdk::AlignRefitArgs g{};
-    int rc = align_args(c, g.r, batch, opts, q_stride, t_stride, match_idx);
+    const int rc = align_args(c, g.r, batch, opts, q_stride, t_stride, match_idx);
     if (rc) return rc;
     if (opts->rounds < 1 || opts->rounds > FD_ALIGN_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 8]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t models = kModel * batch;
-    if (q_stride == 0) {  // no slots: no round is accepted
-        rc = copy_output(c, out_model, in_model, sizeof(double) * models, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
     g.rounds = opts->rounds;
-    rc = list_workspace(c, g.r, 6);
-    if (rc) return rc;
-    FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
-    HostIo io(c, io_on_device);  // 9 inputs and 4 outputs: the whole staging pool
-    rc = align_inputs(c, io, g.r, q_xyz, q_valid, q_counts, t_xyz, t_valid, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.in(in_model, models, g.in_model));
-    FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
-    FD_HIP_TRY(c, io.out(out_model, models, g.r.out_model));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, g.r.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
-    FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
-    FD_HIP_TRY(c, fdk::launch_align_refit(g, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::AlignArgs &r) {
+        return align_inputs(c, io, r, q_xyz, q_valid, q_counts, t_xyz, t_valid, match_idx, pair_valid);
+    };
+    // 9 inputs and 4 outputs: the whole staging pool
+    return refit_call(c, g, kModel, kCorr, stage, fdk::launch_align_refit,
+                      {q_counts, in_model, in_inlier, out_model, out_inlier, out_counts, out_rounds, io_on_device});
 }
 
 int fd_align_apply(fd_ctx *c, int batch, const double *model, const float *xyz_in, const uint8_t *valid, const int32_t *counts,

@@ -1,16 +1,19 @@
 // Host runtime of libfdhip.so: RANSAC verification of matches and tracks (fd_ransac), the least-squares
 // refit of its model (fd_ransac_refit), the pose of a fundamental matrix (fd_pose_recover) and triangulation
 // (fd_triangulate) over the kernels of fd_ransac.hip, and the absolute pose from 3-D points (fd_pnp_ransac,
-// fd_pnp_refit) over those of fd_pnp.hip. The six calls share the staging of the pair arrays here, and with
-// fd_rt_align.cpp their slot checks, the workspace of the compaction kernels and the outputs of a call without slots
-// (fd_ctx.h).
+// fd_pnp_refit) over those of fd_pnp.hip. The six calls share the staging of the pair arrays here. The RANSAC and
+// refit calls keep their checks and hand on to the drivers they share with fd_rt_align.cpp (fd_rt_estimate.h), with
+// their argument block, two widths, their input stager and their launcher.
 #include <cmath>
 
-#include "fd_ctx.h"
+#include "fd_rt_estimate.h"
 
 using namespace fdrt;
 
 namespace {
+
+// doubles per model and per correspondence: F or H and (x, y, u, v); R, t and (Xc, Yc, Zc, bx, by)
+constexpr size_t kPairModel = 9, kPairCorr = 4, kPose = 12, kPnpCorr = 5;
 
 // The pair arrays every call has behind its query side's own (q_xy, or p_xyz and p_valid), staged or handed on.
 template <class A>
@@ -24,9 +27,11 @@ int stage_pairs(fd_ctx *c, HostIo &io, A &a, const float *t_xy, const int32_t *q
     return FD_OK;
 }
 
-// What fd_ransac and fd_ransac_refit ask of the arguments they share (o: fd_ransac_opts or fd_refit_opts).
+// What fd_ransac and fd_ransac_refit ask of the arguments they share (o: fd_ransac_opts or fd_refit_opts), and the
+// fields both fill alike.
 template <class O>
-int check_pairs(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx, const O &o) {
+int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_t t_stride, const int32_t *match_idx,
+              const O &o) {
     const int rc = check_slots(c, batch, q_stride, t_stride, match_idx);
     if (rc) return rc;
     if (o.model != FD_RANSAC_FUNDAMENTAL && o.model != FD_RANSAC_HOMOGRAPHY)
@@ -35,6 +40,13 @@ int check_pairs(fd_ctx *c, int batch, int32_t q_stride, int32_t t_stride, const 
     if (!std::isfinite(o.center_x) || !std::isfinite(o.center_y))
         return fail(c, FD_ERR_INVALID, "center_x and center_y must be finite");
     if (!std::isfinite(o.scale) || !(o.scale > 0.0f)) return fail(c, FD_ERR_INVALID, "scale must be finite and > 0");
+    slot_fields(a, batch, q_stride, t_stride);
+    a.model = o.model;
+    a.cx = static_cast<double>(o.center_x);
+    a.cy = static_cast<double>(o.center_y);
+    a.scale = static_cast<double>(o.scale);
+    const double t = static_cast<double>(o.threshold) * a.scale;
+    a.tt = t * t;
     return FD_OK;
 }
 
@@ -44,19 +56,6 @@ int pair_inputs(fd_ctx *c, HostIo &io, A &a, const float *q_xy, const int32_t *q
                 const int32_t *match_idx, const uint8_t *pair_valid) {
     FD_HIP_TRY(c, io.in(q_xy, 2 * static_cast<size_t>(a.batch) * a.q_stride, a.q_xy));
     return stage_pairs(c, io, a, t_xy, q_counts, match_idx, pair_valid);
-}
-
-// The fields both calls fill alike, and the workspace of k_ransac_compact.
-template <class O>
-int pair_args(fd_ctx *c, fdk::RansacArgs &a, int batch, int32_t q_stride, int32_t t_stride, const O &o) {
-    slot_fields(a, batch, q_stride, t_stride);
-    a.model = o.model;
-    a.cx = static_cast<double>(o.center_x);
-    a.cy = static_cast<double>(o.center_y);
-    a.scale = static_cast<double>(o.scale);
-    const double t = static_cast<double>(o.threshold) * a.scale;
-    a.tt = t * t;
-    return list_workspace(c, a, 4);
 }
 
 // What fd_triangulate and fd_pose_recover ask of the arguments they share, and the option fields of the kernels'
@@ -99,7 +98,7 @@ int pnp_args(fd_ctx *c, fdk::PnpArgs &a, int batch, const fd_pnp_opts *o, int32_
     return FD_OK;
 }
 
-// The workspace of k_pnp_compact and the input arrays of both calls, staged or handed on.
+// The input arrays of both calls, staged or handed on.
 int pnp_inputs(fd_ctx *c, HostIo &io, fdk::PnpArgs &a, const float *p_xyz, const uint8_t *p_valid, const int32_t *q_counts,
                const float *t_xy, const int32_t *match_idx, const uint8_t *pair_valid) {
     const size_t qs = static_cast<size_t>(a.batch) * a.q_stride;
@@ -119,35 +118,17 @@ int fd_pnp_ransac(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_
     if (!c) return FD_ERR_INVALID;
     if (!opts || !p_xyz || !t_xy || !out_pose) return fail(c, FD_ERR_INVALID, "bad arguments");
     fdk::PnpArgs a{};
-    int rc = pnp_args(c, a, batch, opts, q_stride, t_stride, match_idx, true);
+    const int rc = pnp_args(c, a, batch, opts, q_stride, t_stride, match_idx, true);
     if (rc) return rc;
     if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
         return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t poses = static_cast<size_t>(12) * batch;
-    if (q_stride == 0) {  // no slots: no frame has a pose
-        rc = set_output(c, out_pose, 0, sizeof(double) * poses, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = set_output(c, out_best, 0xFF, sizeof(int32_t) * batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
-    rc = list_workspace(c, a, 5);
-    if (rc) return rc;
-    FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 12, a.models));
-    HostIo io(c, io_on_device);
-    rc = pnp_inputs(c, io, a, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.out(out_pose, poses, a.out_pose));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
-    FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
-    FD_HIP_TRY(c, fdk::launch_pnp_ransac(a, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::PnpArgs &r) {
+        return pnp_inputs(c, io, r, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
+    };
+    return ransac_call(c, a, kPose, kPnpCorr, stage, fdk::launch_pnp_ransac,
+                       {q_counts, nullptr, nullptr, out_pose, out_inlier, out_counts, out_best, io_on_device});
 }
 
 int fd_pnp_refit(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_xyz, const uint8_t *p_valid,
@@ -157,35 +138,15 @@ int fd_pnp_refit(fd_ctx *c, int batch, const fd_pnp_opts *opts, const float *p_x
     if (!c) return FD_ERR_INVALID;
     if (!opts || !p_xyz || !t_xy || !in_pose || !in_inlier || !out_pose) return fail(c, FD_ERR_INVALID, "bad arguments");
     fdk::PnpRefitArgs g{};
-    int rc = pnp_args(c, g.r, batch, opts, q_stride, t_stride, match_idx, false);
+    const int rc = pnp_args(c, g.r, batch, opts, q_stride, t_stride, match_idx, false);
     if (rc) return rc;
     if (opts->rounds < 1 || opts->rounds > FD_PNP_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 8]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t poses = static_cast<size_t>(12) * batch;
-    if (q_stride == 0) {  // no slots: no round is accepted
-        rc = copy_output(c, out_pose, in_pose, sizeof(double) * poses, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
     g.rounds = opts->rounds;
-    rc = list_workspace(c, g.r, 5);
-    if (rc) return rc;
-    FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
-    HostIo io(c, io_on_device);  // 8 inputs and 4 outputs: the whole staging pool
-    rc = pnp_inputs(c, io, g.r, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.in(in_pose, poses, g.in_pose));
-    FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
-    FD_HIP_TRY(c, io.out(out_pose, poses, g.r.out_pose));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, g.r.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
-    FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
-    FD_HIP_TRY(c, fdk::launch_pnp_refit(g, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::PnpArgs &r) {
+        return pnp_inputs(c, io, r, p_xyz, p_valid, q_counts, t_xy, match_idx, pair_valid);
+    };
+    return refit_call(c, g, kPose, kPnpCorr, stage, fdk::launch_pnp_refit,  // 8 inputs and 4 outputs
+                      {q_counts, in_pose, in_inlier, out_pose, out_inlier, out_counts, out_rounds, io_on_device});
 }
 
 int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_xy, const int32_t *q_counts,
@@ -193,36 +154,18 @@ int fd_ransac(fd_ctx *c, int batch, const fd_ransac_opts *opts, const float *q_x
               double *out_model, uint8_t *out_inlier, int32_t *out_counts, int32_t *out_best, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xy || !t_xy || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
-    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, *opts);
+    fdk::RansacArgs a{};
+    const int rc = pair_args(c, a, batch, q_stride, t_stride, match_idx, *opts);
     if (rc) return rc;
     if (opts->hypotheses < 1 || opts->hypotheses > FD_RANSAC_MAX_HYPOTHESES)
         return fail(c, FD_ERR_INVALID, "hypotheses must be in [1, 4096]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t models = static_cast<size_t>(9) * batch;
-    if (q_stride == 0) {  // no slots: no frame has a model
-        rc = set_output(c, out_model, 0, sizeof(double) * models, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = set_output(c, out_best, 0xFF, sizeof(int32_t) * batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
-    fdk::RansacArgs a{};
-    rc = pair_args(c, a, batch, q_stride, t_stride, *opts);
-    if (rc) return rc;
     a.hypotheses = opts->hypotheses;
     a.seed = opts->seed;
-    FD_HIP_TRY(c, ensure_as(c, c->g_models, static_cast<size_t>(batch) * opts->hypotheses * 9, a.models));
-    HostIo io(c, io_on_device);
-    rc = pair_inputs(c, io, a, q_xy, q_counts, t_xy, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.out(out_model, models, a.out_model));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, a.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, a.out_counts));
-    FD_HIP_TRY(c, io.out(out_best, batch, a.out_best));
-    FD_HIP_TRY(c, fdk::launch_ransac(a, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::RansacArgs &r) {
+        return pair_inputs(c, io, r, q_xy, q_counts, t_xy, match_idx, pair_valid);
+    };
+    return ransac_call(c, a, kPairModel, kPairCorr, stage, fdk::launch_ransac,
+                       {q_counts, nullptr, nullptr, out_model, out_inlier, out_counts, out_best, io_on_device});
 }
 
 int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float *q_xy, const int32_t *q_counts,
@@ -231,36 +174,16 @@ int fd_ransac_refit(fd_ctx *c, int batch, const fd_refit_opts *opts, const float
                     uint8_t *out_inlier, int32_t *out_counts, int32_t *out_rounds, int io_on_device) {
     if (!c) return FD_ERR_INVALID;
     if (!opts || !q_xy || !t_xy || !in_model || !in_inlier || !out_model) return fail(c, FD_ERR_INVALID, "bad arguments");
-    int rc = check_pairs(c, batch, q_stride, t_stride, match_idx, *opts);
+    fdk::RefitArgs g{};
+    const int rc = pair_args(c, g.r, batch, q_stride, t_stride, match_idx, *opts);
     if (rc) return rc;
     if (opts->rounds < 1 || opts->rounds > FD_REFIT_MAX_ROUNDS) return fail(c, FD_ERR_INVALID, "rounds must be in [1, 4]");
-    FD_HIP_TRY(c, hipSetDevice(c->device));
-    rc = refuse_sync_under_capture(c, io_on_device);
-    if (rc) return rc;
-    const size_t models = static_cast<size_t>(9) * batch;
-    if (q_stride == 0) {  // no slots: no round is accepted
-        rc = copy_output(c, out_model, in_model, sizeof(double) * models, io_on_device);
-        if (!rc) rc = zero_counts(c, out_counts, batch, io_on_device);
-        if (!rc) rc = zero_counts(c, out_rounds, batch, io_on_device);
-        return rc;
-    }
-    const size_t qs = static_cast<size_t>(batch) * q_stride;
-    fdk::RefitArgs g{};
-    rc = pair_args(c, g.r, batch, q_stride, t_stride, *opts);
-    if (rc) return rc;
     g.rounds = opts->rounds;
-    FD_HIP_TRY(c, ensure_as(c, c->g_member, 2 * qs, g.member));
-    HostIo io(c, io_on_device);  // 7 inputs and 4 outputs: the whole staging pool
-    rc = pair_inputs(c, io, g.r, q_xy, q_counts, t_xy, match_idx, pair_valid);
-    if (rc) return rc;
-    FD_HIP_TRY(c, io.in(in_model, models, g.in_model));
-    FD_HIP_TRY(c, io.in(in_inlier, qs, g.in_inlier));
-    FD_HIP_TRY(c, io.out(out_model, models, g.r.out_model));
-    FD_HIP_TRY(c, io.out_slots(out_inlier, qs, 1, g.r.out_inlier));
-    FD_HIP_TRY(c, io.out(out_counts, batch, g.r.out_counts));
-    FD_HIP_TRY(c, io.out(out_rounds, batch, g.out_rounds));
-    FD_HIP_TRY(c, fdk::launch_ransac_refit(g, c->stream));
-    return io.finish(q_counts, batch, q_stride);
+    const auto stage = [&](HostIo &io, fdk::RansacArgs &r) {
+        return pair_inputs(c, io, r, q_xy, q_counts, t_xy, match_idx, pair_valid);
+    };
+    return refit_call(c, g, kPairModel, kPairCorr, stage, fdk::launch_ransac_refit,  // 7 inputs and 4 outputs
+                      {q_counts, in_model, in_inlier, out_model, out_inlier, out_counts, out_rounds, io_on_device});
 }
 
 int fd_triangulate(fd_ctx *c, int batch, const fd_pose_opts *opts, const float *q_xy, const int32_t *q_counts, int32_t q_stride,

@@ -48,6 +48,40 @@ def _slots(on_dev, b, s, ts, first, matches, valid, counts):
             slot_arg(counts, "int32", (b,), on_dev))
 
 
+def _call(fn, ctx, on_dev, like, head, opts, inputs, specs, out):
+    """The tail every wrapper shares: the outputs of `specs` (fresh ones on the side and device of `like`, or out=), the
+    context's stream, the C function `fn` on (ctx, *head, opts, *inputs, *outputs, io_on_device) and its status. head: the
+    batch (and cameras); inputs: arrays (None: a null pointer) and the strides between them. Returns the outputs."""
+    outs = outputs(specs, out, on_dev, like.device if on_dev else None)
+    _bind_stream(ctx, on_dev)
+    args = [x if isinstance(x, int) else ptr(x) for x in (*inputs, *outs)]
+    rc = getattr(_lib.load(), fn)(ctx.ptr, *head, ctypes.byref(opts), *args, 1 if on_dev else 0)
+    _lib.check(ctx.ptr, rc)
+    return outs
+
+
+def _model_specs(b, s, w):
+    """The outputs of a RANSAC or refit call: model [B, W], inliers [B, S], counts [B], best or rounds [B]."""
+    return ((b, w), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)
+
+
+def _unwrap(points, valid):
+    """A PointsResult / PoseResult taken apart: its points, and its valid bytes unless `valid` is given."""
+    if isinstance(points, PointsResult):
+        return points.points, (points.valid if valid is None else valid)
+    return points, valid
+
+
+def _xyz(x, name, b=None, whose=None):
+    """The [B, S, 3] shape of a point array ([S, 3]: batch 1), checked against the batch b (`whose`, for the message)."""
+    shape = tuple(x.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[2] != 3 or (b is not None and shape[0] != b):
+        raise ValueError(f"{name} must be float32 [B, S, 3] (or [S, 3] for batch 1)" + ("" if b is None else f" with {whose} batch"))
+    return shape
+
+
 def _pairs(q_xy, t_xy, others, side_error, matches, valid, counts, ctx):
     """What the wrappers on image pairs share: the side of the call (q_xy's; t_xy and `others` must be on it), the
     context, the checked positions and their sizes, and the slot arguments."""
@@ -87,16 +121,10 @@ def verify_geometry(q_xy, t_xy, matches=None, valid=None, counts=None, model: st
         raise ValueError(f"model must be one of {sorted(MODELS)}")
     ctx, on_dev, pq, pt, b, s, ts, mi, v, cn = _pairs(
         q_xy, t_xy, (), "t_xy must be on the side (host / device) of q_xy", matches, valid, counts, ctx)
-    om, oi, oc, ob = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
-                             on_dev, pq.device if on_dev else None)
     (cx, cy), scale = conditioning(image_size)
     opts = fd_ransac_opts(MODELS[model], int(hypotheses), int(seed) & 0xFFFFFFFF, float(threshold), float(cx), float(cy),
                           float(scale))
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
-                               ptr(om), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return GeometryResult(om, oi, oc, ob)
+    return GeometryResult(*_call("fd_ransac", ctx, on_dev, pq, (b,), opts, (pq, cn, s, pt, ts, mi, v), _model_specs(b, s, 9), out))
 
 
 @dataclass
@@ -126,14 +154,10 @@ def refit_geometry(q_xy, t_xy, result: GeometryResult, matches=None, valid=None,
         q_xy, t_xy, (result.model, result.inliers), "t_xy and result must be on the side (host / device) of q_xy",
         matches, valid, counts, ctx)
     im, ii = slot_arg(result.model, "float64", (b, 9), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
-    om, oi, oc, orr = outputs((((b, 9), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
-                              on_dev, pq.device if on_dev else None)
     (cx, cy), scale = conditioning(image_size)
     opts = fd_refit_opts(MODELS[model], int(rounds), float(threshold), float(cx), float(cy), float(scale))
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_ransac_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
-                                     ptr(im), ptr(ii), ptr(om), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    om, oi, oc, orr = _call("fd_ransac_refit", ctx, on_dev, pq, (b,), opts, (pq, cn, s, pt, ts, mi, v, im, ii),
+                            _model_specs(b, s, 9), out)
     return RefitResult(om, oi, oc, result.best, orr)
 
 
@@ -205,12 +229,7 @@ def triangulate(q_xy, t_xy, pose, K, K_t=None, matches=None, valid=None, counts=
     """
     ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii = _pose_call(
         q_xy, t_xy, pose, "pose", 12, K, K_t, matches, valid, counts, inliers, max_depth, min_parallax, ctx)
-    op, ov, oc = outputs(POINT_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_triangulate(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v), ptr(gm),
-                                    ptr(ii), ptr(op), ptr(ov), ptr(oc), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return PointsResult(op, ov, oc)
+    return PointsResult(*_call("fd_triangulate", ctx, on_dev, pq, (b,), opts, (pq, cn, s, pt, ts, mi, v, gm, ii), POINT_SPECS(b, s), out))
 
 
 def recover_pose(q_xy, t_xy, result: GeometryResult, K, K_t=None, matches=None, valid=None, counts=None,
@@ -230,12 +249,8 @@ def recover_pose(q_xy, t_xy, result: GeometryResult, K, K_t=None, matches=None, 
     """
     ctx, on_dev, pq, pt, b, s, ts, opts, mi, v, cn, gm, ii = _pose_call(
         q_xy, t_xy, result.model, "result", 9, K, K_t, matches, valid, counts, result.inliers, max_depth, min_parallax, ctx)
-    oo, och, op, ov, oc = outputs((((b, 12), "float64", 0), ((b,), "int32", 0)) + POINT_SPECS(b, s), out, on_dev,
-                                  pq.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_pose_recover(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v), ptr(gm),
-                                     ptr(ii), ptr(oo), ptr(och), ptr(op), ptr(ov), ptr(oc), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    oo, och, op, ov, oc = _call("fd_pose_recover", ctx, on_dev, pq, (b,), opts, (pq, cn, s, pt, ts, mi, v, gm, ii),
+                                (((b, 12), "float64", 0), ((b,), "int32", 0)) + POINT_SPECS(b, s), out)
     return PoseResult(op, ov, oc, oo, och)
 
 
@@ -262,8 +277,7 @@ class PnpRefineResult(PnpResult):
 def _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, extra, ctx):
     """What solve_pnp and refine_pnp share: the checked arguments of the two entry points. `extra`: further
     arrays that must be on the side of t_xy."""
-    if isinstance(points, PointsResult):
-        points, point_valid = points.points, (points.valid if point_valid is None else point_valid)
+    points, point_valid = _unwrap(points, point_valid)
     on_dev = _is_torch_device_tensor(t_xy)
     sides = [_is_torch_device_tensor(points)] + [_is_torch_device_tensor(x) for x in extra]
     if point_valid is not None:
@@ -273,12 +287,7 @@ def _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, extra, ctx):
     ctx = _resolve_ctx(ctx, t_xy, points)
     pt = positions(t_xy, "t_xy", on_dev)
     b, ts = int(pt.shape[0]), int(pt.shape[1])
-    shape = tuple(points.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[2] != 3 or shape[0] != b:
-        raise ValueError("points must be float32 [B, S, 3] (or [S, 3] for batch 1) with t_xy's batch")
-    s = int(shape[1])
+    s = int(_xyz(points, "points", b, "t_xy's")[1])
     pp = slot_arg(points, "float32", (b, s, 3), on_dev)
     mi, v, cn = _slots(on_dev, b, s, ts, "points", matches, valid, counts)
     pv = slot_arg(point_valid, "uint8", (b, s), on_dev)
@@ -304,13 +313,7 @@ def solve_pnp(points, t_xy, K, matches=None, valid=None, point_valid=None, count
     ctx, on_dev, pp, pv, pt, b, s, ts, cam, mi, v, cn = _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, (), ctx)
     c3 = (0.0, 0.0, 0.0) if center is None else tuple(float(x) for x in np.asarray(center, np.float64).reshape(3))
     opts = fd_pnp_opts(int(hypotheses), int(seed) & 0xFFFFFFFF, 1, float(threshold), *cam, (ctypes.c_double * 3)(*c3), float(scale))
-    oo, oi, oc, ob = outputs((((b, 12), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
-                             on_dev, pt.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_pnp_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pp), ptr(pv), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
-                                   ptr(oo), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return PnpResult(oo, oi, oc, ob)
+    return PnpResult(*_call("fd_pnp_ransac", ctx, on_dev, pt, (b,), opts, (pp, pv, cn, s, pt, ts, mi, v), _model_specs(b, s, 12), out))
 
 
 def refine_pnp(points, t_xy, result: PnpResult, K, matches=None, valid=None, point_valid=None, counts=None, rounds: int = 4,
@@ -330,12 +333,8 @@ def refine_pnp(points, t_xy, result: PnpResult, K, matches=None, valid=None, poi
                                                                   (result.pose, result.inliers), ctx)
     ip, ii = slot_arg(result.pose, "float64", (b, 12), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
     opts = fd_pnp_opts(1, 0, int(rounds), float(threshold), *cam, (ctypes.c_double * 3)(0.0, 0.0, 0.0), 1.0)
-    oo, oi, oc, orr = outputs((((b, 12), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0)), out,
-                              on_dev, pt.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_pnp_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pp), ptr(pv), ptr(cn), s, ptr(pt), ts, ptr(mi), ptr(v),
-                                  ptr(ip), ptr(ii), ptr(oo), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    oo, oi, oc, orr = _call("fd_pnp_refit", ctx, on_dev, pt, (b,), opts, (pp, pv, cn, s, pt, ts, mi, v, ip, ii),
+                            _model_specs(b, s, 12), out)
     return PnpRefineResult(oo, oi, oc, result.best, orr)
 
 
@@ -391,8 +390,7 @@ def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, co
     inliers uint8 [B, C, O], counts int32 [B], cost float64 [B, 2], rounds int32 [B]) behave as in verify_geometry;
     out= may hold the given poses and points tensors themselves.
     """
-    if isinstance(points, PointsResult):
-        points, point_valid = points.points, (points.valid if point_valid is None else point_valid)
+    points, point_valid = _unwrap(points, point_valid)
     on_dev = _is_torch_device_tensor(obs_xy)
     poses = _stack_poses(poses, on_dev)
     if on_dev and isinstance(fixed, (list, tuple)):  # a few flags written out by hand
@@ -411,12 +409,7 @@ def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, co
         raise ValueError("obs_xy must be float32 [B, C, O, 2] (or [C, O, 2] for batch 1)")
     b, c, o = int(oshape[0]), int(oshape[1]), int(oshape[2])
     po = f32(obs_xy, "obs_xy", on_dev).reshape(oshape)
-    pshape = tuple(points.shape)
-    if len(pshape) == 2:
-        pshape = (1,) + pshape
-    if len(pshape) != 3 or pshape[2] != 3 or pshape[0] != b:
-        raise ValueError("points must be float32 [B, S, 3] (or [S, 3] for batch 1) with obs_xy's batch")
-    s = int(pshape[1])
+    s = int(_xyz(points, "points", b, "obs_xy's")[1])
     if o < s:
         raise ValueError("slot i of a camera observes point i: obs_xy needs at least as many slots as points")
     if tuple(poses.shape) != (b, c, 12):
@@ -426,18 +419,12 @@ def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, co
     ov, pv = slot_arg(obs_valid, "uint8", (b, c, o), on_dev), slot_arg(point_valid, "uint8", (b, s), on_dev)
     cn, fx = slot_arg(counts, "int32", (b,), on_dev), slot_arg(fixed, "uint8", (b, c), on_dev)
     opts = fd_ba_opts(int(rounds), float(threshold), *intrinsics(K), float(lam), float(up), float(down))
-    oo, opn, oi, oc, ocs, orr = outputs((((b, c, 12), "float64", 0), ((b, s, 3), "float32", 0), ((b, c, o), "uint8", 0),
-                                         ((b,), "int32", 0), ((b, 2), "float64", 0), ((b,), "int32", 0)), out, on_dev,
-                                        po.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_bundle_adjust(ctx.ptr, b, c, ctypes.byref(opts), ptr(ip), ptr(fx), ptr(pp), ptr(pv), ptr(cn), s, ptr(po),
-                                      ptr(ov), o, ptr(oo), ptr(opn), ptr(oi), ptr(oc), ptr(ocs), ptr(orr), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return BundleResult(oo, opn, oi, oc, ocs, orr)
+    specs = (((b, c, 12), "float64", 0), ((b, s, 3), "float32", 0), ((b, c, o), "uint8", 0), ((b,), "int32", 0),
+             ((b, 2), "float64", 0), ((b,), "int32", 0))
+    return BundleResult(*_call("fd_bundle_adjust", ctx, on_dev, po, (b, c), opts, (ip, fx, pp, pv, cn, s, po, ov, o), specs, out))
 
 
 ALIGN_KINDS = {"similarity": _lib.FD_ALIGN_SIMILARITY, "rigid": _lib.FD_ALIGN_RIGID}
-MODEL_SPECS = lambda b, s: (((b, 13), "float64", 0), ((b, s), "uint8", 0), ((b,), "int32", 0), ((b,), "int32", 0))  # noqa: E731
 
 
 @dataclass
@@ -463,25 +450,12 @@ class AlignRefineResult(AlignResult):
     rounds: object = None  # int32 [B]: accepted refit rounds; 0: model and inliers are the given ones
 
 
-def _xyz(x, name, b=None):
-    """The [B, S, 3] shape of a point array ([S, 3]: batch 1), checked against the batch b."""
-    shape = tuple(x.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or shape[2] != 3 or (b is not None and shape[0] != b):
-        raise ValueError(f"{name} must be float32 [B, S, 3] (or [S, 3] for batch 1)" + ("" if b is None else " with the call's batch"))
-    return shape
-
-
 def _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind, extra, ctx):
     """What align_points and refine_alignment share: the checked arguments of the two entry points. `extra`: further
     arrays that must be on the side of q_xyz."""
     if kind not in ALIGN_KINDS:
         raise ValueError(f"kind must be one of {sorted(ALIGN_KINDS)}")
-    if isinstance(q_xyz, PointsResult):
-        q_xyz, q_valid = q_xyz.points, (q_xyz.valid if q_valid is None else q_valid)
-    if isinstance(t_xyz, PointsResult):
-        t_xyz, t_valid = t_xyz.points, (t_xyz.valid if t_valid is None else t_valid)
+    (q_xyz, q_valid), (t_xyz, t_valid) = _unwrap(q_xyz, q_valid), _unwrap(t_xyz, t_valid)
     on_dev = _is_torch_device_tensor(q_xyz)
     others = [t_xyz, *extra] + [x for x in (q_valid, t_valid) if x is not None]
     if any(_is_torch_device_tensor(x) != on_dev for x in others):
@@ -515,12 +489,7 @@ def align_points(q_xyz, t_xyz, matches=None, valid=None, q_valid=None, t_valid=N
     ctx, on_dev, pq, qv, pt, tv, b, s, t, mi, v, cn = _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind,
                                                                   (), ctx)
     opts = fd_align_opts(ALIGN_KINDS[kind], int(hypotheses), int(seed) & 0xFFFFFFFF, 1, float(threshold))
-    om, oi, oc, ob = outputs(MODEL_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_align_ransac(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(qv), ptr(cn), s, ptr(pt), ptr(tv), t, ptr(mi),
-                                     ptr(v), ptr(om), ptr(oi), ptr(oc), ptr(ob), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return AlignResult(om, oi, oc, ob)
+    return AlignResult(*_call("fd_align_ransac", ctx, on_dev, pq, (b,), opts, (pq, qv, cn, s, pt, tv, t, mi, v), _model_specs(b, s, 13), out))
 
 
 def refine_alignment(q_xyz, t_xyz, result: AlignResult, matches=None, valid=None, q_valid=None, t_valid=None, counts=None,
@@ -542,11 +511,8 @@ def refine_alignment(q_xyz, t_xyz, result: AlignResult, matches=None, valid=None
                                                                   (result.model, result.inliers), ctx)
     im, ii = slot_arg(result.model, "float64", (b, 13), on_dev), slot_arg(result.inliers, "uint8", (b, s), on_dev)
     opts = fd_align_opts(ALIGN_KINDS[kind], 1, 0, int(rounds), float(threshold))
-    om, oi, oc, orr = outputs(MODEL_SPECS(b, s), out, on_dev, pq.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_align_refit(ctx.ptr, b, ctypes.byref(opts), ptr(pq), ptr(qv), ptr(cn), s, ptr(pt), ptr(tv), t, ptr(mi),
-                                    ptr(v), ptr(im), ptr(ii), ptr(om), ptr(oi), ptr(oc), ptr(orr), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    om, oi, oc, orr = _call("fd_align_refit", ctx, on_dev, pq, (b,), opts, (pq, qv, cn, s, pt, tv, t, mi, v, im, ii),
+                            _model_specs(b, s, 13), out)
     return AlignRefineResult(om, oi, oc, result.best, orr)
 
 
@@ -561,8 +527,7 @@ def transform_points(model, xyz, valid=None, counts=None, out=None, ctx: Context
     a preallocated contiguous float32 [B, S, 3] tensor, of which the transformed slots alone are written; out may be
     xyz itself (in place; kernels only, graph-capturable).
     """
-    if isinstance(xyz, PointsResult):
-        xyz, valid = xyz.points, (xyz.valid if valid is None else valid)
+    xyz, valid = _unwrap(xyz, valid)
     model = getattr(model, "model", model)
     on_dev = _is_torch_device_tensor(xyz)
     if _is_torch_device_tensor(model) != on_dev or any(_is_torch_device_tensor(x) != on_dev for x in (valid, counts) if x is not None):
