@@ -3,10 +3,10 @@
 Layers:
   include/fd_hip.h          C ABI (libfdhip.so: gfx950 HIP kernels + runtime)
   include/feature_detector/ C++ classes with the reference's API (libfeature_detector.so)
-  feature_detector_amd      Python batch API over the C ABI (this package), used by tests and bench.py
+  feature_detector_amd      Python batch API over the C ABI (this package: _lib, _context, _slots, one module per stage)
 """
 from ._lib import FD_FAST, FD_HARRIS, FD_SHI_TOMASI, FdError, LIB_PATH, load  # noqa: F401
-from .points import Context, DetectResult, default_context, detect_points, lsd_lines, lsd_map, point_candidates, point_response, select_points  # noqa: F401
+from .points import Context, DetectResult, default_context, detect_points, point_candidates, point_response, select_points  # noqa: F401
 from .descriptor import brief_compute, to_float, unpack_bits  # noqa: F401
 from .match import MatchResult, brief_match, nn_match  # noqa: F401
 from .flow import FlowResult, Pyramid, build_pyramid, pyramid_layout, track_lk  # noqa: F401
@@ -17,7 +17,7 @@ from .geometry import (AlignRefineResult, AlignResult, BundleResult, GeometryRes
 from .warp import camera_params, warp_frames  # noqa: F401
 from .equalize import equalize_frames  # noqa: F401
 from .blur import blur_frames, gaussian_taps  # noqa: F401
-from .lines import LineDescResult, describe_lines  # noqa: F401
+from .lines import LineDescResult, describe_lines, lsd_lines, lsd_map  # noqa: F401
 from .ingest import Ingest, load_png, png_frames, png_info  # noqa: F401
 
 __all__ = [

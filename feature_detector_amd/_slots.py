@@ -1,6 +1,6 @@
-"""Arguments of the keypoint stages as the C ABI takes them: [batch][stride] slot arrays with optional
-counts [batch] and valid [batch][stride], on the host (numpy) or on the device (torch), and their outputs.
-Shared by descriptor.py, match.py, flow.py, refine.py and geometry.py.
+"""Arguments of the stages as the C ABI takes them: pointers, [batch][stride] slot arrays with optional counts [batch]
+and valid [batch][stride], on the host (numpy) or on the device (torch), and the outputs of a call.
+Shared by every module that hands arrays to the library (ptr); the slot helpers by descriptor, match, flow, refine, geometry, lines, warp.
 """
 from __future__ import annotations
 

@@ -9,12 +9,10 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
-
 from . import _lib
 from ._lib import FD_BLUR_MAX_RADIUS, fd_blur_opts
 from ._slots import ptr
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, frame_output, invoke, resolve_ctx
 
 
 def gaussian_taps(sigma: float, radius: int | None = None) -> tuple[int, list[int]]:
@@ -60,34 +58,15 @@ def blur_frames(frames, sigma=None, radius=None, taps=None, step=1, out=None, ct
     or tensor of the output's shape on the frames' side; it must not be frames (there is no in-place blur).
     Options the library rejects (radius, tap sum, step) raise FdError.
     """
-    fptr, f_dev, b, rows, cols, keep = _frames(frames)
+    _, f_dev, b, rows, cols, keep = as_frames(frames)
     if rows < 1 or cols < 1 or b < 1:
         raise ValueError("frames must not be empty")
     opts = _options(sigma, radius, taps, step)
     on_dev = bool(f_dev)
     s = 2 if opts.step == 2 else 1  # (any other step is refused by the library)
     shape = tuple(keep.shape[:-2]) + ((rows + s - 1) // s, (cols + s - 1) // s)
-    if out is None:
-        if on_dev:
-            import torch
-
-            out = torch.empty(shape, dtype=torch.uint8, device=keep.device)
-        else:
-            out = np.empty(shape, np.uint8)
-    else:
-        if _is_torch_device_tensor(out) != on_dev:
-            raise ValueError("out must be on the side of the frames")
-        if on_dev:
-            import torch
-
-            ok = out.dtype == torch.uint8 and out.is_contiguous()
-        else:
-            ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
-        if not ok or tuple(out.shape) != shape:
-            raise ValueError(f"out must be a contiguous uint8 array of shape {shape}")
-    ctx = _resolve_ctx(ctx, keep, out)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_frames_blur(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(out),
-                                    1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    out = frame_output(shape, "uint8", on_dev, keep.device if on_dev else None, out,
+                       f"out must be a contiguous uint8 array of shape {shape}")
+    ctx = resolve_ctx(ctx, keep, out)
+    invoke(ctx, on_dev, "fd_frames_blur", ptr(keep), f_dev, b, rows, cols, ctypes.byref(opts), ptr(out), 1 if on_dev else 0)
     return out

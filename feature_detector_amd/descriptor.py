@@ -12,10 +12,9 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
 from ._lib import FD_SAMPLE_BILINEAR, FD_SAMPLE_TRUNCATE, fd_brief_opts
 from ._slots import outputs, positions, ptr, slot_arg
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, invoke, is_device_tensor, resolve_ctx
 
 SAMPLERS = {"bilinear": FD_SAMPLE_BILINEAR, "truncate": FD_SAMPLE_TRUNCATE}
 
@@ -33,11 +32,11 @@ def brief_compute(frames, uv, counts=None, length: int = 256, half_patch_size: i
     call is the kernel alone (graph-capturable without an allocation or fill).
     """
     smp = SAMPLERS[sampler] if isinstance(sampler, str) else int(sampler)
-    fptr, f_on_dev, b, r, c, keep_f = _frames(frames)
-    ctx = _resolve_ctx(ctx, frames, uv)
+    _, f_on_dev, b, r, c, keep_f = as_frames(frames)
+    ctx = resolve_ctx(ctx, frames, uv)
     nw = (int(length) + 31) // 32
     opts = fd_brief_opts(int(length), int(half_patch_size), smp)
-    on_dev = _is_torch_device_tensor(uv)
+    on_dev = is_device_tensor(uv)
     msg = "uv must be [batch, S, 2] matching frames"
     puv = positions(uv, "uv", on_dev, convert=True, msg=msg)
     if puv.shape[0] != b:
@@ -49,11 +48,8 @@ def brief_compute(frames, uv, counts=None, length: int = 256, half_patch_size: i
     bits, = outputs([((b, s, nw), "int32" if on_dev else "uint32", 0)], (out,) if on_dev and out is not None else None,
                     on_dev, dev, f"out must be a contiguous int32 tensor of shape {(b, s, nw)}")
     valid = outputs([((b, s), "uint8", 0)], None, on_dev, dev)[0] if with_valid else None
-    _bind_stream(ctx, on_dev or bool(f_on_dev))
-    rc = _lib.load().fd_brief_compute(ctx.ptr, ctypes.c_void_p(fptr), f_on_dev, b, r, c, ctypes.byref(opts), ptr(puv), ptr(cn),
-                                      s, ptr(bits), ptr(valid), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    del keep_f
+    invoke(ctx, on_dev or bool(f_on_dev), "fd_brief_compute", ptr(keep_f), f_on_dev, b, r, c, ctypes.byref(opts), ptr(puv), ptr(cn),
+           s, ptr(bits), ptr(valid), 1 if on_dev else 0)
     return (bits, valid) if with_valid else bits
 
 

@@ -11,10 +11,9 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
 from ._lib import fd_equalize_opts
 from ._slots import ptr
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, frame_output, invoke, resolve_ctx
 
 MAX_TILES = 32
 MAX_TILE_AREA = 1 << 24
@@ -50,34 +49,15 @@ def equalize_frames(frames, tiles=(8, 8), clip_limit=3.0, out=None, ctx: Context
     run), numpy otherwise. out: a preallocated contiguous uint8 array or tensor of the frames' shape on the
     frames' side; it may be frames itself (in place).
     """
-    fptr, f_dev, b, rows, cols, keep = _frames(frames)
+    _, f_dev, b, rows, cols, keep = as_frames(frames)
     if rows < 1 or cols < 1 or b < 1:
         raise ValueError("frames must not be empty")
     tiles_x, tiles_y, clip_milli = _options(tiles, clip_limit, rows, cols)
     on_dev = bool(f_dev)
     shape = tuple(keep.shape)
-    if out is None:
-        if on_dev:
-            import torch
-
-            out = torch.empty(shape, dtype=torch.uint8, device=keep.device)
-        else:
-            out = np.empty(shape, np.uint8)
-    else:
-        if _is_torch_device_tensor(out) != on_dev:
-            raise ValueError("out must be on the side of the frames")
-        if on_dev:
-            import torch
-
-            ok = out.dtype == torch.uint8 and out.is_contiguous()
-        else:
-            ok = isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
-        if not ok or tuple(out.shape) != shape:
-            raise ValueError(f"out must be a contiguous uint8 array of shape {shape}")
-    ctx = _resolve_ctx(ctx, keep, out)
+    out = frame_output(shape, "uint8", on_dev, keep.device if on_dev else None, out,
+                       f"out must be a contiguous uint8 array of shape {shape}")
+    ctx = resolve_ctx(ctx, keep, out)
     opts = fd_equalize_opts(tiles_x, tiles_y, clip_milli)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_frames_equalize(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(out),
-                                        1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev, "fd_frames_equalize", ptr(keep), f_dev, b, rows, cols, ctypes.byref(opts), ptr(out), 1 if on_dev else 0)
     return out

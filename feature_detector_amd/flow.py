@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import fd_flow_opts
 from ._slots import f32, outputs, positions, ptr, slot_arg
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, invoke, is_device_tensor, resolve_ctx
 
 
 def pyramid_layout(batch: int, rows: int, cols: int, levels: int) -> list[int]:
@@ -56,8 +56,8 @@ def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_ou
     """
     if kernel not in ("box", "gauss"):
         raise ValueError('kernel must be "box" or "gauss"')
-    fptr, on_dev, b, r, c, keep = _frames(frames)
-    ctx = _resolve_ctx(ctx, frames)
+    _, on_dev, b, r, c, keep = as_frames(frames)
+    ctx = resolve_ctx(ctx, frames)
     off = pyramid_layout(b, r, c, levels)
     dev_out = bool(on_dev) if device_out is None else bool(device_out)
     if on_dev and not dev_out:
@@ -68,10 +68,8 @@ def build_pyramid(frames, levels: int = 3, ctx: Context | None = None, device_ou
         data = torch.empty((off[-1],), dtype=torch.uint8, device=keep.device if on_dev else f"cuda:{ctx.device}")
     else:
         data = np.zeros((off[-1],), np.uint8)
-    _bind_stream(ctx, bool(on_dev))
-    build = _lib.load().fd_pyr_build_gauss if kernel == "gauss" else _lib.load().fd_pyr_build
-    rc = build(ctx.ptr, ctypes.c_void_p(fptr), on_dev, b, r, c, int(levels), ptr(data), 1 if dev_out else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, bool(on_dev), "fd_pyr_build_gauss" if kernel == "gauss" else "fd_pyr_build", ptr(keep), on_dev, b, r, c, int(levels),
+           ptr(data), 1 if dev_out else 0)
     return Pyramid(data, b, r, c, int(levels), off)
 
 
@@ -88,7 +86,7 @@ def _device_pyramid(p, levels, ctx, name):
     if isinstance(p, Pyramid):
         if p.levels != int(levels):
             raise ValueError(f"{name}: the pyramid has {p.levels} levels, the call asks for {levels}")
-        if _is_torch_device_tensor(p.data):
+        if is_device_tensor(p.data):
             return p
         import torch
 
@@ -117,8 +115,8 @@ def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 
     conventions of pyramidal LK front ends, not values tuned for this library. fb_max_dist >= 0 turns the
     forward-backward check on (a second pass), max_error >= 0 the residual test.
     """
-    on_dev = _is_torch_device_tensor(xy)
-    ctx = _resolve_ctx(ctx, xy, prev.data if isinstance(prev, Pyramid) else prev,
+    on_dev = is_device_tensor(xy)
+    ctx = resolve_ctx(ctx, xy, prev.data if isinstance(prev, Pyramid) else prev,
                        next.data if isinstance(next, Pyramid) else next)
     pxy = positions(xy, "xy", on_dev)
     b, s = int(pxy.shape[0]), int(pxy.shape[1])
@@ -127,7 +125,7 @@ def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 
         raise ValueError("prev and next must have the same batch, rows and cols")
     if pp.batch != b:
         raise ValueError("xy and the frames must have the same batch")
-    if guess is not None and _is_torch_device_tensor(guess) != on_dev:
+    if guess is not None and is_device_tensor(guess) != on_dev:
         raise ValueError("guess must be on the side (host / device) of xy")
     v, cn = slot_arg(valid, "uint8", (b, s), on_dev), slot_arg(counts, "int32", (b,), on_dev)
     g = None if guess is None else f32(guess, "guess", on_dev).reshape(b, s, 2)
@@ -135,9 +133,6 @@ def track_lk(prev, next, xy, counts=None, valid=None, guess=None, levels: int = 
                                     ((b,), "int32", 0)), out, on_dev, pxy.device if on_dev else None)
     opts = fd_flow_opts(int(half_window), int(max_iters), float(epsilon), float(min_eigen), float(fb_max_dist),
                         float(max_error))
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_flow_lk(ctx.ptr, b, pp.rows, pp.cols, int(levels), ctypes.byref(opts), ptr(pp.data), ptr(pn.data),
-                                ptr(pxy), ptr(v), ptr(cn), s, ptr(g), ptr(oxy), ptr(ost), ptr(oerr), ptr(ocnt),
-                                1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev, "fd_flow_lk", b, pp.rows, pp.cols, int(levels), ctypes.byref(opts), ptr(pp.data), ptr(pn.data),
+           ptr(pxy), ptr(v), ptr(cn), s, ptr(g), ptr(oxy), ptr(ost), ptr(oerr), ptr(ocnt), 1 if on_dev else 0)
     return FlowResult(oxy, ost, oerr, ocnt)

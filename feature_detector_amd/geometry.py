@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import fd_align_opts, fd_ba_opts, fd_pnp_opts, fd_pose_opts, fd_ransac_opts, fd_refit_opts
 from ._slots import f32, outputs, positions, ptr, slot_arg
-from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, invoke, is_device_tensor, resolve_ctx
 
 MODELS = {"fundamental": _lib.FD_RANSAC_FUNDAMENTAL, "homography": _lib.FD_RANSAC_HOMOGRAPHY}
 
@@ -53,10 +53,8 @@ def _call(fn, ctx, on_dev, like, head, opts, inputs, specs, out):
     context's stream, the C function `fn` on (ctx, *head, opts, *inputs, *outputs, io_on_device) and its status. head: the
     batch (and cameras); inputs: arrays (None: a null pointer) and the strides between them. Returns the outputs."""
     outs = outputs(specs, out, on_dev, like.device if on_dev else None)
-    _bind_stream(ctx, on_dev)
     args = [x if isinstance(x, int) else ptr(x) for x in (*inputs, *outs)]
-    rc = getattr(_lib.load(), fn)(ctx.ptr, *head, ctypes.byref(opts), *args, 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev, fn, *head, ctypes.byref(opts), *args, 1 if on_dev else 0)
     return outs
 
 
@@ -85,10 +83,10 @@ def _xyz(x, name, b=None, whose=None):
 def _pairs(q_xy, t_xy, others, side_error, matches, valid, counts, ctx):
     """What the wrappers on image pairs share: the side of the call (q_xy's; t_xy and `others` must be on it), the
     context, the checked positions and their sizes, and the slot arguments."""
-    on_dev = _is_torch_device_tensor(q_xy)
-    if any(_is_torch_device_tensor(x) != on_dev for x in (t_xy, *others)):
+    on_dev = is_device_tensor(q_xy)
+    if any(is_device_tensor(x) != on_dev for x in (t_xy, *others)):
         raise ValueError(side_error)
-    ctx = _resolve_ctx(ctx, q_xy, t_xy)
+    ctx = resolve_ctx(ctx, q_xy, t_xy)
     pq, pt = positions(q_xy, "q_xy", on_dev), positions(t_xy, "t_xy", on_dev)
     b, s, ts = int(pq.shape[0]), int(pq.shape[1]), int(pt.shape[1])
     if int(pt.shape[0]) != b:
@@ -278,13 +276,13 @@ def _pnp_call(points, t_xy, K, matches, valid, point_valid, counts, extra, ctx):
     """What solve_pnp and refine_pnp share: the checked arguments of the two entry points. `extra`: further
     arrays that must be on the side of t_xy."""
     points, point_valid = _unwrap(points, point_valid)
-    on_dev = _is_torch_device_tensor(t_xy)
-    sides = [_is_torch_device_tensor(points)] + [_is_torch_device_tensor(x) for x in extra]
+    on_dev = is_device_tensor(t_xy)
+    sides = [is_device_tensor(points)] + [is_device_tensor(x) for x in extra]
     if point_valid is not None:
-        sides.append(_is_torch_device_tensor(point_valid))
+        sides.append(is_device_tensor(point_valid))
     if any(side != on_dev for side in sides):
         raise ValueError("points, point_valid and the given result must be on the side (host / device) of t_xy")
-    ctx = _resolve_ctx(ctx, t_xy, points)
+    ctx = resolve_ctx(ctx, t_xy, points)
     pt = positions(t_xy, "t_xy", on_dev)
     b, ts = int(pt.shape[0]), int(pt.shape[1])
     s = int(_xyz(points, "points", b, "t_xy's")[1])
@@ -391,17 +389,17 @@ def bundle_adjust(poses, points, obs_xy, K, obs_valid=None, point_valid=None, co
     out= may hold the given poses and points tensors themselves.
     """
     points, point_valid = _unwrap(points, point_valid)
-    on_dev = _is_torch_device_tensor(obs_xy)
+    on_dev = is_device_tensor(obs_xy)
     poses = _stack_poses(poses, on_dev)
     if on_dev and isinstance(fixed, (list, tuple)):  # a few flags written out by hand
         import torch
 
         fixed = torch.tensor(fixed, dtype=torch.uint8, device=obs_xy.device)
-    sides = [_is_torch_device_tensor(points), _is_torch_device_tensor(poses)]
-    sides += [_is_torch_device_tensor(x) for x in (obs_valid, point_valid, counts, fixed) if x is not None]
+    sides = [is_device_tensor(points), is_device_tensor(poses)]
+    sides += [is_device_tensor(x) for x in (obs_valid, point_valid, counts, fixed) if x is not None]
     if any(side != on_dev for side in sides):
         raise ValueError("poses, points and the masks must be on the side (host / device) of obs_xy")
-    ctx = _resolve_ctx(ctx, obs_xy, points)
+    ctx = resolve_ctx(ctx, obs_xy, points)
     oshape = tuple(obs_xy.shape)
     if len(oshape) == 3:
         oshape = (1,) + oshape
@@ -456,11 +454,11 @@ def _align_call(q_xyz, t_xyz, matches, valid, q_valid, t_valid, counts, kind, ex
     if kind not in ALIGN_KINDS:
         raise ValueError(f"kind must be one of {sorted(ALIGN_KINDS)}")
     (q_xyz, q_valid), (t_xyz, t_valid) = _unwrap(q_xyz, q_valid), _unwrap(t_xyz, t_valid)
-    on_dev = _is_torch_device_tensor(q_xyz)
+    on_dev = is_device_tensor(q_xyz)
     others = [t_xyz, *extra] + [x for x in (q_valid, t_valid) if x is not None]
-    if any(_is_torch_device_tensor(x) != on_dev for x in others):
+    if any(is_device_tensor(x) != on_dev for x in others):
         raise ValueError("t_xyz, the masks and the given result must be on the side (host / device) of q_xyz")
-    ctx = _resolve_ctx(ctx, q_xyz, t_xyz)
+    ctx = resolve_ctx(ctx, q_xyz, t_xyz)
     qs, ts = _xyz(q_xyz, "q_xyz"), _xyz(t_xyz, "t_xyz")
     b, s, t = int(qs[0]), int(qs[1]), int(ts[1])
     if ts[0] != b:
@@ -529,10 +527,10 @@ def transform_points(model, xyz, valid=None, counts=None, out=None, ctx: Context
     """
     xyz, valid = _unwrap(xyz, valid)
     model = getattr(model, "model", model)
-    on_dev = _is_torch_device_tensor(xyz)
-    if _is_torch_device_tensor(model) != on_dev or any(_is_torch_device_tensor(x) != on_dev for x in (valid, counts) if x is not None):
+    on_dev = is_device_tensor(xyz)
+    if is_device_tensor(model) != on_dev or any(is_device_tensor(x) != on_dev for x in (valid, counts) if x is not None):
         raise ValueError("model, valid and counts must be on the side (host / device) of xyz")
-    ctx = _resolve_ctx(ctx, xyz, xyz)
+    ctx = resolve_ctx(ctx, xyz, xyz)
     shape = _xyz(xyz, "xyz")
     b, s = int(shape[0]), int(shape[1])
     px = f32(xyz, "xyz", on_dev).reshape(shape)
@@ -542,9 +540,7 @@ def transform_points(model, xyz, valid=None, counts=None, out=None, ctx: Context
         res = px.clone() if on_dev else px.copy()
     else:
         (res,) = outputs(((shape, "float32", 0),), (out,), on_dev)
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_align_apply(ctx.ptr, b, ptr(pm), ptr(px), ptr(pv), ptr(cn), s, ptr(res), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev, "fd_align_apply", b, ptr(pm), ptr(px), ptr(pv), ptr(cn), s, ptr(res), 1 if on_dev else 0)
     return res
 
 

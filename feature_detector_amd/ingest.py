@@ -14,7 +14,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import fd_point_opts
-from .points import KINDS, Context
+from ._context import Context, default_context, invoke
+from ._slots import ptr
+from .points import KINDS
 
 
 class Ingest:
@@ -85,7 +87,7 @@ def load_png(path_or_bytes) -> np.ndarray:
     rows, cols, _ = png_info(data)
     out = np.empty((rows, cols), np.uint8)
     r, c = ctypes.c_int32(), ctypes.c_int32()
-    rc = _lib.load().fd_png_decode(data, len(data), ctypes.c_void_p(out.ctypes.data), out.size, ctypes.byref(r),
+    rc = _lib.load().fd_png_decode(data, len(data), ptr(out), out.size, ctypes.byref(r),
                                    ctypes.byref(c))
     if rc:
         raise _lib.FdError(rc, "PNG decode failed")
@@ -98,12 +100,9 @@ def png_frames(images, threads: int = 0, ctx: Context | None = None, out=None):
     gray on the GPU), stream-ordered on torch's current stream."""
     import torch
 
-    from .points import _bind_stream, default_context
-
     images = [bytes(x) for x in images]
     rows, cols, _ = png_info(images[0])
     ctx = ctx or default_context(torch.cuda.current_device())
-    _bind_stream(ctx, True)
     n = len(images)
     if out is None:
         out = torch.empty((n, rows, cols), dtype=torch.uint8, device=f"cuda:{ctx.device}")
@@ -113,7 +112,6 @@ def png_frames(images, threads: int = 0, ctx: Context | None = None, out=None):
                          f"{(n, rows, cols)}, got {tuple(out.shape)} {out.dtype} on {out.device}")
     bufs = (ctypes.c_char_p * n)(*images)
     lens = (ctypes.c_size_t * n)(*[len(x) for x in images])
-    rc = _lib.load().fd_png_frames(ctx.ptr, ctypes.cast(bufs, ctypes.c_void_p), ctypes.cast(lens, ctypes.c_void_p), n,
-                                   rows, cols, ctypes.c_void_p(out.data_ptr()), int(threads))
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, True, "fd_png_frames", ctypes.cast(bufs, ctypes.c_void_p), ctypes.cast(lens, ctypes.c_void_p), n, rows, cols,
+           ptr(out), int(threads))
     return out

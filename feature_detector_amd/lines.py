@@ -1,6 +1,7 @@
-"""Line band descriptor over the C ABI (fd_lines_describe).
+"""The line stage over the C ABI: the level-line map (fd_lsd_map), the LSD segments (fd_lsd_lines) and their band
+descriptor (fd_lines_describe).
 
-An MI355X extension (the reference's line path stops at the rectangles): the stage between lsd_lines and
+The descriptor is an MI355X extension (the reference's line path stops at the rectangles): the stage between lsd_lines and
 nn_match, so that the segments of two frames can be matched, unguided or by their midpoints, with the matchers
 as they are. The arithmetic (integer gradient sums per row of the support region, band statistics and norms in
 double) is in include/fd_hip.h.
@@ -15,7 +16,81 @@ import numpy as np
 from . import _lib
 from ._lib import fd_line_desc_opts
 from ._slots import f32, outputs, ptr, slot_arg
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, invoke, is_device_tensor, resolve_ctx
+
+
+def lsd_map(frames, min_norm: float = 20.0, cap: int | None = None, ctx: Context | None = None, out=None):
+    """ComputeLineLevelAngleMap (fd_lsd_map / fd_lsd_map_pitched).
+
+    Host (numpy) frames: returns per frame (norm, angle, valid, valid_idx_colmajor); maps are
+    (rows-1, cols-1). Torch device frames: returns device tensors (norm [B, R-1, C-1] f32, angle f32,
+    valid u8, valid_idx int32 [B, cap], counts int64 [B]), asynchronous on torch's current stream;
+    the maps are views of storage whose rows are padded to 16 entries (aligned row stores); `out` may
+    pass them preallocated (graph capture), contiguous or as such row-padded views sharing one row
+    pitch; any of norm/angle/valid may be None to skip.
+    """
+    _, on_dev, b, r, c, keep = as_frames(frames)
+    ctx = resolve_ctx(ctx, frames)
+    mr, mc = r - 1, c - 1
+    cap = mr * mc if cap is None else cap
+    if on_dev:
+        import torch
+
+        if out is None:
+            dev = frames.device
+            pitch = (mc + 15) // 16 * 16
+            out = (torch.empty((b, mr, pitch), dtype=torch.float32, device=dev)[..., :mc],
+                   torch.empty((b, mr, pitch), dtype=torch.float32, device=dev)[..., :mc],
+                   torch.empty((b, mr, pitch), dtype=torch.uint8, device=dev)[..., :mc],
+                   torch.empty((b, max(cap, 1)), dtype=torch.int32, device=dev),
+                   torch.empty((b,), dtype=torch.int64, device=dev))
+        norm, ang, val, idx, cnt = out
+        pitch = None
+        for t in (norm, ang, val):
+            if t is None:
+                continue
+            if tuple(t.shape) != (b, mr, mc) or t.stride(2) != 1 or t.stride(0) != mr * t.stride(1):
+                raise ValueError(f"lsd_map: maps must be [{b}, {mr}, {mc}] with unit column stride and rows "
+                                 "packed at one pitch")
+            if pitch not in (None, t.stride(1)):
+                raise ValueError("lsd_map: norm / angle / valid must share one row pitch")
+            pitch = t.stride(1)
+        pitch = mc if pitch is None else pitch
+        invoke(ctx, True, "fd_lsd_map_pitched", ptr(keep), 1, b, r, c, float(min_norm), ptr(norm), ptr(ang), ptr(val),
+               int(pitch), ptr(idx), int(idx.shape[1]), ptr(cnt), 1)
+        return out
+    norm = np.zeros((b, mr, mc), np.float32)
+    ang = np.zeros((b, mr, mc), np.float32)
+    val = np.zeros((b, mr, mc), np.uint8)
+    idx = np.zeros((b, max(cap, 1)), np.int32)
+    cnt = np.zeros((b,), np.int64)
+    invoke(ctx, False, "fd_lsd_map", ptr(keep), 0, b, r, c, float(min_norm), ptr(norm), ptr(ang), ptr(val), ptr(idx), int(cap),
+           ptr(cnt), 0)
+    return [(norm[i], ang[i], val[i], idx[i, :cnt[i]].copy()) for i in range(b)]
+
+
+# FeatureLineDetector::Options defaults (feature_line_detector.h:40-45); kDegToRad = kPai / 180 in float.
+LSD_TOL_RAD = float(np.float32(22.5) * (np.float32(3.14159265358979323846) / np.float32(180.0)))
+
+
+def lsd_lines(frames, needed: int = 1, min_norm: float = 20.0, tol_rad: float = LSD_TOL_RAD, min_length: float = 20.0,
+              min_inlier: float = 0.6, max_lines: int = 4096, threads: int = 0, ctx: Context | None = None):
+    """FeatureLineDetector::DetectGoodFeatures for a batch (fd_lsd_lines): GPU level-line map (compact
+    lists), region growing and rectangle fitting on `threads` host threads (0: all, capped by
+    OMP_NUM_THREADS). frames: numpy [B, R, C] / [R, C] u8 or a torch device tensor.
+
+    Returns a list over frames of float32 arrays [n, 12] (start x, y, end x, y, center x, y, length,
+    width, angle, dir x, y, inlier ratio); columns 0-3 are the reference's Vec4 features."""
+    _, on_dev, b, r, c, keep = as_frames(frames)
+    ctx = resolve_ctx(ctx, frames)
+    opts = _lib.fd_lsd_opts(float(min_norm), float(tol_rad), float(min_length), float(min_inlier))
+    out = np.empty((b, max(max_lines, 1), _lib.LSD_RECT_FLOATS), np.float32)
+    cnt = np.zeros((b,), np.int32)
+    invoke(ctx, on_dev, "fd_lsd_lines", ptr(keep), 1 if on_dev else 0, b, r, c, ctypes.byref(opts), int(needed), ptr(out),
+           int(max_lines), ptr(cnt), int(threads))
+    if (cnt > max_lines).any():
+        raise _lib.FdError(_lib.FD_ERR_CAPACITY, f"max_lines={max_lines} < {int(cnt.max())} segments found")
+    return [out[i, :cnt[i]].copy() for i in range(b)]
 
 
 @dataclass
@@ -60,13 +135,13 @@ def describe_lines(frames, lines, counts=None, bands: int = 9, band_width: int =
     [B, S, 2], valid uint8 [B, S]); slots past a count then keep their contents, and with device frames the
     call is one kernel (graph-capturable).
     """
-    fptr, f_dev, b, rows, cols, keep = _frames(frames)
+    _, f_dev, b, rows, cols, keep = as_frames(frames)
     if isinstance(lines, (list, tuple)):
         if counts is not None:
             raise ValueError("a list of lines carries its own counts")
         lines, counts = _padded(lines)
-    on_dev = _is_torch_device_tensor(lines)
-    ctx = _resolve_ctx(ctx, lines, keep)
+    on_dev = is_device_tensor(lines)
+    ctx = resolve_ctx(ctx, lines, keep)
     ln = f32(lines, "lines", on_dev)
     if len(ln.shape) == 2:
         ln = ln[None]
@@ -82,10 +157,8 @@ def describe_lines(frames, lines, counts=None, bands: int = 9, band_width: int =
                               ln.device if on_dev else None)
     opts = fd_line_desc_opts(int(bands), int(band_width))
     if s > 0:  # (an empty array has no address to hand over; the library does no work for stride 0 either)
-        _bind_stream(ctx, on_dev or bool(f_dev))
-        rc = _lib.load().fd_lines_describe(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(ln),
-                                           floats, ptr(cn), s, ptr(desc), ptr(xy), ptr(valid), 1 if on_dev else 0)
-        _lib.check(ctx.ptr, rc)
+        invoke(ctx, on_dev or bool(f_dev), "fd_lines_describe", ptr(keep), f_dev, b, rows, cols, ctypes.byref(opts), ptr(ln),
+               floats, ptr(cn), s, ptr(desc), ptr(xy), ptr(valid), 1 if on_dev else 0)
     if cn is None:
         if on_dev:
             import torch

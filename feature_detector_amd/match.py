@@ -17,11 +17,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
 from ._lib import fd_match_gate, fd_match_model_gate, fd_match_opts, fd_nn_match_opts
 from .geometry import MODELS, GeometryResult
 from ._slots import outputs, positions, ptr, slot_arg
-from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, invoke, is_device_tensor, resolve_ctx
 
 
 @dataclass
@@ -57,7 +56,7 @@ def _gate(q_xy, t_xy, radius, on_dev, b, sq, st, model=None, model_kind="fundame
     if model is not None:
         if isinstance(model, GeometryResult):
             model = model.model
-        if _is_torch_device_tensor(model) != on_dev:
+        if is_device_tensor(model) != on_dev:
             raise ValueError("model must be on the side (host / device) of the descriptors")
         if not on_dev:
             model = np.asarray(model)
@@ -74,7 +73,7 @@ def _gate(q_xy, t_xy, radius, on_dev, b, sq, st, model=None, model_kind="fundame
         rx = ry = float(radius)
     sides = []
     for xy, s, name in ((q_xy, sq, "q"), (t_xy, st, "t")):
-        if _is_torch_device_tensor(xy) != on_dev:
+        if is_device_tensor(xy) != on_dev:
             raise ValueError(f"{name}_xy must be on the side (host / device) of the descriptors")
         msg = f"{name}_xy must be [{b}, {s}, 2]" + (f" or [{s}, 2]" if b == 1 else "")
         p = positions(xy, f"{name}_xy", on_dev, msg=msg)
@@ -109,18 +108,14 @@ def _run(ctx, entry, opts, q, t, gate, on_dev, dist, out, out_msg=None):
     specs = (((b, sq), "int32", -1), ((b, sq, 2), dist, -1), ((b,), "int32", 0))
     idx, dst, counts = outputs(specs, out, on_dev, qx.device if on_dev else None,
                                out_msg and out_msg.format(*(shape for shape, _, _ in specs)))
-    _bind_stream(ctx, on_dev)
-    head, outs = (ctx.ptr, b, ctypes.byref(opts)), (ptr(idx), ptr(dst), ptr(counts), 1 if on_dev else 0)
+    head, outs = (b, ctypes.byref(opts)), (ptr(idx), ptr(dst), ptr(counts), 1 if on_dev else 0)
     qa, ta = (ptr(qx), ptr(qv), ptr(qc), sq), (ptr(tx), ptr(tv), ptr(tc), st)
     if gate is None:
-        rc = getattr(_lib.load(), entry)(*head, *qa, *ta, *outs)
+        invoke(ctx, on_dev, entry, *head, *qa, *ta, *outs)
     elif len(gate) == 4:
-        rc = getattr(_lib.load(), entry + "_model")(*head, ctypes.byref(gate[0]), ptr(gate[3]), *qa, ptr(gate[1]), *ta,
-                                                    ptr(gate[2]), *outs)
+        invoke(ctx, on_dev, entry + "_model", *head, ctypes.byref(gate[0]), ptr(gate[3]), *qa, ptr(gate[1]), *ta, ptr(gate[2]), *outs)
     else:
-        rc = getattr(_lib.load(), entry + "_guided")(*head, ctypes.byref(gate[0]), *qa, ptr(gate[1]), *ta, ptr(gate[2]),
-                                                     *outs)
-    _lib.check(ctx.ptr, rc)
+        invoke(ctx, on_dev, entry + "_guided", *head, ctypes.byref(gate[0]), *qa, ptr(gate[1]), *ta, ptr(gate[2]), *outs)
     return MatchResult(idx, dst, counts)
 
 
@@ -150,11 +145,11 @@ def brief_match(q_bits, t_bits, q_counts=None, t_counts=None, q_valid=None, t_va
     q_xy and t_xy are required. A frame whose model is all zeros (no model) is gated by the window alone.
     """
     _guided(q_xy, t_xy, radius, model, model_kind)
-    ctx = _resolve_ctx(ctx, q_bits, t_bits)
+    ctx = resolve_ctx(ctx, q_bits, t_bits)
     nw = (int(length) + 31) // 32 if 1 <= int(length) <= 256 else 0
     opts = fd_match_opts(int(length), int(max_distance), float(max_ratio), 1 if cross_check else 0)
-    on_dev = _is_torch_device_tensor(q_bits)
-    if on_dev != _is_torch_device_tensor(t_bits):
+    on_dev = is_device_tensor(q_bits)
+    if on_dev != is_device_tensor(t_bits):
         raise ValueError("q_bits and t_bits must both be device tensors or both host arrays")
     if nw == 0:  # (the library reports the bad length: any word count is taken)
         nw = int(q_bits.shape[-1])
@@ -188,9 +183,9 @@ def nn_match(q_desc, t_desc, q_counts=None, t_counts=None, q_valid=None, t_valid
     brief_match.
     """
     _guided(q_xy, t_xy, radius, model, model_kind)
-    ctx = _resolve_ctx(ctx, q_desc, t_desc)
-    on_dev = _is_torch_device_tensor(q_desc)
-    if on_dev != _is_torch_device_tensor(t_desc):
+    ctx = resolve_ctx(ctx, q_desc, t_desc)
+    on_dev = is_device_tensor(q_desc)
+    if on_dev != is_device_tensor(t_desc):
         raise ValueError("q_desc and t_desc must both be device tensors or both host arrays")
 
     def check(d, xp, name):

@@ -1,155 +1,24 @@
-"""Batch host API over libfdhip.so: contexts, point detection, candidates, LSD map.
+"""Batch host API over libfdhip.so: point detection, selection over given candidates, the per-pixel stage alone.
 
 Inputs are numpy arrays (host memory, staged by the library) or torch CUDA/ROCm tensors (device
 memory, used in place on the context's stream, which follows torch's current stream). Every call
-runs the HIP kernels; there is no CPU path.
+runs the HIP kernels; there is no CPU path. Contexts and sides are _context.py's.
 """
 from __future__ import annotations
 
 import ctypes
-import os
-import threading
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from ._context import TIES, Context, bind_stream, default_context, as_frames, invoke, resolve_ctx  # noqa: F401
 from ._lib import FD_FAST, FD_HARRIS, FD_SHI_TOMASI, fd_point_opts
+from ._slots import ptr
 
 KINDS = {"harris": FD_HARRIS, "shi_tomasi": FD_SHI_TOMASI, "fast": FD_FAST}
-# order of equal responses in the selection (include/fd_hip.h fd_ctx_set_tie_order)
-TIES = {"raster": 0, "reference": 1}
 FRAME_TIES, FRAME_RESOLVED, FRAME_UNRESOLVED, FRAME_VALUE_RANGE, FRAME_GUARD = 0x1, 0x2, 0x4, 0x40000000, 0xBE000000
 FRAME_REDETECTED = 0x8  # FAST, raster order: selected a second time without the adaptive emission cut
-
-_ctx_lock = threading.Lock()
-_contexts: dict[int, "Context"] = {}
-
-
-class Context:
-    """One fd_ctx: a HIP stream and grow-only device workspace on one GPU (not thread-safe)."""
-
-    def __init__(self, device: int = 0):
-        L = _lib.load()
-        p = ctypes.c_void_p()
-        rc = L.fd_ctx_create(int(device), ctypes.byref(p))
-        if rc != _lib.FD_OK:
-            raise _lib.FdError(rc, f"fd_ctx_create(device={device}) failed (is a GPU visible?)")
-        self.ptr = p
-        self.device = int(device)
-
-    def close(self):
-        if self.ptr:
-            _lib.load().fd_ctx_destroy(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, stream_handle: int | None):
-        """Run on the given hipStream_t (0 = the HIP null stream); None = the context's own stream."""
-        if stream_handle is None:
-            _lib.check(self.ptr, _lib.load().fd_ctx_use_own_stream(self.ptr))
-        else:
-            _lib.check(self.ptr, _lib.load().fd_ctx_set_stream(self.ptr, ctypes.c_void_p(int(stream_handle))))
-
-    def synchronize(self):
-        _lib.check(self.ptr, _lib.load().fd_ctx_synchronize(self.ptr))
-
-    def reserve(self, kind: int, batch: int, rows: int, cols: int, max_prior_total: int = 0):
-        _lib.check(self.ptr, _lib.load().fd_ctx_reserve(self.ptr, kind, batch, rows, cols, max_prior_total))
-
-    def set_tie_order(self, ties: str):
-        """'raster' (equal responses by raster index) or 'reference' (the reference's std::sort order)."""
-        _lib.check(self.ptr, _lib.load().fd_ctx_set_tie_order(self.ptr, TIES[ties]))
-
-    def frame_status(self, batch: int, out=None):
-        """Per-frame FD_FRAME_* words of the last selection call: numpy uint32 [batch] (synchronous), or
-        copied asynchronously into `out` (a device int32 tensor [batch]) on the context stream."""
-        if out is not None:
-            _lib.check(self.ptr, _lib.load().fd_ctx_frame_status(self.ptr, ctypes.c_void_p(out.data_ptr()), batch, 1))
-            return out
-        st = np.zeros((batch,), np.uint32)
-        _lib.check(self.ptr, _lib.load().fd_ctx_frame_status(self.ptr, ctypes.c_void_p(st.ctypes.data), batch, 0))
-        return st
-
-
-def _default_device() -> int:
-    return int(os.environ.get("FD_DEVICE", "0"))
-
-
-def default_context(device: int | None = None) -> Context:
-    """The shared context of a GPU (default: $FD_DEVICE or 0), created on first use."""
-    device = _default_device() if device is None else int(device)
-    with _ctx_lock:
-        c = _contexts.get(device)
-        if c is None:
-            c = Context(device)
-            _contexts[device] = c
-        return c
-
-
-def _is_torch_device_tensor(x) -> bool:
-    return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
-
-
-def _frames(x):
-    """(pointer, on_device, batch, rows, cols, keepalive) for a u8 [B,]R,C array or tensor."""
-    if _is_torch_device_tensor(x):
-        import torch
-
-        if x.dtype != torch.uint8:
-            raise TypeError("frames must be uint8")
-        if not x.is_contiguous():
-            x = x.contiguous()
-        shape = tuple(x.shape)
-        ptr, on_dev = x.data_ptr(), 1
-    else:
-        x = np.ascontiguousarray(x)
-        if x.dtype != np.uint8:
-            raise TypeError("frames must be uint8")
-        shape = x.shape
-        ptr, on_dev = x.ctypes.data, 0
-    if len(shape) == 2:
-        b, r, c = 1, shape[0], shape[1]
-    elif len(shape) == 3:
-        b, r, c = shape
-    else:
-        raise ValueError("frames must be [rows, cols] or [batch, rows, cols]")
-    return ptr, on_dev, int(b), int(r), int(c), x
-
-
-def _resolve_ctx(ctx: Context | None, *inputs) -> Context:
-    """The context of a call: `ctx`, or the default context of the GPU the torch inputs live on. A
-    context on another device than its inputs is an error (its workspace and stream are per device)."""
-    dev = None
-    for x in inputs:
-        if _is_torch_device_tensor(x):
-            import torch
-
-            d = x.device.index if x.device.index is not None else torch.cuda.current_device()
-            if dev is not None and d != dev:
-                raise ValueError(f"inputs on different devices ({dev} and {d})")
-            dev = d
-    if ctx is None:
-        return default_context(dev)
-    if dev is not None and ctx.device != dev:
-        raise ValueError(f"context is on device {ctx.device} but the inputs are on device {dev}")
-    return ctx
-
-
-def _bind_stream(ctx: Context, on_device: bool):
-    """Device inputs run on torch's current stream of the context's device; host inputs on the
-    context's own stream. (The library orders a stream switch after the previous stream's work.)"""
-    if on_device:
-        import torch
-
-        ctx.set_stream(torch.cuda.current_stream(ctx.device).cuda_stream)
-    else:
-        ctx.set_stream(None)
 
 
 def _priors(prior, batch):
@@ -209,9 +78,9 @@ def detect_points(kind, frames, need: int, min_feature_distance: int = 15, min_v
     preallocated (xy, counts) or (xy, counts, status) tensors so that repeated calls allocate nothing.
     """
     kind = KINDS[kind] if isinstance(kind, str) else int(kind)
-    ptr, on_dev, b, r, c, keep = _frames(frames)
-    ctx = _resolve_ctx(ctx, frames)
-    _bind_stream(ctx, bool(on_dev))
+    ptr, on_dev, b, r, c, keep = as_frames(frames)
+    ctx = resolve_ctx(ctx, frames)
+    bind_stream(ctx, bool(on_dev))
     if ties is None:
         ties = "raster" if on_dev else "reference"
     ctx.set_tie_order(ties)
@@ -272,8 +141,8 @@ def select_points(candidates, rows: int, cols: int, need: int, min_feature_dista
                 raise ValueError("device candidates: contiguous resp f32 / x, y int32 [B, cap] tensors")
         if counts.dtype != torch.int64 or tuple(counts.shape) != (b,) or not counts.is_cuda:
             raise ValueError("device candidates: counts int64 [B]")
-        ctx = _resolve_ctx(ctx, resp)
-        _bind_stream(ctx, True)
+        ctx = resolve_ctx(ctx, resp)
+        bind_stream(ctx, True)
         ctx.set_tie_order(ties or "raster")
         pxy, pcnt, _keep2 = _priors(prior, b)
         stride = max(int(need), 1) + 1
@@ -307,8 +176,8 @@ def select_points(candidates, rows: int, cols: int, need: int, min_feature_dista
         if len(x_) != n or len(y_) != n:
             raise ValueError(f"frame {i}: resp, x and y differ in length")
         resp[i, :n], xs[i, :n], ys[i, :n] = r_, x_, y_
-    ctx = _resolve_ctx(ctx)
-    _bind_stream(ctx, False)
+    ctx = resolve_ctx(ctx)
+    bind_stream(ctx, False)
     ctx.set_tie_order(ties or "reference")
     pxy, pcnt, _keep2 = _priors(prior, b)
     stride = max(int(need), 1) + 1
@@ -336,11 +205,10 @@ def point_response(kind, frames, min_valid_response: float = 0.1, out=None, ctx:
     import torch
 
     kind = KINDS[kind] if isinstance(kind, str) else int(kind)
-    ptr, on_dev, b, r, c, keep = _frames(frames)
+    _, on_dev, b, r, c, keep = as_frames(frames)
     if not on_dev:
         raise TypeError("point_response takes device frames")
-    ctx = _resolve_ctx(ctx, frames)
-    _bind_stream(ctx, True)
+    ctx = resolve_ctx(ctx, frames)
     cap = r * c if kind == FD_FAST else r * c // 2 + 64
     if out is None:
         resp = torch.empty((b, cap), dtype=torch.float32, device=frames.device)
@@ -352,13 +220,8 @@ def point_response(kind, frames, min_valid_response: float = 0.1, out=None, ctx:
     if append and out is None:
         raise ValueError("append=True needs out=(resp, idx, counts)")
     opts = fd_point_opts(15, float(min_valid_response))
-    L = _lib.load()
-    fn = L.fd_points_response_append if append else L.fd_points_response
-    rc = fn(ctx.ptr, kind, ctypes.c_void_p(ptr), b, r, c, ctypes.byref(opts),
-            ctypes.c_void_p(resp.data_ptr()), ctypes.c_void_p(idx.data_ptr()), int(cap),
-            ctypes.c_void_p(counts.data_ptr()))
-    _lib.check(ctx.ptr, rc)
-    del keep
+    invoke(ctx, True, "fd_points_response_append" if append else "fd_points_response", kind, ptr(keep), b, r, c,
+           ctypes.byref(opts), ptr(resp), ptr(idx), int(cap), ptr(counts))
     return resp, idx, counts
 
 
@@ -370,11 +233,10 @@ def point_candidates(kind, frames, min_feature_distance: int = 15, min_valid_res
     [batch, rows, cols] if requested.
     """
     kind = KINDS[kind] if isinstance(kind, str) else int(kind)
-    ptr, on_dev, b, r, c, keep = _frames(frames)
+    _, on_dev, b, r, c, keep = as_frames(frames)
     if on_dev:
         raise TypeError("point_candidates takes host frames")
-    ctx = _resolve_ctx(ctx, frames)
-    _bind_stream(ctx, False)
+    ctx = resolve_ctx(ctx, frames)
     opts = fd_point_opts(int(min_feature_distance), float(min_valid_response))
     pxy, pcnt, _keep2 = _priors(prior, b)
     if cap is None:
@@ -384,105 +246,7 @@ def point_candidates(kind, frames, min_feature_distance: int = 15, min_valid_res
     ys = np.zeros((b, max(cap, 1)), np.int32)
     counts = np.zeros((b,), np.int64)
     rmap = np.zeros((b, r, c), np.float32) if response_map else None
-    rc = _lib.load().fd_points_candidates(
-        ctx.ptr, kind, ctypes.c_void_p(ptr), 0, b, r, c, ctypes.byref(opts),
-        ctypes.c_void_p(pxy.ctypes.data) if pxy is not None else None,
-        ctypes.c_void_p(pcnt.ctypes.data) if pcnt is not None else None,
-        ctypes.c_void_p(resp.ctypes.data), ctypes.c_void_p(xs.ctypes.data), ctypes.c_void_p(ys.ctypes.data),
-        int(cap), ctypes.c_void_p(counts.ctypes.data),
-        ctypes.c_void_p(rmap.ctypes.data) if rmap is not None else None, 0)
-    _lib.check(ctx.ptr, rc)
-    del keep
+    invoke(ctx, False, "fd_points_candidates", kind, ptr(keep), 0, b, r, c, ctypes.byref(opts), ptr(pxy), ptr(pcnt),
+           ptr(resp), ptr(xs), ptr(ys), int(cap), ptr(counts), ptr(rmap), 0)
     out = [(resp[i, :counts[i]].copy(), xs[i, :counts[i]].copy(), ys[i, :counts[i]].copy()) for i in range(b)]
     return (out, rmap) if response_map else out
-
-
-def lsd_map(frames, min_norm: float = 20.0, cap: int | None = None, ctx: Context | None = None, out=None):
-    """ComputeLineLevelAngleMap (fd_lsd_map / fd_lsd_map_pitched).
-
-    Host (numpy) frames: returns per frame (norm, angle, valid, valid_idx_colmajor); maps are
-    (rows-1, cols-1). Torch device frames: returns device tensors (norm [B, R-1, C-1] f32, angle f32,
-    valid u8, valid_idx int32 [B, cap], counts int64 [B]), asynchronous on torch's current stream;
-    the maps are views of storage whose rows are padded to 16 entries (aligned row stores); `out` may
-    pass them preallocated (graph capture), contiguous or as such row-padded views sharing one row
-    pitch; any of norm/angle/valid may be None to skip.
-    """
-    ptr, on_dev, b, r, c, keep = _frames(frames)
-    ctx = _resolve_ctx(ctx, frames)
-    mr, mc = r - 1, c - 1
-    cap = mr * mc if cap is None else cap
-    if on_dev:
-        import torch
-
-        if out is None:
-            dev = frames.device
-            pitch = (mc + 15) // 16 * 16
-            out = (torch.empty((b, mr, pitch), dtype=torch.float32, device=dev)[..., :mc],
-                   torch.empty((b, mr, pitch), dtype=torch.float32, device=dev)[..., :mc],
-                   torch.empty((b, mr, pitch), dtype=torch.uint8, device=dev)[..., :mc],
-                   torch.empty((b, max(cap, 1)), dtype=torch.int32, device=dev),
-                   torch.empty((b,), dtype=torch.int64, device=dev))
-        norm, ang, val, idx, cnt = out
-        pitch = None
-        for t in (norm, ang, val):
-            if t is None:
-                continue
-            if tuple(t.shape) != (b, mr, mc) or t.stride(2) != 1 or t.stride(0) != mr * t.stride(1):
-                raise ValueError(f"lsd_map: maps must be [{b}, {mr}, {mc}] with unit column stride and rows "
-                                 "packed at one pitch")
-            if pitch not in (None, t.stride(1)):
-                raise ValueError("lsd_map: norm / angle / valid must share one row pitch")
-            pitch = t.stride(1)
-        pitch = mc if pitch is None else pitch
-        cap = idx.shape[1]
-        _bind_stream(ctx, True)
-
-        def p(t):
-            return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-        rc = _lib.load().fd_lsd_map_pitched(ctx.ptr, ctypes.c_void_p(ptr), 1, b, r, c, float(min_norm), p(norm),
-                                            p(ang), p(val), int(pitch), p(idx), int(cap), p(cnt), 1)
-        _lib.check(ctx.ptr, rc)
-        del keep
-        return out
-    _bind_stream(ctx, False)
-    norm = np.zeros((b, mr, mc), np.float32)
-    ang = np.zeros((b, mr, mc), np.float32)
-    val = np.zeros((b, mr, mc), np.uint8)
-    idx = np.zeros((b, max(cap, 1)), np.int32)
-    cnt = np.zeros((b,), np.int64)
-    rc = _lib.load().fd_lsd_map(ctx.ptr, ctypes.c_void_p(ptr), 0, b, r, c, float(min_norm),
-                                ctypes.c_void_p(norm.ctypes.data), ctypes.c_void_p(ang.ctypes.data),
-                                ctypes.c_void_p(val.ctypes.data), ctypes.c_void_p(idx.ctypes.data), int(cap),
-                                ctypes.c_void_p(cnt.ctypes.data), 0)
-    _lib.check(ctx.ptr, rc)
-    del keep
-    return [(norm[i], ang[i], val[i], idx[i, :cnt[i]].copy()) for i in range(b)]
-
-
-# FeatureLineDetector::Options defaults (feature_line_detector.h:40-45); kDegToRad = kPai / 180 in float.
-LSD_TOL_RAD = float(np.float32(22.5) * (np.float32(3.14159265358979323846) / np.float32(180.0)))
-
-
-def lsd_lines(frames, needed: int = 1, min_norm: float = 20.0, tol_rad: float = LSD_TOL_RAD, min_length: float = 20.0,
-              min_inlier: float = 0.6, max_lines: int = 4096, threads: int = 0, ctx: Context | None = None):
-    """FeatureLineDetector::DetectGoodFeatures for a batch (fd_lsd_lines): GPU level-line map (compact
-    lists), region growing and rectangle fitting on `threads` host threads (0: all, capped by
-    OMP_NUM_THREADS). frames: numpy [B, R, C] / [R, C] u8 or a torch device tensor.
-
-    Returns a list over frames of float32 arrays [n, 12] (start x, y, end x, y, center x, y, length,
-    width, angle, dir x, y, inlier ratio); columns 0-3 are the reference's Vec4 features."""
-    ptr, on_dev, b, r, c, keep = _frames(frames)
-    ctx = _resolve_ctx(ctx, frames)
-    _bind_stream(ctx, on_dev)
-    opts = _lib.fd_lsd_opts(float(min_norm), float(tol_rad), float(min_length), float(min_inlier))
-    out = np.empty((b, max(max_lines, 1), _lib.LSD_RECT_FLOATS), np.float32)
-    cnt = np.zeros((b,), np.int32)
-    rc = _lib.load().fd_lsd_lines(ctx.ptr, ctypes.c_void_p(ptr), 1 if on_dev else 0, b, r, c, ctypes.byref(opts),
-                                  int(needed), ctypes.c_void_p(out.ctypes.data), int(max_lines),
-                                  ctypes.c_void_p(cnt.ctypes.data), int(threads))
-    _lib.check(ctx.ptr, rc)
-    del keep
-    if (cnt > max_lines).any():
-        raise _lib.FdError(_lib.FD_ERR_CAPACITY, f"max_lines={max_lines} < {int(cnt.max())} segments found")
-    return [out[i, :cnt[i]].copy() for i in range(b)]

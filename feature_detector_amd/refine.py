@@ -10,11 +10,10 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 
-from . import _lib
 from ._lib import fd_refine_opts
 from ._slots import outputs, positions, ptr, slot_arg
 from .flow import Pyramid
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, invoke, is_device_tensor, resolve_ctx
 
 
 @dataclass
@@ -45,9 +44,9 @@ def refine_points(frames, xy, counts=None, valid=None, half_window: int = 5, max
     """
     if isinstance(frames, Pyramid):
         frames = frames.level(0)
-    fptr, f_dev, b, rows, cols, keep = _frames(frames)
-    on_dev = _is_torch_device_tensor(xy)
-    ctx = _resolve_ctx(ctx, xy, keep)
+    _, f_dev, b, rows, cols, keep = as_frames(frames)
+    on_dev = is_device_tensor(xy)
+    ctx = resolve_ctx(ctx, xy, keep)
     pxy = positions(xy, "xy", on_dev)
     s = int(pxy.shape[1])
     if int(pxy.shape[0]) != b:
@@ -57,8 +56,6 @@ def refine_points(frames, xy, counts=None, valid=None, half_window: int = 5, max
                              pxy.device if on_dev else None)
     opts = fd_refine_opts(int(half_window), int(max_iters), float(epsilon), float(min_eigen),
                           float(half_window if max_shift is None else max_shift))
-    _bind_stream(ctx, on_dev or bool(f_dev))
-    rc = _lib.load().fd_points_refine(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(pxy),
-                                      ptr(v), ptr(cn), s, ptr(oxy), ptr(ost), ptr(ocnt), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev or bool(f_dev), "fd_points_refine", ptr(keep), f_dev, b, rows, cols, ctypes.byref(opts), ptr(pxy),
+           ptr(v), ptr(cn), s, ptr(oxy), ptr(ost), ptr(ocnt), 1 if on_dev else 0)
     return RefineResult(oxy, ost, ocnt)

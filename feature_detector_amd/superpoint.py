@@ -1,5 +1,5 @@
 """NN keypoints + descriptors: the networks in PyTorch-ROCm, the post-processing in
-the HIP kernels behind fd_nn_select / fd_nn_select_list / fd_nn_descriptors.
+the HIP kernels behind fd_nn_select / fd_nn_select_list / fd_nn_descriptors and the layer kernels (nn_layers.py).
 
 Mirrors feature_detector::NNFeaturePointDetector (src/nn_feature_point_detector/
 nn_feature_point_detector.h:12-86) for its four model types (ModelType, :15-20):
@@ -24,356 +24,14 @@ bit-exact to the oracle's restatement on any given network output.
 from __future__ import annotations
 
 import os
-
-import ctypes
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
-from ._lib import fd_nn_opts
-from .points import Context, _bind_stream, _is_torch_device_tensor, _resolve_ctx
-
-
-@dataclass
-class Options:
-    """NNFeaturePointDetector::Options (nn_feature_point_detector.h:22-31)."""
-    kInvalidBoundary: int = 3
-    kMinFeatureDistance: int = 15
-    kMaxImageRows: int = 480
-    kMaxImageCols: int = 752
-    kMaxNumberOfDetectedFeatures: int = 240
-    kMinResponse: float = 0.1
-    kModelType: str = "kSuperpointHeatmap"
-    kComputeDescriptors: bool = False
-
-
-def _opts(o: Options, max_response: float = 1.0) -> fd_nn_opts:
-    return fd_nn_opts(int(o.kInvalidBoundary), int(o.kMinFeatureDistance), int(o.kMaxNumberOfDetectedFeatures),
-                      float(o.kMinResponse), float(max_response))
-
-
-def _prior_arrays(prior, b):
-    """Per-frame prior features (list of (n_i, 2) (x, y) arrays) -> (flat float32 [sum, 2], counts int32)."""
-    if prior is None:
-        return None, None
-    if len(prior) != b:
-        raise ValueError("prior must have one entry per frame")
-    pcnt = np.array([len(p) for p in prior], np.int32)
-    pflat = (np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).reshape(-1, 2) for p in prior]))
-             if pcnt.sum() > 0 else np.zeros((1, 2), np.float32))
-    return pflat, pcnt
-
-
-def nn_select(heat, options: Options | None = None, prior=None, out=None, ctx: Context | None = None,
-              max_response: float = 1.0):
-    """fd_nn_select on heatmaps [B, H, W] float32 (numpy, or a torch device tensor -> device outputs).
-
-    max_response: declared upper bound of the heatmap (1.0: softmax probabilities); float('inf') for
-    arbitrary maps (coarser selection keys). A value above it fails the call.
-    Returns (xy [B, max+1, 2] float32, counts [B] int32): new features per frame, selection order.
-    prior: None or a list (per frame) of (n_i, 2) float arrays of (x, y), host memory.
-    """
-    o = options or Options()
-    ctx = _resolve_ctx(ctx, heat)
-    opts = _opts(o, max_response)
-    on_dev = _is_torch_device_tensor(heat)
-    if on_dev:
-        import torch
-
-        heat = heat.to(torch.float32).contiguous()
-        ptr = heat.data_ptr()
-    else:
-        heat = np.ascontiguousarray(heat, np.float32)
-        ptr = heat.ctypes.data
-    if heat.ndim == 2:
-        heat = heat[None]
-    b, r, c = (int(v) for v in heat.shape)
-    stride = max(int(o.kMaxNumberOfDetectedFeatures), 1) + 1
-    pflat, pcnt = _prior_arrays(prior, b)
-    if on_dev:
-        import torch
-
-        if out is None:
-            out = (torch.empty((b, stride, 2), dtype=torch.float32, device=heat.device),
-                   torch.empty((b,), dtype=torch.int32, device=heat.device))
-        xy, cnt = out
-        stride = xy.shape[1]
-        xy_p, cnt_p = xy.data_ptr(), cnt.data_ptr()
-    else:
-        xy = np.zeros((b, stride, 2), np.float32)
-        cnt = np.zeros((b,), np.int32)
-        xy_p, cnt_p = xy.ctypes.data, cnt.ctypes.data
-    _bind_stream(ctx, on_dev)
-    rc = _lib.load().fd_nn_select(
-        ctx.ptr, ctypes.c_void_p(ptr), 1 if on_dev else 0, b, r, c, ctypes.byref(opts),
-        ctypes.c_void_p(pflat.ctypes.data) if pflat is not None else None,
-        ctypes.c_void_p(pcnt.ctypes.data) if pcnt is not None else None, ctypes.c_void_p(xy_p), int(stride),
-        ctypes.c_void_p(cnt_p), 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return xy, cnt
-
-
-def nn_select_list(keypoints, scores, rows: int, cols: int, counts=None, options: Options | None = None, prior=None,
-                   descriptors=None, out=None, ctx: Context | None = None):
-    """fd_nn_select_list: the keypoint-list models' selection (DirectlySelectGoodFeaturesWithDescriptors).
-
-    keypoints [B, K, 2] int64 (u, v) in a rows x cols frame, scores [B, K] float32, counts [B] int64
-    (None: K each),
-    descriptors [B, K, D] float32 or None. numpy inputs give numpy outputs; torch device tensors give
-    device outputs (current stream). Returns (xy [B, max+1, 2], counts [B] int32, desc [B, max+1, D] or
-    None): the new features per frame in selection order and their descriptor rows.
-    prior: None or a list (per frame) of (n_i, 2) float arrays of (x, y), host memory.
-    """
-    o = options or Options()
-    on_dev = _is_torch_device_tensor(scores)
-    ctx = _resolve_ctx(ctx, scores)
-    opts = _opts(o, float("inf"))
-    stride = max(int(o.kMaxNumberOfDetectedFeatures), 1) + 1
-    pflat, pcnt = _prior_arrays(prior, int(scores.shape[0]))
-    if on_dev:
-        import torch
-
-        kp = keypoints.to(torch.int64).contiguous()
-        sc = scores.to(torch.float32).contiguous()
-        b, k = (int(v) for v in sc.shape)
-        cnt_in = (torch.full((b,), k, dtype=torch.int64, device=sc.device) if counts is None
-                  else counts.to(torch.int64).contiguous())
-        dd = None if descriptors is None else descriptors.to(torch.float32).contiguous()
-        dim = 0 if dd is None else int(dd.shape[2])
-        if out is None:
-            out = (torch.empty((b, stride, 2), dtype=torch.float32, device=sc.device),
-                   torch.empty((b,), dtype=torch.int32, device=sc.device),
-                   None if dd is None else torch.zeros((b, stride, dim), dtype=torch.float32, device=sc.device))
-        xy, cnt, dout = out
-        stride = xy.shape[1]
-        ptrs = (kp.data_ptr(), sc.data_ptr(), cnt_in.data_ptr(), 0 if dd is None else dd.data_ptr(),
-                0 if dout is None else dout.data_ptr(), xy.data_ptr(), cnt.data_ptr())
-    else:
-        kp = np.ascontiguousarray(keypoints, np.int64)
-        sc = np.ascontiguousarray(scores, np.float32)
-        b, k = sc.shape
-        cnt_in = np.full((b,), k, np.int64) if counts is None else np.ascontiguousarray(counts, np.int64)
-        dd = None if descriptors is None else np.ascontiguousarray(descriptors, np.float32)
-        dim = 0 if dd is None else dd.shape[2]
-        xy = np.zeros((b, stride, 2), np.float32)
-        cnt = np.zeros((b,), np.int32)
-        dout = None if dd is None else np.zeros((b, stride, dim), np.float32)
-        ptrs = (kp.ctypes.data, sc.ctypes.data, cnt_in.ctypes.data, 0 if dd is None else dd.ctypes.data,
-                0 if dout is None else dout.ctypes.data, xy.ctypes.data, cnt.ctypes.data)
-    if tuple(kp.shape) != (b, k, 2):
-        raise ValueError("keypoints must be [B, K, 2] matching scores [B, K]")
-    _bind_stream(ctx, on_dev)
-    vp = [ctypes.c_void_p(p) if p else None for p in ptrs]
-    rc = _lib.load().fd_nn_select_list(
-        ctx.ptr, vp[0], vp[1], vp[2], int(k), 1 if on_dev else 0, b, int(rows), int(cols), ctypes.byref(opts),
-        ctypes.c_void_p(pflat.ctypes.data) if pflat is not None else None,
-        ctypes.c_void_p(pcnt.ctypes.data) if pcnt is not None else None,
-        vp[3], int(dim), vp[4], vp[5], int(stride), vp[6], 1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
-    return xy, cnt, dout
-
-
-def bias_relu(x, bias, pool: bool = False, out=None, ctx: Context | None = None):
-    """fd_nn_bias_relu: relu(x + bias) (and the 2x2 max pool when pool) of a channels-last fp16
-    activation [N, C, H, W] on the device, in one pass (torch's current stream). x is the output of a
-    bias-free convolution; the result equals PyTorch's separate half-precision add / ReLU (/ MaxPool2d(2,
-    2)) ops on it, bit for bit (not a conv-with-bias, whose bias is added before the rounding to half;
-    and a NaN sum gives 0 here). out: preallocated result (may be x itself when not pooling)."""
-    import torch
-
-    if not (_is_torch_device_tensor(x) and x.dtype == torch.float16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError("bias_relu: x must be a channels-last float16 [N, C, H, W] device tensor")
-    n, c, h, w = x.shape
-    if pool and (h % 2 or w % 2):
-        raise ValueError("bias_relu: pooling needs even H and W")
-    shape = (n, c, h // 2, w // 2) if pool else (n, c, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
-    elif not (_is_torch_device_tensor(out) and out.device == x.device and out.dtype == torch.float16
-              and tuple(out.shape) == shape and out.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError(f"bias_relu: out must be a channels-last float16 {list(shape)} tensor on {x.device}")
-    if bias.numel() != c:
-        raise ValueError(f"bias_relu: bias has {bias.numel()} values for {c} channels")
-    b = bias.detach().to(device=x.device, dtype=torch.float16).contiguous()
-    ctx = _resolve_ctx(ctx, x)
-    _bind_stream(ctx, True)
-    rc = _lib.load().fd_nn_bias_relu(ctx.ptr, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                                      int(b.numel()), ctypes.c_void_p(out.data_ptr()), int(n), int(h), int(w), int(c),
-                                      1 if pool else 0)
-    _lib.check(ctx.ptr, rc)
-    return out
-
-
-def heat_softmax(semi, bias=None, ctx: Context | None = None):
-    """fd_nn_heat_softmax: SuperPoint's detector-head output from convPb's logits [N, 65, Hc, Wc]
-    (channels-last fp16, on the device): softmax over the 65 channels in float, the dustbin dropped,
-    pixel_shuffle(8) -> heat [N, 8 Hc, 8 Wc] float32, in one pass (PyTorch: float copy, softmax, slice,
-    shuffle). bias (65 values): added to semi in half first (semi from a bias-free convolution). Within
-    float rounding of torch.softmax((semi + bias).float(), 1)[:, :-1] shuffled."""
-    import torch
-
-    if not (_is_torch_device_tensor(semi) and semi.dtype == torch.float16 and semi.dim() == 4 and semi.shape[1] == 65
-            and semi.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError("heat_softmax: semi must be a channels-last float16 [N, 65, Hc, Wc] device tensor")
-    n, _, hc, wc = semi.shape
-    b = None
-    if bias is not None:
-        if bias.numel() != 65:
-            raise ValueError("heat_softmax: bias must hold 65 values")
-        b = bias.detach().to(device=semi.device, dtype=torch.float16).contiguous()
-    heat = torch.empty((n, 8 * hc, 8 * wc), dtype=torch.float32, device=semi.device)
-    ctx = _resolve_ctx(ctx, semi)
-    _bind_stream(ctx, True)
-    rc = _lib.load().fd_nn_heat_softmax(ctx.ptr, ctypes.c_void_p(semi.data_ptr()),
-                                         ctypes.c_void_p(b.data_ptr() if b is not None else None),
-                                         ctypes.c_void_p(heat.data_ptr()), int(n), int(hc), int(wc))
-    _lib.check(ctx.ptr, rc)
-    return heat
-
-
-def desc_normalize(desc, bias=None, ctx: Context | None = None):
-    """fd_nn_desc_normalize: SuperPoint's descriptor-head output from convDb's [N, C, Hc, Wc] (channels-last
-    fp16, on the device): each cell's vector over its L2 norm (clamped to 1e-12) in float -> [N, C, Hc, Wc]
-    float32 channels-last, in one pass (PyTorch: float copy, norm, division). bias (C values): added in
-    half first (desc from a bias-free convolution). Within float rounding of d.float() /
-    d.float().norm(dim=1, keepdim=True).clamp_min(1e-12), d = desc + bias."""
-    import torch
-
-    if not (_is_torch_device_tensor(desc) and desc.dtype == torch.float16 and desc.dim() == 4 and desc.shape[1] % 8 == 0
-            and desc.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError("desc_normalize: desc must be a channels-last float16 [N, C, Hc, Wc] device tensor, C % 8 == 0")
-    n, c, hc, wc = desc.shape
-    b = None
-    if bias is not None:
-        if bias.numel() != c:
-            raise ValueError(f"desc_normalize: bias must hold {c} values")
-        b = bias.detach().to(device=desc.device, dtype=torch.float16).contiguous()
-    out = torch.empty((n, c, hc, wc), dtype=torch.float32, device=desc.device, memory_format=torch.channels_last)
-    ctx = _resolve_ctx(ctx, desc)
-    _bind_stream(ctx, True)
-    rc = _lib.load().fd_nn_desc_normalize(ctx.ptr, ctypes.c_void_p(desc.data_ptr()),
-                                           ctypes.c_void_p(b.data_ptr() if b is not None else None),
-                                           ctypes.c_void_p(out.data_ptr()), int(n) * int(hc) * int(wc), int(c))
-    _lib.check(ctx.ptr, rc)
-    return out
-
-
-def conv1_bias_relu(x, weight, bias, out=None, ctx: Context | None = None):
-    """fd_nn_conv3x3_c1: the encoder's first layer (1 input channel, 3x3, stride 1, padding 1) with its bias
-    and ReLU in one pass: x [N, 1, H, W] fp16 on the device -> [N, C, H, W] fp16 channels-last. The 9
-    products are summed in float and rounded to half, then the bias is added in float and rounded (as the
-    bias-free convolution followed by bias_relu); within fp16 rounding of PyTorch's convolution + ReLU.
-    W <= 4096 (the kernel's row staging); a wider frame is refused."""
-    import torch
-
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.shape[1] == 1
-            and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last))):
-        raise ValueError("conv1_bias_relu: x must be a [N, 1, H, W] float16 device tensor")
-    n, _, h, w = x.shape
-    c = weight.shape[0]
-    if tuple(weight.shape) != (c, 1, 3, 3) or weight.dtype != torch.float16 or bias.numel() != c:
-        raise ValueError("conv1_bias_relu: weight must be [C, 1, 3, 3] float16 and bias C values")
-    if out is None:
-        out = torch.empty((n, c, h, w), dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
-    elif not (out.dtype == torch.float16 and tuple(out.shape) == (n, c, h, w)
-              and out.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError(f"conv1_bias_relu: out must be a channels-last float16 {[n, c, h, w]} tensor")
-    ctx = _resolve_ctx(ctx, x)
-    _bind_stream(ctx, True)
-    wt = weight.detach().to(device=x.device, dtype=torch.float16).contiguous()  # (the kernel reads it on x's device)
-    b = bias.detach().to(device=x.device, dtype=torch.float16).contiguous()
-    rc = _lib.load().fd_nn_conv3x3_c1(ctx.ptr, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wt.data_ptr()),
-                                       ctypes.c_void_p(b.data_ptr()), c, ctypes.c_void_p(out.data_ptr()), n, h, w)
-    _lib.check(ctx.ptr, rc)
-    return out
-
-
-def pack_conv3x3_weight(weight):
-    """[C_out, C_in, 3, 3] -> [9 taps (ky, kx)][C_out][C_in] contiguous (fd_nn_conv3x3_c64's filter layout)."""
-    return weight.detach().permute(2, 3, 0, 1).reshape(9, weight.shape[0], weight.shape[1]).contiguous()
-
-
-def conv64_bias_relu(x, weight, bias, pool: bool = False, out=None, ctx: Context | None = None, packed=None):
-    """fd_nn_conv3x3_c64: 3x3 convolution from 64 channels to a multiple of 64 (stride 1, padding 1) + bias +
-    ReLU (+ 2x2 max pool) on the matrix cores, one call per 64-output-channel block: x [N, 64, H, W] fp16
-    channels-last on the device -> [N, C_out, H(/2), W(/2)] fp16 channels-last. fp16 products summed in
-    float, the sum rounded to half, then the bias added in float and rounded (as the bias-free
-    convolution + bias_relu path). packed: the filter's blocks already in pack_conv3x3_weight's layout
-    (a list, one per 64 output channels; reused across calls)."""
-    import torch
-
-    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and x.shape[1] == 64
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError("conv64_bias_relu: x must be a channels-last float16 [N, 64, H, W] device tensor")
-    n, c, h, w = x.shape
-    co = weight.shape[0]
-    if co % 64 or tuple(weight.shape) != (co, 64, 3, 3) or bias.numel() != co:
-        raise ValueError("conv64_bias_relu: weight must be [64 k, 64, 3, 3] and bias as many values")
-    if pool and (h % 2 or w % 2):
-        raise ValueError("conv64_bias_relu: pooling needs even H and W")
-    shape = (n, co, h // 2, w // 2) if pool else (n, co, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
-    elif not (out.dtype == torch.float16 and tuple(out.shape) == shape
-              and out.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError(f"conv64_bias_relu: out must be a channels-last float16 {list(shape)} tensor")
-    if packed is None:
-        packed = [pack_conv3x3_weight(weight[k:k + 64].to(device=x.device, dtype=torch.float16)) for k in range(0, co, 64)]
-    elif any(wp.device != x.device or wp.dtype != torch.float16 or tuple(wp.shape) != (9, 64, 64) for wp in packed) \
-            or len(packed) != co // 64:
-        raise ValueError(f"conv64_bias_relu: packed must be {co // 64} float16 [9, 64, 64] blocks on {x.device}")
-    b = bias.detach().to(device=x.device, dtype=torch.float16).contiguous()
-    ctx = _resolve_ctx(ctx, x)
-    _bind_stream(ctx, True)
-    for blk, wp in enumerate(packed):
-        bb = b[blk * 64:(blk + 1) * 64]
-        rc = _lib.load().fd_nn_conv3x3_c64(ctx.ptr, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(wp.data_ptr()),
-                                            ctypes.c_void_p(bb.data_ptr()), ctypes.c_void_p(out.data_ptr()), n, h, w,
-                                            1 if pool else 0, co, blk * 64)
-        _lib.check(ctx.ptr, rc)
-    return out
-
-
-def nn_descriptors(desc_map, xy, counts=None, out=None, ctx: Context | None = None):
-    """fd_nn_descriptors: desc_map [B, C, h, w] float32, xy [B, S, 2] -> descriptors [B, S, C].
-
-    Host arrays give numpy outputs; torch device tensors give device outputs (current stream)."""
-    ctx = _resolve_ctx(ctx, desc_map, xy)
-    if _is_torch_device_tensor(desc_map):
-        import torch
-
-        m = desc_map.to(torch.float32)
-        b, ch, h, w = (int(v) for v in m.shape)
-        # a channels-last map (the network's output) is read in place; anything else as NCHW
-        if m.is_contiguous(memory_format=torch.channels_last) and not m.is_contiguous():
-            layout = 1
-        else:
-            m, layout = m.contiguous(), 0
-        xy_t = xy.to(torch.float32).contiguous()
-        s = int(xy_t.shape[1])
-        cnt_t = None if counts is None else counts.to(torch.int32).contiguous()
-        res = out if out is not None else torch.zeros((b, s, ch), dtype=torch.float32, device=m.device)
-        _bind_stream(ctx, True)
-        rc = _lib.load().fd_nn_descriptors(
-            ctx.ptr, ctypes.c_void_p(m.data_ptr()), 1, layout, b, ch, h, w, ctypes.c_void_p(xy_t.data_ptr()),
-            ctypes.c_void_p(cnt_t.data_ptr()) if cnt_t is not None else None, s, ctypes.c_void_p(res.data_ptr()), 1)
-        _lib.check(ctx.ptr, rc)
-        return res
-    m = np.ascontiguousarray(desc_map, np.float32)
-    b, ch, h, w = m.shape
-    xy_h = np.ascontiguousarray(np.asarray(xy, np.float32).reshape(b, -1, 2))
-    s = xy_h.shape[1]
-    cnt_h = None if counts is None else np.ascontiguousarray(np.asarray(counts, np.int32).reshape(b))
-    res = np.zeros((b, s, ch), np.float32)
-    _bind_stream(ctx, False)
-    rc = _lib.load().fd_nn_descriptors(
-        ctx.ptr, ctypes.c_void_p(m.ctypes.data), 0, 0, b, ch, h, w, ctypes.c_void_p(xy_h.ctypes.data),
-        ctypes.c_void_p(cnt_h.ctypes.data) if cnt_h is not None else None, s, ctypes.c_void_p(res.ctypes.data), 0)
-    _lib.check(ctx.ptr, rc)
-    return res
-
+# (the stream binder and context resolver under their earlier names: the layer tests launch kernels through them)
+from ._context import bind_stream as _bind_stream, resolve_ctx as _resolve_ctx  # noqa: F401
+from .nn_layers import (Options, bias_relu, conv1_bias_relu, conv64_bias_relu, desc_normalize, heat_softmax, nn_descriptors,  # noqa: F401
+                        nn_select, nn_select_list, pack_conv3x3_weight)
 
 MODEL_TYPES = ("kSuperpointHeatmap", "kSuperpointNms", "kDiskHeatmap", "kDiskNms")  # ModelType (:15-20)
 DESCRIPTOR_DIM = {"superpoint": 256, "disk": 128}  # SuperpointDescriptorType / DiskDescriptorType

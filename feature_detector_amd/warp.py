@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import fd_warp_opts
 from ._slots import outputs, ptr
-from .points import Context, _bind_stream, _frames, _is_torch_device_tensor, _resolve_ctx
+from ._context import Context, as_frames, invoke, is_device_tensor, resolve_ctx
 
 MODELS = {"homography": (_lib.FD_WARP_HOMOGRAPHY, 9), "camera": (_lib.FD_WARP_CAMERA, 22)}
 
@@ -57,9 +57,9 @@ def warp_frames(frames, params, out_shape=None, model: str = "homography", fill:
     if model not in MODELS:
         raise ValueError(f"model must be one of {sorted(MODELS)}")
     kind, per = MODELS[model]
-    fptr, f_dev, b, rows, cols, keep = _frames(frames)
-    p_dev = _is_torch_device_tensor(params)
-    ctx = _resolve_ctx(ctx, keep, params)
+    _, f_dev, b, rows, cols, keep = as_frames(frames)
+    p_dev = is_device_tensor(params)
+    ctx = resolve_ctx(ctx, keep, params)
     if p_dev:
         import torch
 
@@ -84,9 +84,6 @@ def warp_frames(frames, params, out_shape=None, model: str = "homography", fill:
     if out_rows == 0 or out_cols == 0:  # nothing to write (an empty array has no pointer to pass)
         return (o[0], o[1]) if return_mask else o[0]
     opts = fd_warp_opts(kind, 1 if len(shape) == 1 else 0, int(fill))
-    _bind_stream(ctx, on_dev or p_dev)
-    rc = _lib.load().fd_frames_warp(ctx.ptr, ctypes.c_void_p(fptr), f_dev, b, rows, cols, ctypes.byref(opts), ptr(p),
-                                    1 if p_dev else 0, out_rows, out_cols, ptr(o[0]), ptr(o[1]) if return_mask else None,
-                                    1 if on_dev else 0)
-    _lib.check(ctx.ptr, rc)
+    invoke(ctx, on_dev or p_dev, "fd_frames_warp", ptr(keep), f_dev, b, rows, cols, ctypes.byref(opts), ptr(p), 1 if p_dev else 0,
+           out_rows, out_cols, ptr(o[0]), ptr(o[1]) if return_mask else None, 1 if on_dev else 0)
     return (o[0], o[1]) if return_mask else o[0]

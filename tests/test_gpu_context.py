@@ -51,7 +51,7 @@ def test_alternating_streams_on_one_context(fd, oracle):
 
 def test_context_device_mismatch_is_an_error(fd):
     torch = pytest.importorskip("torch")
-    from feature_detector_amd.points import _resolve_ctx
+    from feature_detector_amd._context import resolve_ctx as _resolve_ctx
 
     class OtherDevice:  # a context object claiming another GPU
         device = 1
